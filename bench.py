@@ -2,6 +2,7 @@
 """Headline benchmark: wavefronts/s through the 20-surface SYN20 chain.
 
     python bench.py --gpus 1 --steps 20 --warmup 3           # 4096^2 complex128 (default)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   # ... and what the last timed step computed (.npy)
     python bench.py --gpus N --steps K --warmup W            # starts its own N ranks (one process per GPU, no torch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W   # ... or joins the ranks a launcher started
@@ -641,6 +642,59 @@ def write_detail(full, path):
         return None
 
 
+DUMP_LIMIT = 60_000_000  # bytes: what --dump-outputs may write in all (under 64 MB however the directory is counted)
+DUMP_SEED = 20210914     # the pixels psf_sample.npy holds: default_rng(DUMP_SEED) over the grid
+
+
+def dump_shape(n, nb, records_bytes=0):
+    """(c, s) of --dump-outputs for ``nb`` PSFs of n x n: the central c x c pixels (c <= 256) and s seeded pixels of each,
+    float64, the largest that fit into DUMP_LIMIT bytes beside ``records_bytes`` of records (4 KB kept for the headers)."""
+    import math
+
+    per_item = max(0, (DUMP_LIMIT - records_bytes - 4096) // (8 * nb))
+    c = min(n, 256, math.isqrt(per_item // 2))
+    return c, min(n * n, per_item - c * c)
+
+
+def dump_outputs(dev, results, path):
+    """--dump-outputs: what the timed path hands its caller in one step (``results``: run_batch's list, the PSFs kept in
+    ``dev``), as float64 .npy files under ``path``, at most DUMP_LIMIT bytes in all:
+      records.npy     one row per wavefront: its saved surfaces as paos_amd.dist packs them for the gather (surface number,
+                      wl, dx, dy, wz, distancetofocus, 1 / fratio, extent, propagator code, power, ABCD factors); the
+                      f-ratio goes in as its reciprocal D/f, 0 for a collimated beam, so that every entry is finite
+      psf_centre.npy  the central c x c pixels of every wavefront's PSF (|u|^2 behind the last surface)
+      psf_sample.npy  the same PSFs at s pixels drawn by default_rng(DUMP_SEED) over the whole grid, in raster order
+    (c, s: dump_shape).  The powers are fetched, so their tickets are spent.  Returns the bytes written."""
+    import numpy as np
+
+    from paos_amd.dist import _pack_result
+
+    for i, res in enumerate(results):
+        for rec in res.values():
+            if "power_ticket" in rec:
+                rec["power"] = float(dev.norm2_fetch(rec["power_ticket"])[i])
+    records = np.array([_pack_result(i, {num: dict(rec, fratio=1.0 / float(rec["fratio"])) for num, rec in res.items()})
+                        for i, res in enumerate(results)], dtype=np.float64)
+    if not np.isfinite(records).all():
+        raise ValueError("--dump-outputs: a record of the last step is not finite")
+    n, nb = dev.n, len(results)
+    c, s = dump_shape(n, nb, records.nbytes)
+    pixels = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n * n, s))
+    lo = (n - c) // 2
+    centre, sample = np.empty((nb, c, c)), np.empty((nb, s))
+    for i in range(nb):
+        psf = dev.psf_fetch(i)
+        centre[i] = psf[lo:lo + c, lo:lo + c]
+        sample[i] = psf.ravel()[pixels]
+    os.makedirs(path, exist_ok=True)
+    written = 0
+    for name, arr in (("records", records), ("psf_centre", centre), ("psf_sample", sample)):
+        np.save(os.path.join(path, name + ".npy"), arr)
+        written += os.path.getsize(os.path.join(path, name + ".npy"))
+    assert written <= DUMP_LIMIT, written
+    return written
+
+
 def sweep_report(m):
     """What the walked sweep did to the context's kept aperture line records, per timed step."""
     sets = m["per_step_sets"]
@@ -752,7 +806,12 @@ def main(argv=None):
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
                     help="where the detailed record goes (classes of launch, sweep, other kernels, side measurements, extras); "
                          "stdout carries the contract line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's wavefronts) to DIR/*.npy: records.npy, "
+                         "psf_centre.npy, psf_sample.npy (float64, at most 60 MB; see dump_outputs)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.batch <= 0:
         # 8 -> 32 wavefronts per step is +3 % (launch tails and host work amortised; 64: +0.3 % more): 217 -> 224 at 4096^2
         args.batch = max(32, 32 * (4096 // args.grid) ** 2)
@@ -820,6 +879,8 @@ def main(argv=None):
     # the power behind the last surface of the last step (a sanity figure of the line); its tickets are given back here
     last = m.pop("res")
     power_check = float(dev.norm2_fetch(last[0][20]["power_ticket"])[0])
+    if args.dump_outputs and rank == 0:  # (before anything else runs on the context: the kept PSFs are the last step's)
+        dump_outputs(dev, last, args.dump_outputs)
     for t in {rec["power_ticket"] for r in last for rec in r.values() if "power_ticket" in rec} - {last[0][20]["power_ticket"]}:
         dev.norm2_release(t)
     if args.traffic_child:  # measure_traffic's child: one step, every dispatch of which is counted
