@@ -334,6 +334,36 @@ int paos_zernike_gram(paos_ctx* ctx, int nmax, int kdim, const double* table, co
 int paos_zernike_pupil(paos_ctx* ctx, int nmax, int kdim, const double* table, const double* params,
                        int param_stride, double* host_wfe);
 
+/* ---- broadband PSFs on a detector pixel grid (docs/source/user/montecarlo/index.rst, "Multi-wavelength simulations") -- */
+/* No reference counterpart: the reference hands out each wavelength's PSF on its own sampling and leaves the rebinning to
+ * the user.  Definitions (README.md, "Detector images"):
+ *   grid column j of item i spans [(j - N/2 - 1/2) dx_i, (j - N/2 + 1/2) dx_i] (wfo.py:236-237, run.py:443: a pixel centre
+ *   at x / dx + N/2); row k likewise with dy_i.  Detector column m spans [xc + (m - nx/2) pitch_x, xc + (m + 1 - nx/2) pitch_x],
+ *   row n likewise with yc, pitch_y; images are [ny][nx] doubles, rows along y (as paos_export / paos_psf_fetch).
+ *   fx_i(j, m) = |grid column j  ^  detector column m| / dx_i, fy_i(k, n) likewise, and the per-item image
+ *   A_i[n][m] = sum_k sum_j PSF_i[k][j] fy_i(k, n) fx_i(j, m): flux-conserving rebinning of a PSF that is constant within
+ *   each grid pixel.  Energy outside the detector is dropped; detector area outside the grid receives nothing.
+ *   The accumulator is updated once per item, in ascending item order, in fp64: image <- image + w_i A_i (no atomics,
+ *   every sum in a fixed order: splitting a sweep into batches differently changes no bit when the PSFs are the same).
+ * The PSF read is the context's kept buffer (paos_psf_keep, paos_psf_keep_power or a pass program with final_intensity),
+ * doubles in fp32 contexts too; rebinning and accumulator are fp64.  Only the grid rows and columns under each item's
+ * detector footprint are read.  Scratch is allocated on first use and freed by paos_ctx_destroy; when the scratch of a whole
+ * batch would exceed 512 MiB (PAOS_DETECTOR_SCRATCH_MIB) the items are processed in chunks, in item order. */
+enum { PAOS_DETECTOR_GEOM = 6 };  /* nx, ny, pitch_x, pitch_y, xc, yc (metres, image-plane coordinates) */
+enum { PAOS_DETECTOR_ITEM = 3 };  /* dx, dy, w: the item's pitch at the last surface and its weight */
+enum { PAOS_DETECTOR_SCRATCH_MIB = 512 };
+/* Set the detector geometry (geom[PAOS_DETECTOR_GEOM]) and zero the accumulator.  nx, ny: integers in 1..4096; pitches
+ * finite and positive; centre finite -- otherwise PAOS_EINVAL.  Does not read the PSF buffer. */
+int paos_detector_begin(paos_ctx* ctx, const double* geom);
+/* image <- image + w_i A_i for i = 0 .. batch-1 in order, from the kept PSFs; per_item[batch][PAOS_DETECTOR_ITEM].
+ * Enqueues only (no synchronisation).  PAOS_EINVAL before paos_psf_keep or paos_detector_begin, or for a dx / dy that is
+ * not finite and positive or a weight that is not finite. */
+int paos_detector_add(paos_ctx* ctx, const double* per_item);
+/* A_i of every item to host_out[batch][ny][nx] (per_item as above, w not read; Monte-Carlo studies).  Synchronises. */
+int paos_detector_images(paos_ctx* ctx, const double* per_item, double* host_out);
+/* the accumulator to host_out[ny][nx].  Synchronises. */
+int paos_detector_fetch(paos_ctx* ctx, double* host_out);
+
 #ifdef __cplusplus
 }
 #endif

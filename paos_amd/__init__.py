@@ -18,7 +18,8 @@ from .zernike import Zernike
 
 from .raytrace import raytrace
 
-__all__ = ["ABCD", "WFO", "Zernike", "coordinate_break", "parse_config", "raytrace", "run_batch", "run_sharded"]
+__all__ = ["ABCD", "Detector", "WFO", "Zernike", "coordinate_break", "parse_config", "raytrace", "run_batch",
+           "run_broadband", "run_sharded"]
 __version__ = "0.1.0"
 
 
@@ -32,6 +33,8 @@ def __getattr__(name):
         return importlib.import_module(".wfo", __name__).WFO
     if name == "run_batch":
         return importlib.import_module(".run", __name__).run_batch
+    if name in ("Detector", "run_broadband"):
+        return getattr(importlib.import_module(".detector", __name__), name)
     if name == "run_sharded":
         return importlib.import_module(".dist", __name__).run_sharded
     raise AttributeError(name)

@@ -115,6 +115,10 @@ SYMBOLS = {
     "paos_norm2_enqueue_rows_like": (ctypes.c_int, [_c_ctx, _dbl_p, _dbl_p, ctypes.POINTER(ctypes.c_int)]),
     "paos_run_program": (ctypes.c_int, [_c_ctx, ctypes.POINTER(Pass), ctypes.c_int, _dbl_p, ctypes.c_int,
                                         ctypes.POINTER(ProgramOpts)]),
+    "paos_detector_begin": (ctypes.c_int, [_c_ctx, _dbl_p]),
+    "paos_detector_add": (ctypes.c_int, [_c_ctx, _dbl_p]),
+    "paos_detector_images": (ctypes.c_int, [_c_ctx, _dbl_p, _dbl_p]),
+    "paos_detector_fetch": (ctypes.c_int, [_c_ctx, _dbl_p]),
 }
 
 _lib = None
@@ -249,6 +253,7 @@ class DeviceFields:
         self._lib = load()
         _HIP_TOUCHED[0] = True
         self._ctx = _c_ctx()
+        self.detector = None  # the geometry of the last detector_begin
         self.n, self.batch = int(n), int(batch)
         if precision not in ("fp64", "fp32"):
             raise ValueError("precision must be 'fp64' or 'fp32'")
@@ -368,6 +373,45 @@ class DeviceFields:
     def psf_fetch(self, item=0):
         out = np.empty((self.n, self.n), dtype=np.float64)
         self._check(self._lib.paos_psf_fetch(self._ctx, int(item), _dptr(out)), "paos_psf_fetch")
+        return out
+
+    # -- detector pixel grid (paos_detector_*: README.md, "Detector images") ----------------------------------------
+    def _detector_items(self, dxs, dys, weights=None):
+        d = np.empty((self.batch, 3), dtype=np.float64)
+        d[:, 0] = np.broadcast_to(np.asarray(dxs, dtype=np.float64), (self.batch,))
+        d[:, 1] = np.broadcast_to(np.asarray(dys, dtype=np.float64), (self.batch,))
+        d[:, 2] = 0.0 if weights is None else np.broadcast_to(np.asarray(weights, dtype=np.float64), (self.batch,))
+        return d
+
+    def detector_begin(self, det):
+        """Set the detector geometry (a :class:`paos_amd.detector.Detector`) and zero the accumulator."""
+        geom = np.ascontiguousarray(det.geometry(), dtype=np.float64)
+        self._check(self._lib.paos_detector_begin(self._ctx, _dptr(geom)), "paos_detector_begin")
+        self.detector = det
+
+    def detector_add(self, dxs, dys, weights):
+        """image += w_i A_i for every item in order, from the kept PSFs (``dxs`` / ``dys``: each item's pitch at the
+        last surface).  Enqueued only: nothing synchronises."""
+        d = self._detector_items(dxs, dys, weights)
+        self._check(self._lib.paos_detector_add(self._ctx, _dptr(d)), "paos_detector_add")
+
+    def detector_images(self, dxs, dys):
+        """A_i of every item, (batch, ny, nx) float64.  Synchronises."""
+        d = self._detector_items(dxs, dys)
+        det = getattr(self, "detector", None)
+        if det is None:
+            raise PaosHipError("paos_detector_images failed: no detector (detector_begin)")
+        out = np.empty((self.batch, det.ny, det.nx), dtype=np.float64)
+        self._check(self._lib.paos_detector_images(self._ctx, _dptr(d), _dptr(out)), "paos_detector_images")
+        return out
+
+    def detector_fetch(self):
+        """The accumulated image, (ny, nx) float64.  Synchronises."""
+        det = getattr(self, "detector", None)
+        if det is None:
+            raise PaosHipError("paos_detector_fetch failed: no detector (detector_begin)")
+        out = np.empty((det.ny, det.nx), dtype=np.float64)
+        self._check(self._lib.paos_detector_fetch(self._ctx, _dptr(out)), "paos_detector_fetch")
         return out
 
     # -- operators ------------------------------------------------------------------

@@ -1,0 +1,132 @@
+"""Broadband PSFs on a detector pixel grid, integrated on the GPU.
+
+The reference's user guide puts multi-wavelength runs first (docs/source/user/montecarlo/index.rst, "Multi-wavelength
+simulations"); the product of such a run is one image on the instrument's pixels.  Each wavelength's PSF comes out on
+its own sampling (``dx`` and ``dy`` at the image plane scale with the wavelength), so the PSFs are rebinned onto a common
+detector grid before they are added.  The rebinning runs on the device, from the PSFs the walk keeps in HBM
+(``keep_psf``), into an accumulator that stays there across the batches of a sweep (include/paos_hip.h,
+``paos_detector_*``).
+
+Definition (README.md, "Detector images"):
+
+* Grid column ``j`` of item ``i`` spans ``[(j - N/2 - 1/2) dx_i, (j - N/2 + 1/2) dx_i]`` (the pixel-centre convention of
+  wfo.py:236-237 and run.py:443); row ``k`` likewise with ``dy_i``.
+* Detector column ``m`` spans ``[xc + (m - nx/2) pitch_x, xc + (m + 1 - nx/2) pitch_x]``; row ``n`` likewise with ``yc``
+  and ``pitch_y``.  Images are ``(ny, nx)`` float64 arrays, rows along ``y`` (as ``download`` and ``psf_fetch``).
+* ``fx_i(j, m)`` is the length of the overlap of grid column ``j`` and detector column ``m`` divided by ``dx_i``;
+  ``fy_i(k, n)`` likewise along ``y``.
+* ``A_i[n, m] = sum_k sum_j PSF_i[k, j] fy_i(k, n) fx_i(j, m)``: exact, flux-conserving rebinning of a PSF that is
+  constant within each grid pixel.  Energy outside the detector is dropped; detector area outside the grid receives
+  nothing.
+* The broadband image is updated once per item, in ascending item order, in fp64: ``image <- image + w_i A_i``.  No
+  float atomics: splitting a sweep into batches differently changes no bit, provided the PSFs are bit-identical.
+"""
+import math
+from dataclasses import dataclass
+from numbers import Integral, Real
+
+import numpy as np
+
+MAX_PIXELS = 4096  # per axis (paos_detector_begin)
+
+
+@dataclass(frozen=True)
+class Detector:
+    """A detector pixel grid in the image plane: ``ny`` rows and ``nx`` columns of ``pitch_x`` x ``pitch_y`` metres
+    (``pitch_y`` defaults to ``pitch_x``), centred on ``(xc, yc)`` metres."""
+
+    nx: int
+    ny: int
+    pitch_x: float
+    pitch_y: float = None
+    xc: float = 0.0
+    yc: float = 0.0
+
+    def __post_init__(self):
+        for name in ("nx", "ny"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, Integral) or not 1 <= int(v) <= MAX_PIXELS:
+                raise ValueError(f"{name} must be an integer in 1..{MAX_PIXELS}, got {v!r}")
+            object.__setattr__(self, name, int(v))
+        if self.pitch_y is None:
+            object.__setattr__(self, "pitch_y", self.pitch_x)
+        for name in ("pitch_x", "pitch_y", "xc", "yc"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, Real) or not math.isfinite(float(v)):
+                raise ValueError(f"{name} must be a finite number, got {v!r}")
+            object.__setattr__(self, name, float(v))
+        if self.pitch_x <= 0.0 or self.pitch_y <= 0.0:
+            raise ValueError("detector pitches must be positive")
+
+    def geometry(self):
+        """The parameter block of ``paos_detector_begin``: nx, ny, pitch_x, pitch_y, xc, yc."""
+        return np.array([self.nx, self.ny, self.pitch_x, self.pitch_y, self.xc, self.yc], dtype=np.float64)
+
+
+def run_broadband(pupil_diameter, wavelengths, weights, gridsize, zoom, field, opt_chains, detector, batch=32,
+                  precision="fp64", device=0):
+    """The broadband image of a wavelength sweep on ``detector``: ``sum_i w_i A_i`` over ``wavelengths[i]`` /
+    ``weights[i]`` (``opt_chains``: one chain per wavelength, or one chain for all; their last surface must be saved).
+
+    The sweep is walked in blocks of ``batch`` on one device context, each block issued as ``bench.measure`` issues a
+    step (``run_batch`` with ``outputs=()``, the lean walk, ``keep_psf``, no synchronisation) and followed by
+    ``detector_add``.  A last block that is short is filled up with its last wavelength at weight 0, which adds exact
+    zeros.  Returns ``{"image": (ny, nx) float64, "power": sum_i w_i P_i (P_i: sum |u|^2 at the last surface),
+    "wavelengths", "weights"}``; the image crosses to the host once, at the end."""
+    from . import _lib
+    from .run import run_batch
+
+    if not isinstance(detector, Detector):
+        raise TypeError("detector must be a paos_amd.detector.Detector")
+    wls = [float(w) for w in wavelengths]
+    nw = len(wls)
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if nw == 0 or w.size != nw:
+        raise ValueError("one weight per wavelength is required (and at least one wavelength)")
+    if not np.all(np.isfinite(w)):
+        raise ValueError("weights must be finite")
+    chains = [opt_chains] * nw if isinstance(opt_chains, dict) else list(opt_chains)
+    if len(chains) != nw:
+        raise ValueError("one chain per wavelength (or a single chain) is required")
+    if int(batch) < 1:
+        raise ValueError("batch must be >= 1")
+    nb = min(int(batch), nw)
+    dev = _lib.DeviceFields(int(gridsize), nb, precision, device)
+    try:
+        dev.detector_begin(detector)
+        pending = []  # (the powers of a block's last surface, or their handle; that block's weights)
+        power = 0.0
+
+        def settle(entry):
+            p, wb = entry
+            p = p.fetch() if hasattr(p, "fetch") else p
+            return sum(float(wb[i]) * float(p[i]) for i in range(len(wb)))
+
+        for b0 in range(0, nw, nb):
+            idx = list(range(b0, min(b0 + nb, nw)))
+            pad = nb - len(idx)
+            wl_blk = [wls[i] for i in idx] + [wls[idx[-1]]] * pad
+            ch_blk = [chains[i] for i in idx] + [chains[idx[-1]]] * pad
+            w_blk = np.concatenate([w[idx], np.zeros(pad)])
+            res = run_batch(pupil_diameter, wl_blk, gridsize, zoom, field, ch_blk, precision=precision, device=device,
+                            outputs=(), dev=dev, sync=False, keep_psf=True, detector=detector, detector_weights=w_blk)
+            num = _last_num(ch_blk[0])
+            handle = res[0][num].get("power_ticket")
+            # every other reduction of the block is given back unread (as bench.measure does)
+            others = {id(t._red): t for r in res for rec in r.values() for t in [rec.get("power_ticket")] if t is not None}
+            for t in others.values():
+                if handle is None or t._red is not handle._red:
+                    t.release()
+            pending.append((handle if handle is not None else [r[num]["power"] for r in res], w_blk))
+            if len(pending) >= _lib.NORM_SLOTS // 2:  # a long sweep: keep the library's ticket ring from filling
+                power += settle(pending.pop(0))
+        image = dev.detector_fetch()
+        for entry in pending:
+            power += settle(entry)
+    finally:
+        dev.close()
+    return {"image": image, "power": power, "wavelengths": np.asarray(wls), "weights": w.copy()}
+
+
+def _last_num(chain):
+    return chain[list(chain.keys())[-1]]["num"]

@@ -1115,7 +1115,7 @@ def run(pupil_diameter, wavelength, gridsize, zoom, field, opt_chain, precision=
 
 def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, precision="fp64",
               device=0, outputs=("psf",), dev=None, sync=True, stats=None, metrics_radii_px=None,
-              keep_psf=False, power=True):
+              keep_psf=False, power=True, detector=None, detector_weights=None):
     """Propagate ``B = len(opt_chains)`` wavefronts together on one GPU.
 
     ``wavelengths[i]`` / ``opt_chains[i]`` describe wavefront ``i`` (chains must
@@ -1135,6 +1135,13 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     reduction per saved surface (the reference does not return it; chains that save a dozen
     surfaces spend 7 % of their time there).  ``dev`` may pass a pre-allocated
     ``DeviceFields(gridsize, B)`` to reuse across calls.
+
+    ``detector`` (a :class:`paos_amd.detector.Detector`) rebins every item's PSF at the LAST surface of the chain, which
+    must be saved (``ValueError`` otherwise), onto that detector pixel grid on the GPU (README.md, "Detector images"; it
+    implies ``keep_psf``).  With ``detector_weights`` (one per item) ``w_i A_i`` is added, item after item, into the
+    accumulator of ``dev`` (``dev.detector_fetch()`` reads it; a ``dev`` that is not on that detector yet is started
+    there, ``dev.detector_begin``): nothing synchronises.  Without weights each item's record of the last surface gets
+    ``'detector'``, its image ``A_i`` as a (ny, nx) float64 array.
     """
     nb = len(opt_chains)
     if len(wavelengths) != nb:
@@ -1144,6 +1151,21 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     unknown = set(outputs) - {"psf", "wfo", "amplitude", "phase"}
     if unknown:
         raise ValueError(f"unknown outputs {sorted(unknown)}")
+    last_key = list(opt_chains[0].keys())[-1] if len(opt_chains[0]) else None
+    det_pitch = None
+    if detector is not None:
+        if last_key is None or not all(chain[last_key]["save"] for chain in opt_chains):
+            raise ValueError("a detector needs the last surface of the chain to be saved")
+        if detector_weights is not None:
+            detector_weights = np.asarray(detector_weights, dtype=np.float64).reshape(-1)
+            if detector_weights.size != nb:
+                raise ValueError("one detector weight per chain is required")
+            if dev is None:
+                raise ValueError("detector_weights accumulate into `dev`: pass a DeviceFields that outlives the call")
+        keep_psf = True
+        det_pitch = [None] * nb
+    elif detector_weights is not None:
+        raise ValueError("detector_weights without a detector")
     states = [_Item(pupil_diameter, wl, gridsize, zoom, field) for wl in wavelengths]
     own = dev is None
     if own:
@@ -1154,7 +1176,6 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     what = {"psf": _lib.WHAT_INTENSITY, "wfo": _lib.WHAT_FIELD, "amplitude": _lib.WHAT_AMPLITUDE,
             "phase": _lib.WHAT_PHASE}
 
-    last_key = list(opt_chains[0].keys())[-1] if len(opt_chains[0]) else None
     # nobody reads an array at a saved surface: the walk may skip writing dead rows at the start and store the PSF
     # straight from the last pass (csrc/frugal_pass.h: STORE)
     lean = _WalkState() if (not outputs and metrics_radii_px is None) else None
@@ -1213,6 +1234,9 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
             for i, rec in pending:
                 rec["metrics"] = met[i]
         keep = keep_psf and key == last_key
+        if det_pitch is not None and key == last_key:
+            for i, plan in enumerate(plans):
+                det_pitch[i] = (plan["scalars"]["dx"], plan["scalars"]["dy"])
         # the last pass has stored |u|^2 and enqueued its sum -- for this surface, or for good (inert surfaces behind it)
         fused = (lean.psf_ticket if lean.psf_ticket is not None else lean.final_ticket) if lean is not None else None
         rows = lean.rows if lean is not None else None
@@ -1254,6 +1278,17 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     try:
         _walk(dev, states, list(opt_chains), on_saved, stats=stats, fresh=1.0 + 0.0j, lean=lean,
               psf_at=last_key if (keep_psf and lean is not None) else None, power_state=power_state)
+        if detector is not None:  # the kept PSFs of the last surface onto the detector (include/paos_hip.h)
+            dxs = [p[0] for p in det_pitch]
+            dys = [p[1] for p in det_pitch]
+            if getattr(dev, "detector", None) != detector:
+                dev.detector_begin(detector)
+            if detector_weights is not None:
+                dev.detector_add(dxs, dys, detector_weights)
+            else:
+                images = dev.detector_images(dxs, dys)
+                for i in range(nb):
+                    results[i][opt_chains[i][last_key]["num"]]["detector"] = images[i]
         if sync or own:
             drain()
         else:  # caller synchronises later: hand out handles to the reductions still outstanding (nothing waits here)
