@@ -159,13 +159,17 @@ struct FrugalArgs {
 // were 40 % of the vector instructions of a two-transform pass, and these passes run at the rate
 // the fp64 pipe (and the power cap that throttles it) allows (profiles/r02_timeline_*.txt).
 constexpr int kCircleLds = 256;
-__device__ __forceinline__ void sincos_tab(double a, const cx<double>* circle, double* sn, double* cs) {
+// `tail`: a small exact correction of the argument (slot_factor<2>: the rounding error of a sum of two arguments, up to
+// ulp(a) / 2 ~ 6e-5 rad at 1e12), added to the reduced argument, where it is exact to 1e-20.
+template <bool TAIL = false>
+__device__ __forceinline__ void sincos_tab(double a, const cx<double>* circle, double* sn, double* cs, double tail = 0.0) {
   const double kMagic = 6755399441055744.0;  // 1.5 * 2^52: the integer lands in the low mantissa bits
   const double nb = fma(a, 40.743665431525205956834243423363677, kMagic);  // 128 / pi
   const unsigned j = (unsigned)__double2loint(nb) & (unsigned)(kCircleLds - 1);
   const double n = nb - kMagic;
   double r = fma(-n, 2.45436926061702596754894014318e-02, a);   // hi(pi / 128)
   r = fma(-n, 9.56755311833869697380e-19, r);                   // lo(pi / 128)
+  if constexpr (TAIL) r = __dadd_rn(r, tail);
   const cx<double> c = circle[j];
   const double z = r * r;
   const double ps = fma(z, 8.33333333333333333333e-03, -1.66666666666666666667e-01);
@@ -237,9 +241,10 @@ __device__ __forceinline__ cx<double> slot_factor(const double* g, const double*
   cx<double> p = {1.0, 0.0};
   if constexpr (K == 2 && PAOS_MERGE_PHASES != 0) {
     // Two phases of one slot through ONE sincos: exp(i q0) exp(i q1) = exp(i (q0 + q1)).  The sum of the two rounded
-    // arguments is taken exactly (TwoSum: a = fl(q0 + q1), e = q0 + q1 - a, |e| <= ulp(a) / 2 ~ 1e-10 at 1e6 rad)
-    // and the tail applied to first order, exp(i (a + e)) = exp(i a) (1 + i e) + O(e^2 ~ 1e-20): 12 + 6 + 17 + 2
-    // instructions instead of 2 x 23 + 4.  (Each argument is still the reference's rounded one.)
+    // arguments is taken exactly (TwoSum: a = fl(q0 + q1), e = q0 + q1 - a, |e| <= ulp(a) / 2 ~ 6e-5 at 1e12 rad)
+    // and the tail joins the argument after its reduction, where r + e is exact to 1e-20 (a first-order tail,
+    // exp(i a) (1 + i e), is off by e^2 / 2: ~1e-9 at 1e12 rad): 12 + 6 + 18 instructions instead of 2 x 23 + 4.
+    // (Each argument is still the reference's rounded one.)
     const double x0 = __dmul_rn(g[0], step[0]);
     const double q0 = __dmul_rn(m2[0], __dmul_rn(coefq[0], __dadd_rn(__dmul_rn(x0, x0), across2[0])));
     const double x1 = __dmul_rn(g[1], step[1]);
@@ -248,8 +253,8 @@ __device__ __forceinline__ cx<double> slot_factor(const double* g, const double*
     const double bb = __dsub_rn(a, q0);
     const double e = __dadd_rn(__dsub_rn(q0, __dsub_rn(a, bb)), __dsub_rn(q1, bb));
     double sn, cs;
-    sincos_tab(a, circle, &sn, &cs);
-    return cx<double>{fma(-e, sn, cs), fma(e, cs, sn)};
+    sincos_tab<true>(a, circle, &sn, &cs, e);
+    return cx<double>{cs, sn};
   }
 #pragma unroll
   for (int j = 0; j < K; ++j) {
@@ -267,27 +272,39 @@ __device__ __forceinline__ cx<double> slot_factor(const double* g, const double*
   return p;
 }
 
-// The same factor in fp32 mode (complex64 fields): the argument in TURNS, still formed in fp64 (it reaches 1e5 turns), one
-// fraction, then the hardware sin / cos (inputs in revolutions).  turn_coef[j] = m2 coef / 2 pi (the sign rides on coef).
-// Shared by frugal_slot and phase_table_kernel like slot_factor.
+// The same factor in fp32 mode (complex64 fields): the argument formed in fp64 exactly as slot_factor forms it (the
+// reference's roundings), reduced by 2 pi in fp64 (two-term Cody-Waite with FMA: good to ~4e-16 rad for |q| < 1e12,
+// where a product in turns would already be off by ulp(1.6e11 turns) ~ 1e-4 rad), then one fraction of a turn in
+// [-1/2, 1/2] and the hardware sin / cos (inputs in revolutions).  Shared by frugal_slot and phase_table_kernel like
+// slot_factor.
+__device__ __forceinline__ float turn_fraction(double q) {
+  const double k = rint(q * 0.15915494309189535);  // 1 / 2 pi
+  double r = fma(-k, 6.283185307179586, q);        // hi(2 pi)
+  r = fma(-k, 2.4492935982947064e-16, r);          // lo(2 pi)
+  return (float)(r * 0.15915494309189535);
+}
 template <int K>
 __device__ __forceinline__ cx<float> slot_factor32(const double* g, const double* step, const double* across2,
-                                                   const double* turn_coef) {
+                                                   const double* coefq, const double* m2) {
   cx<float> p = {1.0f, 0.0f};
   if constexpr (K == 2 && PAOS_MERGE_PHASES != 0) {
-    // two phases of one slot: their turns add in fp64 (1e5 turns to 1e-11, the field carries 1e-7), then ONE
-    // fraction and ONE hardware sin / cos instead of two of each and a rotation
-    const double x0 = g[0] * step[0];
-    const double x1 = g[1] * step[1];
-    const double turns = fma(fma(x0, x0, across2[0]), turn_coef[0], fma(x1, x1, across2[1]) * turn_coef[1]);
-    const float frac = (float)(turns - floor(turns));
+    // two phases of one slot: their arguments add exactly (TwoSum, as slot_factor<2>), then ONE reduction and ONE
+    // hardware sin / cos instead of two of each and a rotation
+    const double x0 = __dmul_rn(g[0], step[0]);
+    const double q0 = __dmul_rn(m2[0], __dmul_rn(coefq[0], __dadd_rn(__dmul_rn(x0, x0), across2[0])));
+    const double x1 = __dmul_rn(g[1], step[1]);
+    const double q1 = __dmul_rn(m2[1], __dmul_rn(coefq[1], __dadd_rn(__dmul_rn(x1, x1), across2[1])));
+    const double a = __dadd_rn(q0, q1);
+    const double bb = __dsub_rn(a, q0);
+    const double e = __dadd_rn(__dsub_rn(q0, __dsub_rn(a, bb)), __dsub_rn(q1, bb));
+    const float frac = turn_fraction(a) + (float)(e * 0.15915494309189535);
     return cx<float>{__builtin_amdgcn_cosf(frac), __builtin_amdgcn_sinf(frac)};
   }
 #pragma unroll
   for (int j = 0; j < K; ++j) {
-    const double x = g[j] * step[j];
-    const double turns = fma(x, x, across2[j]) * turn_coef[j];
-    const float frac = (float)(turns - floor(turns));
+    const double x = __dmul_rn(g[j], step[j]);
+    const double q = __dmul_rn(m2[j], __dmul_rn(coefq[j], __dadd_rn(__dmul_rn(x, x), across2[j])));
+    const float frac = turn_fraction(q);
     const float snf = __builtin_amdgcn_sinf(frac), csf = __builtin_amdgcn_cosf(frac);
     p = j == 0 ? cx<float>{csf, snf} : cmul_after_trans(p, cx<float>{csf, snf});
   }
@@ -428,19 +445,19 @@ __device__ __forceinline__ void frugal_slot(cx<T>* v, const FrugalSlot& sl, cons
   const int mbase = (tpos == 0 ? TL : 0) + mt;          // + (E - 1 - k) TL: where element k's factor was left
   if constexpr (sizeof(T) == 4) {
     // fp32 mode: the field carries ~1e-7, so the phase needs no more than that -- but its ARGUMENT
-    // reaches 1e6 rad and is still formed in fp64: in turns, s * (m2 coef / 2 pi), one fraction
-    // instruction, then the hardware sin / cos (inputs in revolutions) and an fp32 rotation.  No
+    // reaches 1e12 rad and is still formed and reduced in fp64 (slot_factor32), then the hardware
+    // sin / cos (inputs in revolutions) and an fp32 rotation.  No
     // fp64 copy of the element: 8 temporaries instead of 14, which is what lets the kernel keep to
     // the register budget of three workgroups per CU.
-    double turn_coef[KK];
+    double m2s32[KK];
 #pragma unroll
-    for (int j = 0; j < K; ++j) turn_coef[j] = ph[j].m2 * coefq[j] * 0.15915494309189535;  // / 2 pi; coef carries the sign
+    for (int j = 0; j < K; ++j) m2s32[j] = ph[j].m2;
     const float ff = (float)f, ffy = (float)fy;
     auto factor32 = [&](int k) __attribute__((always_inline)) {
       double gk[KK];
 #pragma unroll
       for (int j = 0; j < K; ++j) gk[j] = (k < E / 2 ? g_lo[j] : g_hi[j]) + (double)(k * TL);
-      return slot_factor32<K>(gk, step, across2, turn_coef);
+      return slot_factor32<K>(gk, step, across2, coefq, m2s32);
     };
     if constexpr (K > 0 && TAB != 0) {  // TAB builds: the factors by position, from phase_table_kernel's table (cx<float> entries)
       static_assert(!SHARE, "a table slot does not stand for a barrier");
@@ -599,14 +616,11 @@ __global__ void __launch_bounds__(256) phase_table_kernel(PhaseTableArgs a) {
     m2[j] = q.m2;
   }
   if (a.f32) {
-    double turn_coef[kFrugalMaxMid];
-#pragma unroll
-    for (int j = 0; j < kFrugalMaxMid; ++j) turn_coef[j] = m2[j] * coefq[j] * 0.15915494309189535;
     cx<float> pf = {1.0f, 0.0f};
     if (K <= 0) {}
-    else if (K == 1) pf = slot_factor32<1>(g, step, across2, turn_coef);
-    else if (K == 2) pf = slot_factor32<2>(g, step, across2, turn_coef);
-    else pf = slot_factor32<3>(g, step, across2, turn_coef);
+    else if (K == 1) pf = slot_factor32<1>(g, step, across2, coefq, m2);
+    else if (K == 2) pf = slot_factor32<2>(g, step, across2, coefq, m2);
+    else pf = slot_factor32<3>(g, step, across2, coefq, m2);
     reinterpret_cast<cx<float>*>(const_cast<cx<double>*>(sl.table))[pos] = pf;
     return;
   }

@@ -1447,6 +1447,16 @@ int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const do
       for (int q = 0; q < n_passes; ++q) active = active || low[q].items[it].active != 0.0;
       need = !active;
     }
+    // ... and for an item whose window is empty: the planner takes an empty window for no window at all (plan_pruning),
+    // so its first pass would load every line of stale data
+    const double* windows[2] = {entry_rows, entry_cols};
+    for (int w = 0; w < 2 && !need; ++w)
+      for (int it = 0; windows[w] && it < c->batch && !need; ++it) {
+        const int br = c->br, l = ((int)windows[w][2 * it] / br) * br;
+        int h = (((int)windows[w][2 * it + 1] + br - 1) / br) * br;
+        if (h > c->n) h = c->n;
+        need = l >= h;
+      }
     if (need) {
       // (all items at once: the ones the planner handles lose nothing but a little time, and the planner was told
       // "stale", which is also right for zeros)
