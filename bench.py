@@ -1,11 +1,17 @@
 #!/usr/bin/env python3
 """Headline benchmark: wavefronts/s through the 20-surface SYN20 chain.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3           # 4096^2 complex128 (default)
+    python bench.py --gpus 1 --steps 20 --warmup 3           # 4096^2 complex128 (default): the headline only
     python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   # ... and what the last timed step computed (.npy)
+    python bench.py --gpus 1 --steps K --warmup W --full     # ... and every side measurement below (minutes)
     python bench.py --gpus N --steps K --warmup W            # starts its own N ranks (one process per GPU, no torch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W   # ... or joins the ranks a launcher started
+
+A plain run sets up, runs W warm-up and K timed steps, writes --dump-outputs if asked and prints the line: its `roofline`
+and `sweep` come from the launch records of the timed steps alone.  --full adds everything that takes runs of its own
+(marked [full] below): the CPU baselines, the counter children, the ptp probe, the copy yardstick, the variants of the
+same steps and the `extra` entries; --no-cpu-baseline / --no-extras / --no-traffic switch parts of it off again.
 
 A "step" propagates one batch of ``--batch`` wavefronts per GPU through all 20 surfaces on the HIP path; fields are
 created and stay in HBM.  The sweep is WALKED: step g (warm-up steps count) runs the wavelengths
@@ -19,34 +25,35 @@ only relays rank 0's line and the exit codes.  With N > 1 the run FAILS (exit 3)
 RCCL, unless --allow-tcp is given -- and still prints a JSON line then (`"value": null`, the transport, the ranks
 seen and every rank's bring-up note).  Rank 0 prints ONE JSON line of at most 4 KB as the last line of stdout
 (`contract_line`: the contract's keys, `roofline` for the dominant class of pass launch on the roofline that binds it,
-`cpu_baseline`) and writes everything else to bench_detail.json (`--detail`), where the record holds these entries:
+`cpu_baseline`) and writes everything else to `--detail` (with --full: bench_detail.json unless given), where the record
+holds these entries:
 
   roofline           the dominant kernel (the fused FFT pass): every pass launch of the timed region is bracketed by
                      HIP events on the context's stream (paos_profile_end_launches: time and class of each launch);
                      `achieved` = the bytes the library's pruning plan has those launches load + store (live lines x
                      (loaded + stored positions) x element size: paos_profile_planned_bytes -- for a launch that skips
-                     nothing: one read and one write of every element of the batch) / their summed duration; `dense` =
+                     nothing: one read and one write of every element of the batch) / their summed duration; [full] `dense` =
                      the same kernel with the pruning off for one step (every launch moves the whole batch: what rounds
                      1-3 reported as `achieved`); `classes` lists every class of launch (skipping tiles of dead lines /
                      loads of dead positions / stores nobody reads, storing the PSF, running two or three passes of a
                      row / column chain) with its mean time, planned bytes and -- from the counters -- the bytes it
-                     really moved; `all_launches` sums them over one step; `copy_yardstick` is measured in this run
-                     (paos_copy_yardstick); `traffic` = HBM bytes per launch from FETCH_SIZE / WRITE_SIZE, collected
+                     really moved; `all_launches` sums them over one step; [full] `copy_yardstick` is measured in this run
+                     (paos_copy_yardstick); [full] `traffic` = HBM bytes per launch from FETCH_SIZE / WRITE_SIZE, collected
                      by two child runs of this script under rocprofv3 --pmc (measure_traffic; N = 1 only,
                      --no-traffic skips it).
-  chain_vs_survey_model / ptp_step   the whole chain and one ptp priced with SURVEY 8d's UNFUSED byte model next to
-                     the bytes the launches of one step really moved under the counters.
-  without_ptp_algebra  the rate over the SAME number of steps with the pass compiler's ptp identities switched off
+  chain_vs_survey_model / ptp_step   the whole chain and [full] one ptp priced with SURVEY 8d's UNFUSED byte model next
+                     to [full] the bytes the launches of one step really moved under the counters.
+  without_ptp_algebra  [full] the rate over the SAME number of steps with the pass compiler's ptp identities switched off
                      (PAOS_PTP_ALGEBRA=0: 44 passes per wavefront instead of 24).
-  operator_by_operator  the rate over the same steps with the pass compiler of rounds 2-3 (PAOS_SEPARABLE=0: every operator's
+  operator_by_operator  [full] the rate over the same steps with the pass compiler of rounds 2-3 (PAOS_SEPARABLE=0: every operator's
                      transforms glued to its neighbours' instead of row factors first, column factors second).
-  same_wavelengths_every_step  the rate when every step repeats the first block of the sweep (how rounds 1-3 quoted
+  same_wavelengths_every_step  [full] the rate when every step repeats the first block of the sweep (how rounds 1-3 quoted
                      the headline; the walked sweep costs ~3 %: records rendered, PSF zeros rewritten).
-  extra              2048^2 / 1024^2 (the north star's sweep); fp32_4096 (SYN20 in fp32 mode with its roofline);
+  extra              [full] 2048^2 / 1024^2 (the north star's sweep); fp32_4096 (SYN20 in fp32 mode with its roofline);
                      dense (SYN20 behind a white-noise grid-sag screen: rough fields everywhere, per-class times);
                      configs (BASELINE.json configs 3-5 on one GPU: AIRS-CH0 64 wavelengths @2048^2, FGS1 256
                      Monte-Carlo draws @2048^2 with on-device rEE90, Excite_TEL @4096^2 fp64 and fp32).
-  cpu_baseline       the NumPy oracle ("port") on the host: one wavefront of the workload at the benchmark grid
+  cpu_baseline       [full] the NumPy oracle ("port") on the host: one wavefront of the workload at the benchmark grid
                      on one core, and `cpu_baseline_parallel`: min(batch, cores, memory, 8) worker processes over
                      wavelengths at the benchmark grid -- the reference's own joblib scheme (pipeline.py:140).
 """
@@ -359,7 +366,7 @@ def class_name(tag):
     return " + ".join(CLASS_NAMES[b] for b in (1, 2, 4, 8, 16, 32) if tag & b) if tag else CLASS_NAMES[0]
 
 
-def roofline_block(m, n, nb, esz, dev, kernel_name, steps, traffic=None, traffic_step=1, dense=None):
+def roofline_block(m, n, nb, esz, dev, kernel_name, steps, traffic=None, traffic_step=1, dense=None, yardstick=True):
     """The pass kernel against the HBM roofline, over EVERY pass launch of the timed steps:
     `achieved` = the launches' algorithmic bytes / their HIP-event time, where a launch's algorithmic bytes are what the
     library's pruning plan has it load and store (live lines x (loaded + stored positions) x element size, summed over
@@ -367,18 +374,18 @@ def roofline_block(m, n, nb, esz, dev, kernel_name, steps, traffic=None, traffic
     once.  `traffic`: what the FETCH_SIZE / WRITE_SIZE counters saw per launch (``traffic``: measure_traffic, the launches
     of global step ``traffic_step``).  `dense` (``dense``: a measure() of one step with the pruning switched off): the
     same kernel when every line is alive -- the figure rounds 1-3 reported as `achieved`.  `classes`: per class of launch
-    the mean event time, planned and counted bytes."""
+    the mean event time, planned and counted bytes.  ``yardstick``: measure the copy yardstick on ``dev`` (a run of its own:
+    --full only; None otherwise)."""
     import numpy as np
 
     pass_bytes = 2 * esz * n * n * nb  # one pass over the batch: every element read + written once
     ms, tags, planned = m["launch_ms"], m["launch_tags"], m["launch_bytes"]
     known = ms.size > 0 and planned.size == ms.size and float(planned.sum()) > 0.0
     achieved = float(planned.sum()) / (float(ms.sum()) * 1e-3) / 1e9 if known else 0.0
-    y_ms, y_bytes = dev.copy_yardstick(10)
     block = {
         "bound": "hbm", "kernel": kernel_name, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
         "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-        "traffic_note": "not measured in this run (--no-traffic, an `extra` entry, or N > 1); per-kernel FETCH_SIZE / WRITE_SIZE "
+        "traffic_note": "not measured in this run (no --full, --no-traffic, an `extra` entry, or N > 1); per-kernel FETCH_SIZE / WRITE_SIZE "
                         "of the default command under rocprofv3: profiles/r05_pmc_hbm_traffic_bench.txt",
         "launches": int(ms.size), "avg_launch_ms": float(ms.mean()) if ms.size else 0.0,
         "algorithmic_bytes_per_launch": float(planned.mean()) if known else None,
@@ -390,10 +397,13 @@ def roofline_block(m, n, nb, esz, dev, kernel_name, steps, traffic=None, traffic
                 "`dense` is the same kernel with every line alive",
         "fused_passes_per_wavefront": m["fused_passes"],
         "launches_per_step": float(ms.size) / steps if steps else None,
-        "copy_yardstick": {"ms_per_launch": y_ms, "GBps": y_bytes / (y_ms * 1e-3) / 1e9,
-                           "what": "measured in this run (paos_copy_yardstick): in-place copy of the same batch buffer, "
-                                   "16 B per lane, unit stride, no transform"},
+        "copy_yardstick": None,
     }
+    if yardstick:
+        y_ms, y_bytes = dev.copy_yardstick(10)
+        block["copy_yardstick"] = {"ms_per_launch": y_ms, "GBps": y_bytes / (y_ms * 1e-3) / 1e9,
+                                   "what": "measured in this run (paos_copy_yardstick): in-place copy of the same batch buffer, "
+                                           "16 B per lane, unit stride, no transform"}
     if dense is not None and dense["launch_ms"].size:
         dms = dense["launch_ms"]
         full = dense["launch_tags"] == 0
@@ -705,6 +715,75 @@ def sweep_report(m):
                     "sets, per timed step (paos_record_set_stats)"}
 
 
+def side_measurements(dev, args, n, nb, world, wavelengths_of, chains):
+    """--full, rank 0, behind the timed steps on the same context: the ptp probe (`ptp_step`) and the variants of the
+    same steps (`without_ptp_algebra`, `operator_by_operator`, `roofline.dense`, `same_wavelengths_every_step`).  Returns
+    a dict of them; every entry that does not apply to ``world`` ranks is None."""
+    from paos_amd import _lib
+    from paos_amd.planner import PilotBeam
+
+    # The north star's headline step: one ptp (fft2 -> H -> ifft2, wfo.py:462-472) on the whole batch, timed
+    # alone with the pass timer (3 launches: rows | cols x2 fused | rows).
+    blk = [PilotBeam(1.0, wl, n, 4).ptp(2.5) for wl in wavelengths_of(0)]
+    for _ in range(2):
+        dev.ptp(blk)
+    dev.profile_begin(_lib.KERNEL_PASS_ANY, max_launches=64)
+    for _ in range(5):
+        dev.ptp(blk)
+    _, tot = dev.profile_end()
+    ptp_ms = tot / 5.0
+
+    side_steps = max(1, min(args.steps, 20))  # the side measurements below (variants of the same steps)
+    # the same steps with the compiler's ptp identities switched off (every ptp of the reference as three passes)
+    plain = None
+    if world == 1:
+        import paos_amd.passes as ppasses
+
+        ppasses.PTP_ALGEBRA = False
+        try:
+            mp = measure(dev, n, args.precision, wavelengths_of, chains, side_steps, 1, None, first_step=args.warmup - 1)
+            plain = {"value": nb * side_steps / mp["elapsed"], "unit": "wavefronts/s", "steps": side_steps,
+                     "fused_passes_per_wavefront": mp["fused_passes"],
+                     "what": "PAOS_PTP_ALGEBRA=0 over the same steps of the walked sweep: consecutive ptp neither share a "
+                             "middle pass nor cancel, a wts and the stw that undoes it both run"}
+        finally:
+            ppasses.PTP_ALGEBRA = True
+    # ... and operator by operator (rounds 2-3: every operator's transforms glued to its neighbours', all rows / columns
+    # that are not known to be zero processed)
+    by_operator = None
+    if world == 1:
+        import paos_amd.passes as ppasses
+
+        ppasses.SEPARABLE = False
+        try:
+            mo = measure(dev, n, args.precision, wavelengths_of, chains, side_steps, 1, None, first_step=args.warmup - 1)
+            by_operator = {"value": nb * side_steps / mo["elapsed"], "unit": "wavefronts/s", "steps": side_steps,
+                           "fused_passes_per_wavefront": mo["fused_passes"],
+                           "pass_launch_ms_per_step": float(mo["launch_ms"].sum()) / side_steps,
+                           "what": "PAOS_SEPARABLE=0 over the same steps: the pass compiler of rounds 2-3 (a 2-D transform's "
+                                   "second half glued to the next one's first; the column passes behind an aperture run on "
+                                   "all 4096 columns)"}
+        finally:
+            ppasses.SEPARABLE = True
+    # ... and one step with the pruning off: the pass kernel when every line is alive (roofline.dense)
+    dense = None
+    if hasattr(dev, "set_pruning"):
+        dev.set_pruning(False)
+        try:
+            dense = measure(dev, n, args.precision, wavelengths_of, chains, 1, 1, None, first_step=args.warmup - 1)
+        finally:
+            dev.set_pruning(True)
+    # ... and with the SAME wavelengths every step (rounds 1-3 measured this way): what the walk costs
+    repeated = None
+    if world == 1:
+        mr = measure(dev, n, args.precision, lambda g: wavelengths_of(0), chains, side_steps, max(args.warmup, 1), None, timer=False)
+        repeated = {"value": nb * side_steps / mr["elapsed"], "unit": "wavefronts/s", "steps": side_steps,
+                    "what": "every step runs the first block of the sweep again (how rounds 1-3 quoted the headline): the "
+                            "context's kept aperture records and PSF zeros are found every time"}
+    return {"ptp_ms": ptp_ms, "without_ptp_algebra": plain, "operator_by_operator": by_operator, "dense": dense,
+            "same_wavelengths_every_step": repeated}
+
+
 # ---- self-launch: `bench.py --gpus N` with no launcher ------------------------------------------------------------
 def self_launch(n_ranks, argv, child=None, timeout=3000.0, env_extra=None, grace=30.0):
     """Start ``n_ranks`` copies of this script (``child``: another command, for tests) as one job and relay rank 0's
@@ -787,7 +866,10 @@ def no_rccl_line(args, comm, world, local_rank):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 PMC child runs that measure roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: CPU baselines, counter children, ptp probe, copy yardstick, "
+                         "variants of the same steps, extras (minutes; a plain run does only what the headline needs)")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: skip the rocprofv3 PMC child runs that measure roofline.traffic")
     # (defaults: a step is 22 ms since the separable programs; the first two or three steps of a context still allocate the
     # aperture record sets and the phase tables lazily, which `--warmup 1` left inside a five-step timed region)
     # (defaults, round 5: 100 timed steps = 1.4 s -- over 20 the edges of the timed region still weigh 0.5 %; the side
@@ -797,21 +879,23 @@ def main(argv=None):
     ap.add_argument("--grid", type=int, default=4096)
     ap.add_argument("--batch", type=int, default=0, help="wavefronts per GPU per step (default: 32 at 4096^2 = 8 GiB of fields + 4 GiB of PSFs of the 288 GB)")
     ap.add_argument("--precision", default="fp64", choices=["fp64", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra entries (other grids, fp32, dense, BASELINE configs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra entries (other grids, fp32, dense, BASELINE configs)")
     ap.add_argument("--allow-tcp", action="store_true",
                     help="with --gpus N > 1: accept the TCP transport when RCCL does not come up on every rank (default: exit 3)")
     ap.add_argument("--launch-timeout", type=float, default=3000.0, help="self-launch: seconds the ranks may take")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)  # one chain step and nothing else (measure_traffic)
-    ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
-                    help="where the detailed record goes (classes of launch, sweep, other kernels, side measurements, extras); "
-                         "stdout carries the contract line only")
+    ap.add_argument("--detail", default=None,
+                    help="where the detailed record goes (classes of launch, sweep, other kernels, side measurements, extras; "
+                         "default: none, with --full bench_detail.json); stdout carries the contract line only")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed (rank 0's wavefronts) to DIR/*.npy: records.npy, "
                          "psf_centre.npy, psf_sample.npy (float64, at most 60 MB; see dump_outputs)")
     args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.full and args.detail is None:
+        args.detail = os.path.join(ROOT, "bench_detail.json")
     if args.batch <= 0:
         # 8 -> 32 wavefronts per step is +3 % (launch tails and host work amortised; 64: +0.3 % more): 217 -> 224 at 4096^2
         args.batch = max(32, 32 * (4096 // args.grid) ** 2)
@@ -828,14 +912,14 @@ def main(argv=None):
 
     # forked CPU workers: before anything initialises the GPU in this process
     cpu_parallel = cpu_single = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu_parallel = cpu_baseline_parallel(args.grid, args.batch)
-    if world > 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world > 1 and rank == 0 and not args.no_cpu_baseline:
         # N > 1: the one-core baseline on rank 0 before any GPU call (the other ranks wait at the rendezvous)
         cpu_single = cpu_baseline(args.grid)
     # the PMC child runs too: no process is started from one that holds a GPU context
     traffic_result = None
-    if world == 1 and not args.no_traffic:
+    if args.full and world == 1 and not args.no_traffic:
         traffic_result = measure_traffic(args.grid, args.batch, args.precision)
 
     from paos_amd import _lib
@@ -894,67 +978,8 @@ def main(argv=None):
     kernel_name = ("frugal_pass_kernel" if frugal else "fused_pass_kernel") + " (every FFT pass launch, rows and columns)"
 
     if rank == 0:
-        # The north star's headline step: one ptp (fft2 -> H -> ifft2, wfo.py:462-472) on the whole batch, timed
-        # alone with the pass timer (3 launches: rows | cols x2 fused | rows).
-        from paos_amd.planner import PilotBeam
-
-        blk = [PilotBeam(1.0, wl, n, 4).ptp(2.5) for wl in wavelengths_of(0)]
-        for _ in range(2):
-            dev.ptp(blk)
-        dev.profile_begin(_lib.KERNEL_PASS_ANY, max_launches=64)
-        for _ in range(5):
-            dev.ptp(blk)
-        _, tot = dev.profile_end()
-        ptp_ms = tot / 5.0
-
         value = total * args.steps / m["elapsed"]
-        side_steps = max(1, min(args.steps, 20))  # the side measurements below (variants of the same steps)
-        # the same steps with the compiler's ptp identities switched off (every ptp of the reference as three passes)
-        plain = None
-        if world == 1:
-            import paos_amd.passes as ppasses
-
-            ppasses.PTP_ALGEBRA = False
-            try:
-                mp = measure(dev, n, args.precision, wavelengths_of, chains, side_steps, 1, None, first_step=args.warmup - 1)
-                plain = {"value": nb * side_steps / mp["elapsed"], "unit": "wavefronts/s", "steps": side_steps,
-                         "fused_passes_per_wavefront": mp["fused_passes"],
-                         "what": "PAOS_PTP_ALGEBRA=0 over the same steps of the walked sweep: consecutive ptp neither share a "
-                                 "middle pass nor cancel, a wts and the stw that undoes it both run"}
-            finally:
-                ppasses.PTP_ALGEBRA = True
-        # ... and operator by operator (rounds 2-3: every operator's transforms glued to its neighbours', all rows / columns
-        # that are not known to be zero processed)
-        by_operator = None
-        if world == 1:
-            import paos_amd.passes as ppasses
-
-            ppasses.SEPARABLE = False
-            try:
-                mo = measure(dev, n, args.precision, wavelengths_of, chains, side_steps, 1, None, first_step=args.warmup - 1)
-                by_operator = {"value": nb * side_steps / mo["elapsed"], "unit": "wavefronts/s", "steps": side_steps,
-                               "fused_passes_per_wavefront": mo["fused_passes"],
-                               "pass_launch_ms_per_step": float(mo["launch_ms"].sum()) / side_steps,
-                               "what": "PAOS_SEPARABLE=0 over the same steps: the pass compiler of rounds 2-3 (a 2-D transform's "
-                                       "second half glued to the next one's first; the column passes behind an aperture run on "
-                                       "all 4096 columns)"}
-            finally:
-                ppasses.SEPARABLE = True
-        # ... and one step with the pruning off: the pass kernel when every line is alive (roofline.dense)
-        dense = None
-        if hasattr(dev, "set_pruning"):
-            dev.set_pruning(False)
-            try:
-                dense = measure(dev, n, args.precision, wavelengths_of, chains, 1, 1, None, first_step=args.warmup - 1)
-            finally:
-                dev.set_pruning(True)
-        # ... and with the SAME wavelengths every step (rounds 1-3 measured this way): what the walk costs
-        repeated = None
-        if world == 1:
-            mr = measure(dev, n, args.precision, lambda g: wavelengths_of(0), chains, side_steps, max(args.warmup, 1), None, timer=False)
-            repeated = {"value": nb * side_steps / mr["elapsed"], "unit": "wavefronts/s", "steps": side_steps,
-                        "what": "every step runs the first block of the sweep again (how rounds 1-3 quoted the headline): the "
-                                "context's kept aperture records and PSF zeros are found every time"}
+        side = side_measurements(dev, args, n, nb, world, wavelengths_of, chains) if args.full else {}
         n_ptp, n_stw, n_wts = chain_fft_counts(wavelengths_of(0)[0], n)
         ffts = 2 * n_ptp + n_stw + n_wts
         survey_bytes = (ffts * 4 * esz + 8) * n * n  # 2 passes x (read + write) per 2-D FFT + the 8 B/px PSF write
@@ -967,6 +992,13 @@ def main(argv=None):
         per_gpu = value / world
         dtype = "c128 (f64)" if args.precision == "fp64" else "c64 (f32, f64 phase arguments)"
         passes_seen = sorted(set(c for c in m["per_step_passes"] if c is not None))
+        ptp_ms, ptp_step = side.get("ptp_ms"), None
+        if ptp_ms is not None:
+            ptp_step = {"what": "one ptp over the batch: 2 2-D FFTs + H, 3 fused passes",
+                        "ms_per_wavefront": ptp_ms / nb,
+                        "frac_of_hbm_peak_vs_survey_model": 8 * esz * n * n * nb / (ptp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                        "frac_bytes_moved": 6 * esz * n * n * nb / (ptp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                        "note": "SURVEY 8d prices a ptp at 128 B/px (4 passes); the fused path moves 96 B/px"}
         out = {
             "metric": f"wavefronts/sec ({n}^2 {'c128' if esz == 16 else 'c64'}, 20-surface chain) + achieved HBM GB/s",
             "value": value,
@@ -1004,7 +1036,8 @@ def main(argv=None):
                        "ranks_seen": len(ranks_seen), "devices_seen": ranks_seen,
                        "bringup_notes": {str(r): t for r, t in enumerate(notes) if t}},
             "sweep": sweep_report(m),
-            "roofline": roofline_block(m, n, nb, esz, dev, kernel_name, args.steps, traffic, dense=dense),
+            "roofline": roofline_block(m, n, nb, esz, dev, kernel_name, args.steps, traffic, dense=side.get("dense"),
+                                       yardstick=args.full),
             "dominant_launch": dominant_launch(m, n, args.precision, args.steps, traffic),
             "chain_vs_survey_model": {
                 "survey_model_bytes_per_wavefront": survey_bytes,
@@ -1017,31 +1050,27 @@ def main(argv=None):
                         "bytes_moved_per_wavefront = every dispatch of one step under the FETCH_SIZE (x2) / WRITE_SIZE counters "
                         "(pass kernels and the start / Zernike / aperture-record / reduction kernels in `other_kernels`, whose "
                         "ms are rocprofv3 kernel-trace durations), null when the counters were not collected"},
-            "ptp_step": {"what": "one ptp over the batch: 2 2-D FFTs + H, 3 fused passes",
-                         "ms_per_wavefront": ptp_ms / nb,
-                         "frac_of_hbm_peak_vs_survey_model": 8 * esz * n * n * nb / (ptp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "frac_bytes_moved": 6 * esz * n * n * nb / (ptp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "note": "SURVEY 8d prices a ptp at 128 B/px (4 passes); the fused path moves 96 B/px"},
-            "without_ptp_algebra": plain,
-            "operator_by_operator": by_operator,
-            "same_wavelengths_every_step": repeated,
+            "ptp_step": ptp_step,
+            "without_ptp_algebra": side.get("without_ptp_algebra"),
+            "operator_by_operator": side.get("operator_by_operator"),
+            "same_wavelengths_every_step": side.get("same_wavelengths_every_step"),
             "power_check": power_check,
             "build": dev.build_info(),
         }
         dev.close()
-        if world == 1 and not args.no_extras and n == 4096:
+        if args.full and world == 1 and not args.no_extras and n == 4096:
             from bench_extras import extras
 
             out["extra"] = extras(args, esz, measure, roofline_block, sweep_report)
         if traffic_result is not None:
             out["roofline"]["counters_note"] = traffic_result[1]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(n)
             out["cpu_baseline_parallel"] = cpu_parallel
         elif cpu_single is not None:
             out["cpu_baseline"] = cpu_single
         # the detailed record to a file (and nothing but the contract line to stdout: <= 4 KB, strict JSON, last line)
-        out["detail_file"] = os.path.basename(args.detail) if write_detail(out, args.detail) else None
+        out["detail_file"] = os.path.basename(args.detail) if args.detail and write_detail(out, args.detail) else None
         print(contract_line(out), flush=True)
     else:
         dev.close()

@@ -1,4 +1,4 @@
-"""The `extra` entries of bench.py's line (N = 1, default grid only): the same chain at other grids and in fp32 mode, a
+"""The `extra` entries of bench.py --full (N = 1, default grid only): the same chain at other grids and in fp32 mode, a
 rough-field variant, and BASELINE.json's configs 3-5 on one GPU.  Everything here runs on the HIP path through the same
 `run_batch` the headline uses; nothing is timed with fields crossing PCIe unless an entry says so."""
 import os

@@ -715,3 +715,79 @@ def test_bench_dump_outputs_writes_the_last_step_within_its_budget(tmp_path):
         assert records[i, 2 + 26 + 6] == 1.0 / m["res"][i][20]["fratio"]
     with pytest.raises(SystemExit):
         bench.main(["--steps", "0"])
+
+
+def test_bench_plain_run_measures_the_headline_only_and_full_runs_the_rest(tmp_path, monkeypatch, capsys):
+    """bench.py without --full: set-up, warm-up, the timed steps and the line -- no CPU baseline, no counter children, no
+    side measurement on the context, no copy yardstick, no detail file unless --detail names one.  With --full all of them
+    run and land in the line and the detail record.  On the NumPy model of the device (grid 64: no `extra` entries), with
+    the CPU baselines and the counter children replaced by stand-ins that record their calls."""
+    import json
+
+    import bench
+    from fakes import ModelDevice
+    from paos_amd import _lib
+
+    calls = []
+
+    class Device(ModelDevice):
+        def profile_begin(self, kind, max_launches=0):
+            pass
+
+        def profile_end(self):
+            return 3, 1.5
+
+        def profile_planned_bytes(self):
+            return np.zeros(0)
+
+        def profile_line_transforms(self):
+            return np.zeros(0)
+
+        def profile_end_launches(self):
+            return np.zeros(0), np.zeros(0, dtype=np.int32)
+
+        def copy_yardstick(self, reps=10):
+            calls.append("copy_yardstick")
+            return 1.0, 8.0e9
+
+        def ptp(self, blocks):
+            calls.append("ptp")
+            return super().ptp(blocks)
+
+    for key in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "PAOS_BENCH_FORCE_COMM"):
+        monkeypatch.delenv(key, raising=False)
+    monkeypatch.setattr(_lib, "DeviceFields", Device)
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))  # where --full puts bench_detail.json by default
+    monkeypatch.setattr(bench, "cpu_baseline_parallel", lambda n, nb: calls.append("cpu_parallel") or {"value": 2.0})
+    monkeypatch.setattr(bench, "cpu_baseline", lambda n: calls.append("cpu_single") or
+                        {"value": 1.0, "unit": "wavefronts/s", "cores": 1, "kind": "port", "sample": "s"})
+    monkeypatch.setattr(bench, "measure_traffic", lambda *a: calls.append("traffic") or (None, "stand-in"))
+    small = ["--grid", "64", "--batch", "2", "--steps", "2", "--warmup", "1"]
+
+    bench.main(small)
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert calls == [] and os.listdir(tmp_path) == []
+    assert line["value"] > 0 and line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["unit"] == "wavefronts/s" and line["higher_is_better"] is True and line["dtype"] == "c128 (f64)"
+    assert line["cpu_baseline"] is None and line["detail"] is None and "extra_wavefronts_per_s" not in line
+    assert line["roofline"]["ptp_step_frac"] is None and line["roofline"]["copy_yardstick_frac"] is None
+
+    detail = str(tmp_path / "plain.json")
+    bench.main(small + ["--detail", detail])
+    capsys.readouterr()
+    rec = json.load(open(detail))
+    assert calls == [] and rec["sweep"]["walked"] is True and rec["ptp_step"] is None
+    assert rec["without_ptp_algebra"] is None and rec["same_wavelengths_every_step"] is None
+    assert rec["roofline"]["copy_yardstick"] is None and "dense" not in rec["roofline"] and "cpu_baseline" not in rec
+    os.remove(detail)
+
+    bench.main(small + ["--full"])
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert calls[:2] == ["cpu_parallel", "traffic"] and calls[-1] == "cpu_single"
+    assert "ptp" in calls and "copy_yardstick" in calls
+    assert line["value"] > 0 and line["cpu_baseline"]["value"] == 1.0 and line["detail"] == "bench_detail.json"
+    rec = json.load(open(tmp_path / "bench_detail.json"))
+    assert rec["ptp_step"]["ms_per_wavefront"] == 0.3 / 2 and rec["cpu_baseline_parallel"] == {"value": 2.0}
+    assert rec["without_ptp_algebra"]["steps"] == 2 and rec["operator_by_operator"]["steps"] == 2
+    assert rec["same_wavelengths_every_step"]["value"] > 0 and rec["roofline"]["copy_yardstick"]["GBps"] == 8000.0
+    assert rec["roofline"]["counters_note"] == "stand-in"

@@ -6,7 +6,7 @@ mkdir -p gpurun_out/mall
 for spec in "4096 fp64 1" "4096 fp64 2" "4096 fp64 8" "4096 fp32 1" "4096 fp32 2" "2048 fp64 1" "2048 fp64 2" "2048 fp64 4" "2048 fp64 16" "2048 fp32 4" "1024 fp64 4" "1024 fp64 16" "1024 fp64 64"; do
   set -- $spec
   out=gpurun_out/mall/g$1_$2_b$3.json
-  timeout -k 10 300 python bench.py --grid $1 --precision $2 --batch $3 --steps 10 --warmup 2 --no-cpu-baseline --no-extras > $out 2> gpurun_out/mall/g$1_$2_b$3.err
+  timeout -k 10 300 python bench.py --full --grid $1 --precision $2 --batch $3 --steps 10 --warmup 2 --no-cpu-baseline --no-extras > $out 2> ${out%.json}.err
   python - "$out" "$spec" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
