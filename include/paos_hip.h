@@ -228,7 +228,8 @@ int paos_norm2_release(paos_ctx* ctx, int ticket);
 /* PSF metrics on the GPU for Monte-Carlo studies (the encircled-energy workflow of
  * docs/source/user/montecarlo/index.rst:26-66; PSF = |u|^2, plot.py:125-130).  Per item:
  * [sum I, sum I*col, sum I*row, max I, then nr values: sum of I over pixels whose centre lies
- * within radii_px[k] of (cx_px, cy_px)], nr <= 16.  host_out: [batch][4 + nr].  Synchronises. */
+ * within radii_px[k] of (cx_px, cy_px)], nr <= 16.  host_out: [batch][4 + nr].  Radii finite and >= 0, centre
+ * finite -- otherwise PAOS_EINVAL.  Synchronises. */
 int paos_psf_metrics(paos_ctx* ctx, int nr, const double* radii_px, double cx_px, double cy_px,
                      double* host_out);
 /* quadratic phase u *= exp(i sgn [2 pi] coef ((x sx)^2 + (y sy)^2)), x, y centred pixel
@@ -301,7 +302,8 @@ int paos_run_program(paos_ctx* ctx, const paos_pass* passes, int n_passes, const
  * u *= exp(2 pi i wfe / wl) inside rho <= 1.  `table` holds the Jacobi recurrence
  * constants [(nmax+1)][kdim][3]; `params` the per-item blocks (PAOS_ZERNIKE_HEAD +
  * 2 (nmax+1) kdim doubles).  If host_wfe != NULL the wfe map of item 0 is returned
- * (row-major doubles, NaN where rho > 1 -- the masked array of wfo.py:654). */
+ * (row-major doubles, NaN where rho > 1 -- the masked array of wfo.py:654).  PAOS_EINVAL for an enabled item whose
+ * radius is not > 0 or whose record holds a non-finite value: NaN inside the disk would read as masked. */
 int paos_zernike(paos_ctx* ctx, int nmax, int kdim, const double* table, const double* params,
                  int param_stride, double* host_wfe);
 /* Round 5: paos_zernike for a caller who knows that some items hold COPIES of one field -- the surface right behind the
@@ -326,7 +328,7 @@ int paos_pupil_upload(paos_ctx* ctx, int item, const double* host_weights);
  * polynomials, i <= j enumerated row by row, followed by the pixel count:
  * host_out[batch][K (K + 1) / 2 + 1].  poly[K][4] = {|m|, k = (n - |m|) / 2, is_sin, factor}
  * with factor = (-1)^k norm; table / params as for paos_zernike (the coefficient planes of
- * params are not read).  K <= 64.  Synchronises. */
+ * params are not read; the header is refused as for paos_zernike).  K <= 64.  Synchronises. */
 int paos_zernike_gram(paos_ctx* ctx, int nmax, int kdim, const double* table, const double* params,
                       int param_stride, int K, const double* poly, int use_pupil, double* host_out);
 /* paos_zernike restricted to the pupil: pixels outside it keep their value and read NaN in

@@ -2359,6 +2359,10 @@ int paos_psf_metrics(paos_ctx* c, int nr, const double* radii_px, double cx_px, 
   SETTLE_SCALE(c);
   if (c) (void)hipSetDevice(c->device);  // one process may drive several GPUs
   if (!c || !host_out || nr < 0 || nr > kMaxRadii || (nr > 0 && !radii_px)) return fail(c, PAOS_EINVAL, "bad metrics request");
+  // (a negative radius would act as |r| once squared, a NaN one would count nothing)
+  for (int k = 0; k < nr; ++k)
+    if (!(radii_px[k] >= 0.0) || !std::isfinite(radii_px[k])) return fail(c, PAOS_EINVAL, "radii must be finite and >= 0");
+  if (!std::isfinite(cx_px) || !std::isfinite(cy_px)) return fail(c, PAOS_EINVAL, "the centre must be finite");
   const int nvals = 4 + nr, nblocks = 512;
   if (!c->metric_partial) {
     HIPCHK(c, hipMalloc(&c->metric_partial, (size_t)c->batch * nblocks * (4 + kMaxRadii) * sizeof(double)));
@@ -2783,6 +2787,15 @@ static int zernike_apply(paos_ctx* c, int nmax, int kdim, const double* table, c
   if (nmax < 0 || kdim < nmax / 2 + 1 || param_stride < ZP_HEAD + 2 * (nmax + 1) * kdim)
     return fail(c, PAOS_EINVAL, "inconsistent Zernike table dimensions");
   if (use_pupil && !c->mask) return fail(c, PAOS_EINVAL, "no pupil defined (paos_pupil_aperture / paos_pupil_upload)");
+  // NaN is the kernel's "outside the disk" marker in the wfe map: a record that would make NaN inside the disk (a
+  // non-finite coefficient, offset or sampling, a radius <= 0) must not come back looking masked
+  for (int i = 0; i < c->batch; ++i) {
+    const double* q = params + (size_t)i * param_stride;
+    if (q[ZP_ENABLE] == 0.0) continue;
+    if (!(q[ZP_RADIUS] > 0.0)) return fail(c, PAOS_EINVAL, "Zernike radius must be > 0");
+    for (int k = ZP_DX; k < param_stride; ++k)
+      if (!std::isfinite(q[k])) return fail(c, PAOS_EINVAL, "non-finite Zernike parameter");
+  }
   const double *dt = nullptr, *dp = nullptr;
   int rc = arena_push(c, table, (size_t)(nmax + 1) * kdim * 3, &dt);
   if (rc) return rc;
@@ -2946,6 +2959,13 @@ int paos_zernike_gram(paos_ctx* c, int nmax, int kdim, const double* table, cons
     return fail(c, PAOS_EINVAL, "inconsistent Zernike table dimensions");
   if (K < 1 || K > kGramMaxK) return fail(c, PAOS_EUNSUPPORTED, "1 <= K <= 64 polynomials");
   if (use_pupil && !c->mask) return fail(c, PAOS_EINVAL, "no pupil defined (paos_pupil_aperture / paos_pupil_upload)");
+  for (int i = 0; i < c->batch; ++i) {  // (the header only: the coefficient planes are not read)
+    const double* q = params + (size_t)i * param_stride;
+    if (q[ZP_ENABLE] == 0.0) continue;
+    if (!(q[ZP_RADIUS] > 0.0)) return fail(c, PAOS_EINVAL, "Zernike radius must be > 0");
+    for (int k = ZP_DX; k < ZP_HEAD; ++k)
+      if (!std::isfinite(q[k])) return fail(c, PAOS_EINVAL, "non-finite Zernike parameter");
+  }
   // poly[j] = {|m|, k, is_sin, factor}  ->  slot table + factors
   const size_t ncoef = (size_t)(nmax + 1) * kdim;
   std::vector<double> slots(2 * ncoef, -1.0), fac(K);

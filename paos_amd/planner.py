@@ -328,6 +328,13 @@ def zernike_block(m, n, norm, coeffs, dx, dy, radius, wl, origin="x", offset_deg
     planes indexed [|m|][k], k = (n - |m|)/2, with (-1)^k * norm * Z folded in."""
     m = np.asarray(m, dtype=int)
     n = np.asarray(n, dtype=int)
+    # the kernels mark pixels outside the disk with NaN: a request that would put NaN inside it is refused here
+    if not np.all(np.isfinite(np.asarray(coeffs, dtype=np.float64))):
+        raise ValueError("Zernike coefficients must be finite")
+    if not np.isfinite(offset_deg):
+        raise ValueError("Zernike offset must be finite")
+    if not (np.isfinite(radius) and radius > 0):
+        raise ValueError(f"Zernike radius must be finite and > 0, got {radius}")
     if nmax is None:
         nmax = int(n.max())
     pref, at_cos, is_cos, at_sin, is_sin, kdim = _block_template(m, n, norm, nmax)

@@ -613,6 +613,8 @@ def _launch_zernike(dev, plans, want_wfe=False, same_as=None):
             hit = planes.get(key)
             if hit is None:
                 hit = planes[key] = zernike_block(z["m"], z["n"], z["norm"], c, 1.0, 1.0, 1.0, 1.0, origin=z["origin"], nmax=nmax)[0]
+            if not (np.isfinite(z["radius"]) and z["radius"] > 0):
+                raise ValueError(f"Zernike radius must be finite and > 0, got {z['radius']}")
             row = blocks[i]
             row[:] = hit
             row[1], row[2], row[3], row[7] = z["dx"], z["dy"], z["radius"], 1.0 / z["wl"]
