@@ -365,6 +365,16 @@ int paos_detector_add(paos_ctx* ctx, const double* per_item);
 int paos_detector_images(paos_ctx* ctx, const double* per_item, double* host_out);
 /* the accumulator to host_out[ny][nx].  Synchronises. */
 int paos_detector_fetch(paos_ctx* ctx, double* host_out);
+/* Placed items (README.md, "Detector images"): per_item[batch][PAOS_DETECTOR_PLACED_ITEM] = dx, dy, w, x0, y0, where
+ * (x0, y0) is the image-plane position in metres of item i's grid centre (pixel N/2): grid column j of item i spans
+ * [x0_i + (j - N/2 - 1/2) dx_i, x0_i + (j - N/2 + 1/2) dx_i], row k likewise with y0_i and dy_i; everything else as above.
+ * On the device the detector centre seen from the item is xc - x0_i (and yc - y0_i), rounded once and then used as the
+ * unplaced calls use xc: zero offsets give paos_detector_add / paos_detector_images bit for bit.  Footprint, chunking,
+ * item order and the fp64 accumulator are per item as above; a footprint that misses the detector adds exact zeros.
+ * PAOS_EINVAL, besides the cases above, for an x0 / y0 that is not finite (or whose difference to the centre overflows). */
+enum { PAOS_DETECTOR_PLACED_ITEM = 5 };  /* dx, dy, w, x0, y0 */
+int paos_detector_add_placed(paos_ctx* ctx, const double* per_item);
+int paos_detector_images_placed(paos_ctx* ctx, const double* per_item, double* host_out);
 
 #ifdef __cplusplus
 }

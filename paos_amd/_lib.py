@@ -119,6 +119,8 @@ SYMBOLS = {
     "paos_detector_add": (ctypes.c_int, [_c_ctx, _dbl_p]),
     "paos_detector_images": (ctypes.c_int, [_c_ctx, _dbl_p, _dbl_p]),
     "paos_detector_fetch": (ctypes.c_int, [_c_ctx, _dbl_p]),
+    "paos_detector_add_placed": (ctypes.c_int, [_c_ctx, _dbl_p]),
+    "paos_detector_images_placed": (ctypes.c_int, [_c_ctx, _dbl_p, _dbl_p]),
 }
 
 _lib = None
@@ -376,11 +378,13 @@ class DeviceFields:
         return out
 
     # -- detector pixel grid (paos_detector_*: README.md, "Detector images") ----------------------------------------
-    def _detector_items(self, dxs, dys, weights=None):
-        d = np.empty((self.batch, 3), dtype=np.float64)
+    def _detector_items(self, dxs, dys, weights=None, origins=None):
+        d = np.empty((self.batch, 3 if origins is None else 5), dtype=np.float64)
         d[:, 0] = np.broadcast_to(np.asarray(dxs, dtype=np.float64), (self.batch,))
         d[:, 1] = np.broadcast_to(np.asarray(dys, dtype=np.float64), (self.batch,))
         d[:, 2] = 0.0 if weights is None else np.broadcast_to(np.asarray(weights, dtype=np.float64), (self.batch,))
+        if origins is not None:  # (x0, y0) per item: the image-plane position of its grid centre
+            d[:, 3:5] = np.broadcast_to(np.asarray(origins, dtype=np.float64), (self.batch, 2))
         return d
 
     def detector_begin(self, det):
@@ -389,20 +393,28 @@ class DeviceFields:
         self._check(self._lib.paos_detector_begin(self._ctx, _dptr(geom)), "paos_detector_begin")
         self.detector = det
 
-    def detector_add(self, dxs, dys, weights):
+    def detector_add(self, dxs, dys, weights, origins=None):
         """image += w_i A_i for every item in order, from the kept PSFs (``dxs`` / ``dys``: each item's pitch at the
-        last surface).  Enqueued only: nothing synchronises."""
-        d = self._detector_items(dxs, dys, weights)
-        self._check(self._lib.paos_detector_add(self._ctx, _dptr(d)), "paos_detector_add")
+        last surface).  ``origins`` ((batch, 2), metres): the image-plane position (x0, y0) of each item's grid centre
+        (paos_detector_add_placed); None places every grid centre at the origin.  Enqueued only: nothing synchronises."""
+        d = self._detector_items(dxs, dys, weights, origins)
+        if origins is None:
+            self._check(self._lib.paos_detector_add(self._ctx, _dptr(d)), "paos_detector_add")
+        else:
+            self._check(self._lib.paos_detector_add_placed(self._ctx, _dptr(d)), "paos_detector_add_placed")
 
-    def detector_images(self, dxs, dys):
-        """A_i of every item, (batch, ny, nx) float64.  Synchronises."""
-        d = self._detector_items(dxs, dys)
+    def detector_images(self, dxs, dys, origins=None):
+        """A_i of every item, (batch, ny, nx) float64 (``origins`` as for ``detector_add``).  Synchronises."""
+        d = self._detector_items(dxs, dys, origins=origins)
         det = getattr(self, "detector", None)
         if det is None:
             raise PaosHipError("paos_detector_images failed: no detector (detector_begin)")
         out = np.empty((self.batch, det.ny, det.nx), dtype=np.float64)
-        self._check(self._lib.paos_detector_images(self._ctx, _dptr(d), _dptr(out)), "paos_detector_images")
+        if origins is None:
+            self._check(self._lib.paos_detector_images(self._ctx, _dptr(d), _dptr(out)), "paos_detector_images")
+        else:
+            self._check(self._lib.paos_detector_images_placed(self._ctx, _dptr(d), _dptr(out)),
+                        "paos_detector_images_placed")
         return out
 
     def detector_fetch(self):

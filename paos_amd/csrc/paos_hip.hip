@@ -3040,24 +3040,35 @@ int det_reserve(paos_ctx* c, double** buf, size_t* have, size_t bytes) {
 }
 
 // A_i of every batch item, chunk by chunk in item order: added as w_i A_i into the accumulator (host_out == NULL) or
-// written to host_out[i][ny][nx] (synchronises).
-int detector_run(paos_ctx* c, const double* per_item, double* host_out) {
+// written to host_out[i][ny][nx] (synchronises).  per_item holds `stride` doubles per item: dx, dy, w and, when
+// stride == PAOS_DETECTOR_PLACED_ITEM, the image-plane position (x0, y0) of the item's grid centre.  The detector centre
+// seen from the item is then xc - x0 (rounded once; x0 = 0 gives xc itself, so zero offsets change no bit).
+int detector_run(paos_ctx* c, const double* per_item, int stride, double* host_out) {
   if (!c->psf) return fail(c, PAOS_EINVAL, "no PSF kept (paos_psf_keep)");
   if (!c->det_set) return fail(c, PAOS_EINVAL, "no detector (paos_detector_begin)");
   if (!per_item) return fail(c, PAOS_EINVAL, "null per-item parameters");
-  const bool accumulate = host_out == nullptr;
+  const bool accumulate = host_out == nullptr, placed = stride == PAOS_DETECTOR_PLACED_ITEM;
   const int n = c->n, nx = c->det_nx, ny = c->det_ny;
   const DetGeom g{nx, ny, c->det_geom[0], c->det_geom[1], c->det_geom[2], c->det_geom[3]};
   const size_t npix = (size_t)nx * ny;
   std::vector<int> k0(c->batch), k1(c->batch);
+  std::vector<double> cx(c->batch), cy(c->batch);
   for (int i = 0; i < c->batch; ++i) {
-    const double dx = per_item[PAOS_DETECTOR_ITEM * i], dy = per_item[PAOS_DETECTOR_ITEM * i + 1];
-    const double w = per_item[PAOS_DETECTOR_ITEM * i + 2];
+    const double* q = per_item + (size_t)stride * i;
+    const double dx = q[0], dy = q[1], w = q[2];
     if (!finite_positive(dx) || !finite_positive(dy)) return fail(c, PAOS_EINVAL, "dx and dy must be finite and positive");
     if (accumulate && !std::isfinite(w)) return fail(c, PAOS_EINVAL, "weights must be finite");
+    cx[i] = g.xc;
+    cy[i] = g.yc;
+    if (placed) {
+      if (!std::isfinite(q[3]) || !std::isfinite(q[4])) return fail(c, PAOS_EINVAL, "item origins x0 and y0 must be finite");
+      cx[i] = g.xc - q[3];
+      cy[i] = g.yc - q[4];
+      if (!std::isfinite(cx[i]) || !std::isfinite(cy[i])) return fail(c, PAOS_EINVAL, "detector centre minus item origin overflows");
+    }
     // the item's footprint: the grid rows under detector rows 0 .. ny-1 (det_edge is monotonic in its index)
-    k0[i] = det_lo(det_edge(0, ny, g.py, g.yc, dy, n), n);
-    k1[i] = std::max(k0[i], det_hi(det_edge(ny, ny, g.py, g.yc, dy, n), n));
+    k0[i] = det_lo(det_edge(0, ny, g.py, cy[i], dy, n), n);
+    k1[i] = std::max(k0[i], det_hi(det_edge(ny, ny, g.py, cy[i], dy, n), n));
   }
   const dim3 block(kPwThreads);
   for (int start = 0; start < c->batch;) {
@@ -3077,10 +3088,11 @@ int detector_run(paos_ctx* c, const double* per_item, double* host_out) {
     for (int li = 0; li < cnt; ++li) {
       const int i = start + li;
       double* r = rec.data() + (size_t)li * kDetItem;
-      r[0] = per_item[PAOS_DETECTOR_ITEM * i];
-      r[1] = per_item[PAOS_DETECTOR_ITEM * i + 1];
-      r[2] = accumulate ? per_item[PAOS_DETECTOR_ITEM * i + 2] : 0.0;
+      r[0] = per_item[(size_t)stride * i];
+      r[1] = per_item[(size_t)stride * i + 1];
+      r[2] = accumulate ? per_item[(size_t)stride * i + 2] : 0.0;
       r[3] = k0[i]; r[4] = k1[i]; r[5] = (double)off; r[6] = i;
+      r[8] = cx[i]; r[9] = cy[i];
       off += (size_t)(k1[i] - k0[i]) * nx;
       if (k1[i] > k0[i]) max_block_rows = std::max(max_block_rows, (k1[i] - 1) / c->br - k0[i] / c->br + 1);
     }
@@ -3141,13 +3153,25 @@ int paos_detector_begin(paos_ctx* c, const double* geom) {
 int paos_detector_add(paos_ctx* c, const double* per_item) {
   if (c) (void)hipSetDevice(c->device);
   if (!c) return fail(c, PAOS_EINVAL, "null context");
-  return detector_run(c, per_item, nullptr);
+  return detector_run(c, per_item, PAOS_DETECTOR_ITEM, nullptr);
+}
+
+int paos_detector_add_placed(paos_ctx* c, const double* per_item) {
+  if (c) (void)hipSetDevice(c->device);
+  if (!c) return fail(c, PAOS_EINVAL, "null context");
+  return detector_run(c, per_item, PAOS_DETECTOR_PLACED_ITEM, nullptr);
 }
 
 int paos_detector_images(paos_ctx* c, const double* per_item, double* host_out) {
   if (c) (void)hipSetDevice(c->device);
   if (!c || !host_out) return fail(c, PAOS_EINVAL, "null context or output buffer");
-  return detector_run(c, per_item, host_out);
+  return detector_run(c, per_item, PAOS_DETECTOR_ITEM, host_out);
+}
+
+int paos_detector_images_placed(paos_ctx* c, const double* per_item, double* host_out) {
+  if (c) (void)hipSetDevice(c->device);
+  if (!c || !host_out) return fail(c, PAOS_EINVAL, "null context or output buffer");
+  return detector_run(c, per_item, PAOS_DETECTOR_PLACED_ITEM, host_out);
 }
 
 int paos_detector_fetch(paos_ctx* c, double* host_out) {

@@ -1424,11 +1424,14 @@ __global__ void import_weights_kernel(const double* src, double* dst, int n, uns
 // fx(j, m) = max(0, min(j + 1, e(m + 1)) - max(j, e(m))).  The edge is formed by exactly these IEEE operations
 // (no contraction: the library is built with -ffp-contract=off), so a NumPy restatement that writes them the same way
 // gets the same fractions bit for bit.
+// (g.xc / g.yc are not read by the kernels: every item carries its own detector centre in its record, measured from its
+// grid centre -- the detector's (xc, yc), or xc - x0_i / yc - y0_i for an item placed at (x0_i, y0_i), paos_detector_*_placed)
 struct DetGeom {
   int nx, ny;
   double px, py, xc, yc;
 };
-enum { kDetItem = 8 };  // per-item device record: dx, dy, w, k0, k1, scratch offset, batch item, (pad)
+// per-item device record: dx, dy, w, k0, k1, scratch offset, batch item, (pad), detector centre x, y seen from the item
+enum { kDetItem = 10 };
 
 __host__ __device__ inline double det_edge(int m, int nd, double pitch, double centre, double d, int n) {
   const double t = (double)m - 0.5 * (double)nd;  // exact
@@ -1447,7 +1450,7 @@ __global__ void __launch_bounds__(256) detector_rows_kernel(const double* __rest
                                                             int n, const double* __restrict__ items, DetGeom g,
                                                             double* __restrict__ R) {
   const double* p = items + (size_t)blockIdx.y * kDetItem;
-  const double dx = p[0];
+  const double dx = p[0], xc = p[8];
   const int k0 = (int)p[3], k1 = (int)p[4];
   if (k1 <= k0) return;
   const size_t off = (size_t)p[5];
@@ -1456,7 +1459,7 @@ __global__ void __launch_bounds__(256) detector_rows_kernel(const double* __rest
   const size_t total = (size_t)nbr * g.nx;
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
     const int kb = kb0 + (int)(t / g.nx), m = (int)(t % g.nx);
-    const double e0 = det_edge(m, g.nx, g.px, g.xc, dx, n), e1 = det_edge(m + 1, g.nx, g.px, g.xc, dx, n);
+    const double e0 = det_edge(m, g.nx, g.px, xc, dx, n), e1 = det_edge(m + 1, g.nx, g.px, xc, dx, n);
     const int jlo = det_lo(e0, n), jhi = det_hi(e1, n);
     const double* base = psf + (size_t)item * item_stride + (size_t)kb * pitch;
     double acc[BR];
@@ -1488,10 +1491,10 @@ __global__ void __launch_bounds__(256) detector_cols_kernel(const double* __rest
     double acc = accumulate ? out[q] : 0.0;
     for (int li = 0; li < nitems; ++li) {
       const double* p = items + (size_t)li * kDetItem;
-      const double dy = p[1], w = p[2];
+      const double dy = p[1], w = p[2], yc = p[9];
       const int k0 = (int)p[3], k1 = (int)p[4];
       const size_t off = (size_t)p[5];
-      const double e0 = det_edge(row, g.ny, g.py, g.yc, dy, n), e1 = det_edge(row + 1, g.ny, g.py, g.yc, dy, n);
+      const double e0 = det_edge(row, g.ny, g.py, yc, dy, n), e1 = det_edge(row + 1, g.ny, g.py, yc, dy, n);
       const int klo = max(det_lo(e0, n), k0), khi = min(det_hi(e1, n), k1);
       double a = 0.0;
       for (int k = klo; k < khi; ++k) {

@@ -64,9 +64,12 @@ class Detector:
 
 
 def run_broadband(pupil_diameter, wavelengths, weights, gridsize, zoom, field, opt_chains, detector, batch=32,
-                  precision="fp64", device=0):
+                  precision="fp64", device=0, detector_origin=None):
     """The broadband image of a wavelength sweep on ``detector``: ``sum_i w_i A_i`` over ``wavelengths[i]`` /
     ``weights[i]`` (``opt_chains``: one chain per wavelength, or one chain for all; their last surface must be saved).
+    ``field``: one field point for all, or one per wavelength (the items are then (wavelength, field, weight) triples:
+    a field-of-view study lists every wavelength once per field point).  ``detector_origin`` as for ``run_batch``: None,
+    ``"chief_ray"``, or an (items, 2) array of grid-centre positions.
 
     The sweep is walked in blocks of ``batch`` on one device context, each block issued as ``bench.measure`` issues a
     step (``run_batch`` with ``outputs=()``, the lean walk, ``keep_psf``, no synchronisation) and followed by
@@ -90,6 +93,14 @@ def run_broadband(pupil_diameter, wavelengths, weights, gridsize, zoom, field, o
         raise ValueError("one chain per wavelength (or a single chain) is required")
     if int(batch) < 1:
         raise ValueError("batch must be >= 1")
+    from .run import _fields_of
+
+    fields = _fields_of(field, nw)
+    origins = None
+    if detector_origin is not None and not isinstance(detector_origin, str):
+        origins = np.array(detector_origin, dtype=np.float64)
+        if origins.shape != (nw, 2):
+            raise ValueError(f"detector_origin must have shape ({nw}, 2), got {origins.shape}")
     nb = min(int(batch), nw)
     dev = _lib.DeviceFields(int(gridsize), nb, precision, device)
     try:
@@ -107,9 +118,12 @@ def run_broadband(pupil_diameter, wavelengths, weights, gridsize, zoom, field, o
             pad = nb - len(idx)
             wl_blk = [wls[i] for i in idx] + [wls[idx[-1]]] * pad
             ch_blk = [chains[i] for i in idx] + [chains[idx[-1]]] * pad
+            f_blk = field if isinstance(field, dict) else [fields[i] for i in idx] + [fields[idx[-1]]] * pad
+            o_blk = detector_origin if origins is None else origins[idx + [idx[-1]] * pad]
             w_blk = np.concatenate([w[idx], np.zeros(pad)])
-            res = run_batch(pupil_diameter, wl_blk, gridsize, zoom, field, ch_blk, precision=precision, device=device,
-                            outputs=(), dev=dev, sync=False, keep_psf=True, detector=detector, detector_weights=w_blk)
+            res = run_batch(pupil_diameter, wl_blk, gridsize, zoom, f_blk, ch_blk, precision=precision, device=device,
+                            outputs=(), dev=dev, sync=False, keep_psf=True, detector=detector, detector_weights=w_blk,
+                            detector_origin=o_blk)
             num = _last_num(ch_blk[0])
             handle = res[0][num].get("power_ticket")
             # every other reduction of the block is given back unread (as bench.measure does)

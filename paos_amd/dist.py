@@ -120,7 +120,8 @@ def run_sharded(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, 
     """The reference's fan-out over wavelengths / Monte-Carlo draws (pipeline.py:139-150,
     joblib workers on one host) on N GPUs: call from every rank of ``comm`` (a ``paos_amd.comm.Comm``;
     None = single process).  Rank 0 supplies ``wavelengths`` and ``opt_chains`` (other ranks may pass
-    None); they travel in ONE broadcast.  Every rank then propagates its contiguous shard in batches of
+    None); they travel in ONE broadcast.  ``field`` is one dict for every wavefront (every rank passes it) or, on
+    rank 0, a sequence of one dict per wavefront, which travels in that broadcast too.  Every rank then propagates its contiguous shard in batches of
     ``batch`` wavefronts with ``run_batch`` -- no further communication -- and returns
     ``[(global index, result dict), ...]`` for its shard, arrays asked for in ``outputs`` included (PSFs
     stay with the rank that computed them).  With ``gather`` every rank ALSO receives the per-wavefront
@@ -137,11 +138,19 @@ def run_sharded(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, 
 
     rank = comm.rank if comm is not None else 0
     world = comm.size if comm is not None else 1
-    work = {"wavelengths": list(wavelengths), "chains": list(opt_chains)} if rank == 0 else None
+    if rank == 0:
+        work = {"wavelengths": list(wavelengths), "chains": list(opt_chains)}
+        if not isinstance(field, dict):  # one field point per wavefront: travels with the work, sliced with the shard
+            work["fields"] = list(field)
+    else:
+        work = None
     work = broadcast_work(work, comm)
     total = len(work["chains"])
     if len(work["wavelengths"]) != total:
         raise ValueError("one wavelength per chain is required")
+    fields = work.get("fields")
+    if fields is not None and len(fields) != total:
+        raise ValueError(f"one field per chain is required: {len(fields)} fields for {total} chains")
     lo, hi = shard_bounds(total, rank, world)
     if device is None:
         device = int(os.environ.get("LOCAL_RANK", "0"))
@@ -156,7 +165,8 @@ def run_sharded(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, 
                     dev.close()
                 dev = (make_device or (lambda n, b: _lib.DeviceFields(n, b, precision, device)))(int(gridsize), nb)
                 dev_nb = nb
-            res = run_batch(pupil_diameter, work["wavelengths"][start:stop], gridsize, zoom, field,
+            res = run_batch(pupil_diameter, work["wavelengths"][start:stop], gridsize, zoom,
+                            field if fields is None else fields[start:stop],
                             work["chains"][start:stop], precision=precision, outputs=outputs, dev=dev,
                             metrics_radii_px=metrics_radii_px)
             mine.extend(zip(range(start, stop), res))

@@ -19,7 +19,9 @@ import atexit
 import gc
 import math
 import threading
+from collections.abc import Mapping, Sequence
 from copy import deepcopy
+from numbers import Real
 
 import numpy as np
 
@@ -237,6 +239,7 @@ class _Plans(list):
 
     ap = None
     _summary = None
+    chief_ray = None  # (batch, 2) chief-ray positions (x, y) at a saved surface (_walk)
 
     def summary(self):
         if self._summary is None:
@@ -263,6 +266,79 @@ class _Item:
         # until a coordinate break moves them -- no need to multiply
         self.still = field["ut"] == 0.0 and field["us"] == 0.0
         self.factors_t, self.factors_s = [], []
+
+
+def _fields_of(field, nb):
+    """``field`` of ``run_batch``: one dict for every wavefront, or a sequence of one dict per wavefront.  Returns the list
+    of ``nb`` dicts; every slope must be finite (``ValueError`` otherwise, and for a sequence of another length)."""
+    if isinstance(field, Mapping):
+        fields = [field] * nb
+    else:
+        if isinstance(field, (str, bytes)) or not isinstance(field, Sequence):
+            raise ValueError("field must be a dict {'us': ..., 'ut': ...} or a sequence of one such dict per chain")
+        fields = list(field)
+        if len(fields) != nb:
+            raise ValueError(f"one field per chain is required: {len(fields)} fields for {nb} chains")
+    for f in (fields[:1] if isinstance(field, Mapping) else fields):
+        if not isinstance(f, Mapping):
+            raise ValueError("every field must be a dict {'us': ..., 'ut': ...}")
+        for k in ("us", "ut"):
+            v = f.get(k)
+            if isinstance(v, bool) or not isinstance(v, Real) or not math.isfinite(float(v)):
+                raise ValueError(f"field slope {k!r} must be a finite number, got {v!r}")
+    return fields
+
+
+class _Rays:
+    """The two paraxial rays of every wavefront of a batch as arrays: ``vt`` / ``vs`` (batch, 2) and ``still`` (both rays
+    exactly zero).  The walk keeps them here so that items at different field points are planned with array arithmetic
+    (``_plan_batch(..., rays=)``) and advanced through a surface with one stacked ``A @ v`` (``advance``) -- the very
+    operations ``_plan_host`` and the per-item update form, so the numbers are the same.  ``_Item.vt`` / ``vs`` are
+    brought up to date around the per-item planner only (``to_states`` / ``from_states``)."""
+
+    def __init__(self, states):
+        self.vt = np.array([st.vt for st in states], dtype=np.float64).reshape(len(states), 2)
+        self.vs = np.array([st.vs for st in states], dtype=np.float64).reshape(len(states), 2)
+        self.still = np.array([bool(st.still) for st in states])
+        self._all_still = bool(self.still.all())
+
+    def all_still(self):
+        return self._all_still
+
+    def to_states(self, states):
+        for i, st in enumerate(states):
+            st.vt, st.vs, st.still = self.vt[i].copy(), self.vs[i].copy(), bool(self.still[i])
+
+    def from_states(self, states):
+        for i, st in enumerate(states):
+            self.vt[i], self.vs[i], self.still[i] = st.vt, st.vs, st.still
+        self._all_still = bool(self.still.all())
+
+    def coordinate_break(self, items):
+        """``coordinate_break`` of every item (run.py:81-91), once per distinct (rays, break) of the batch."""
+        memo = {}
+        for i, it in enumerate(items):
+            key = (self.vt[i].tobytes(), self.vs[i].tobytes(), it["xdec"], it["ydec"], it["xrot"], it["yrot"])
+            hit = memo.get(key)
+            if hit is None:
+                hit = memo[key] = coordinate_break(self.vt[i], self.vs[i], it["xdec"], it["ydec"], it["xrot"], it["yrot"], 0.0)
+            self.vt[i], self.vs[i] = hit
+        self.still = ~(self.vt.any(axis=1) | self.vs.any(axis=1))
+        self._all_still = bool(self.still.all())
+
+    def advance(self, col_t, col_s):
+        """``v <- A @ v`` for the items whose rays are not zero (an on-axis item's stay [0, 0] under every matrix)."""
+        if self._all_still:
+            return
+        mt, ms = _ray_matrices(col_t, col_s)
+        idx = np.flatnonzero(~self.still)
+        # (a stack of 2 x 2 @ 2 products: np.matmul runs the kernel of the single product once per item)
+        self.vt[idx] = np.matmul(mt[idx], self.vt[idx][:, :, None])[:, :, 0]
+        self.vs[idx] = np.matmul(ms[idx], self.vs[idx][:, :, None])[:, :, 0]
+
+    def chief(self):
+        """(batch, 2): the chief ray's position (x, y) = (vs[0], vt[0]) of every item, metres."""
+        return np.stack([self.vs[:, 0], self.vt[:, 0]], axis=1)
 
 
 class ABCDProduct(ABCD):
@@ -299,6 +375,7 @@ def forget_maps():
     _SAG_SEEN.clear()
     _FILLED_MAPS.clear()
     _GATE_COLUMNS.clear()
+    _RAY_COLUMNS.clear()
 
 
 _SAG_SEEN = {}  # id(array) -> (array, fingerprint) within ONE walk (cleared when a walk starts): the items of a batch share it
@@ -409,20 +486,37 @@ def _plan_host(st, item, n, dx, dy, wl, wz_of, aperture_plan=False):
     return plan
 
 
-def _plan_batch(states, items, n, dxs, dys, wls, wz_of, all_still=None):
+def _plan_batch(states, items, n, dxs, dys, wls, wz_of, all_still=None, rays=None):
     """``_plan_host`` for every wavefront of a batch.  The common case -- every item on axis (both paraxial rays zero:
     no coordinate break has moved them), the same kind of surface for all, no Grid Sag / PSD map to build -- is planned
     with array arithmetic (round 5: at 1024^2 x 256 wavefronts the per-item Python of this function was 40 % of a
     step that the GPU finishes in half the time the host needed to describe it).  The numbers are the ones
     ``_plan_host`` forms: with the rays at zero its ``xrad *= sqrt(1 / (0**2 + 1))`` and ``xdec - 0.0`` are exact
-    identities, the pixel quantities are the same IEEE divisions and sums.  Anything else takes the per-item path."""
+    identities, the pixel quantities are the same IEEE divisions and sums.  Anything else takes the per-item path.
+
+    ``rays`` (a ``_Rays``: the walk's) lifts the on-axis condition: the rays are read from (and a coordinate break is
+    applied to) its arrays, and the radii and centres are formed as ``_plan_host`` forms them, operation for operation
+    -- ``vs[1] ** 2`` of a NumPy scalar is C ``pow``, which rounds differently from ``vs[1] * vs[1]`` (what an array's
+    ``** 2`` forms) at ties, so the squares are taken of the scalars here too.  Only Grid Sag / PSD surfaces and mixed kinds then go item by item."""
     kind = items[0]["type"]
-    if all_still is None:
-        all_still = all(st.still for st in states)
-    fast = kind not in ("Coordinate Break", "Grid Sag", "PSD") and all_still and all(it["type"] == kind for it in items)
+    same_kind = all(it["type"] == kind for it in items)
+    if rays is not None:
+        fast = kind not in ("Grid Sag", "PSD") and same_kind
+        if fast and kind == "Coordinate Break":
+            rays.coordinate_break(items)
+    else:
+        if all_still is None:
+            all_still = all(st.still for st in states)
+        fast = kind not in ("Coordinate Break", "Grid Sag", "PSD") and all_still and same_kind
     if not fast:
-        return _Plans(_plan_host(st, it, n, dxs[i], dys[i], wls[i], lambda i=i: wz_of(i))
-                      for i, (st, it) in enumerate(zip(states, items)))
+        if rays is not None:
+            rays.to_states(states)
+        plans = _Plans(_plan_host(st, it, n, dxs[i], dys[i], wls[i], lambda i=i: wz_of(i))
+                       for i, (st, it) in enumerate(zip(states, items)))
+        if rays is not None:
+            rays.from_states(states)
+        return plans
+    moving = rays is not None and not rays.all_still()
     plans = _Plans({"aperture": None, "stop": bool(it["is_stop"]), "zernike": None, "phase_map": None} for it in items)
     aps = [it.get("aperture") for it in items]
     have = [i for i, a in enumerate(aps) if a is not None]
@@ -437,8 +531,18 @@ def _plan_batch(states, items, n, dxs, dys, wls, wz_of, all_still=None):
         shapes = [a["shape"] for a in sel]
         rect = np.array([sh == "rectangular" for sh in shapes])
         known = all(sh in ("elliptical", "rectangular") for sh in shapes)
-        xaper = np.where(np.isfinite(xc), xc, 0.0)  # (a missing centre falls back on the chief ray: zero here)
-        yaper = np.where(np.isfinite(yc), yc, 0.0)
+        if moving:  # run.py:97-108 with the rays of every item (_plan_host, operation for operation)
+            sel_rows = slice(None) if len(have) == len(aps) else np.asarray(have)
+            vs0, vs1 = rays.vs[sel_rows, 0], rays.vs[sel_rows, 1]
+            vt0, vt1 = rays.vt[sel_rows, 0], rays.vt[sel_rows, 1]
+            with np.errstate(all="ignore"):
+                xrad = xrad * np.sqrt(1 / (np.array([v ** 2 for v in vs1]) + 1))
+                yrad = yrad * np.sqrt(1 / (np.array([v ** 2 for v in vt1]) + 1))
+                xaper = np.where(np.isfinite(xc), xc, vs0) - vs0  # (a missing centre falls back on the chief ray)
+                yaper = np.where(np.isfinite(yc), yc, vt0) - vt0
+        else:
+            xaper = np.where(np.isfinite(xc), xc, 0.0)  # (a missing centre falls back on the chief ray: zero here)
+            yaper = np.where(np.isfinite(yc), yc, 0.0)
         with np.errstate(all="ignore"):
             ixc, iyc = xaper / dx + n / 2, yaper / dy + n / 2
             ea, eb = xrad / dx, yrad / dy   # semi-axes of an ellipse, FULL widths of a rectangle (wfo.py:224,261-264)
@@ -529,14 +633,35 @@ def _gate_arrays(col_t, col_s):
     return arrays
 
 
+_RAY_COLUMNS = {}
+
+
+def _ray_matrices(col_t, col_s):
+    """The (batch, 2, 2) stacks of a surface's ABCD matrices, remembered per column like ``_gate_arrays``."""
+    key = (id(col_t[0]), id(col_s[0]), len(col_t))
+    hit = _RAY_COLUMNS.get(key)
+    if hit is not None and hit[0] == _abcd.EPOCH[0] and hit[1] == col_t and hit[2] == col_s:
+        return hit[3]
+    arrays = (np.array([a() for a in col_t], dtype=np.float64), np.array([a() for a in col_s], dtype=np.float64))
+    if len(_RAY_COLUMNS) >= 1024:
+        _RAY_COLUMNS.clear()
+    _RAY_COLUMNS[key] = (_abcd.EPOCH[0], list(col_t), list(col_s), arrays)
+    return arrays
+
+
+def _identity_gates(item):
+    """The surface's ABCD matrices do nothing to the field: Mt = Ms = 1, fl = inf, T = 0, n1n2 = 1 (run.py:181-207)."""
+    Mt, fl, T, n1n2 = item["ABCDt"].gates()
+    return Mt == 1.0 and item["ABCDs"].M == 1.0 and math.isinf(fl) and T == 0.0 and n1n2 == 1.0
+
+
 def _inert(item):
     """A surface that does nothing to the field whatever the beam: no aperture, no stop, no phase, and identity ABCD
     matrices (zero thickness, no power, unit magnification, no change of medium) -- the image plane right behind a slit,
     a coordinate break.  (What run.py:181-207 would gate on: Mt = Ms = 1, fl = inf, T = 0, n1n2 = 1.)"""
     if item.get("aperture") is not None or item.get("is_stop") or item["type"] in ("Zernike", "Grid Sag", "PSD"):
         return False
-    Mt, fl, T, n1n2 = item["ABCDt"].gates()
-    return Mt == 1.0 and item["ABCDs"].M == 1.0 and math.isinf(fl) and T == 0.0 and n1n2 == 1.0
+    return _identity_gates(item)
 
 
 def _live_rows_after(plans, live, n):
@@ -806,7 +931,7 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
 
     prog_power = [None]  # ticket of the power of the field a program has just stored (flush(final_power=True))
     factor_cols_t, factor_cols_s = [], []  # [surface][item] ABCD factors met so far (run.py:215-219)
-    all_still = [all(st.still for st in states)]  # every item on axis: nothing moves the rays (refreshed behind a coordinate break)
+    rays = _Rays(states)  # the paraxial rays of every item (_plan_batch plans from them, `advance` moves them)
 
     def known_rows():
         return [list(r) for r in live] if any(r[0] > 0 or r[1] < dev.n for r in live) else None
@@ -877,11 +1002,11 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
                 readout.extend(beams.readout())
             return readout
 
-        plans = _plan_batch(states, items, n, dxs, dys, wls, lambda i: wz_dtf()[0][i], all_still[0])
-        if not all_still[0] or items[0]["type"] == "Coordinate Break" or any(it["type"] == "Coordinate Break" for it in items):
-            all_still[0] = all(st.still for st in states)
+        plans = _plan_batch(states, items, n, dxs, dys, wls, lambda i: wz_dtf()[0][i], rays=rays)
         saved = any(it["save"] for it in items)
         if saved:  # push_results scalars (run.py:12-27) are those BEFORE magnification / lens / propagate
+            # ... and so is the chief ray: behind this surface's coordinate break, before its ABCD matrices (run.py:209-210)
+            plans.chief_ray = rays.chief()
             wz, dtf = wz_dtf()
             fr, props, ext = state[:, beams.FRATIO].tolist(), beams.propagators(), beams.extents()
             for i, (it, p) in enumerate(zip(items, plans)):
@@ -896,11 +1021,7 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
         factor_cols_t.append(col_t)
         factor_cols_s.append(col_s)
         lens, stw, ptp, wts, inv_stw, inv_wts = beams.surface(*_gate_arrays(col_t, col_s))
-        if not all_still[0]:
-            for i, st in enumerate(states):
-                if not st.still:
-                    st.vt = col_t[i]() @ st.vt
-                    st.vs = col_s[i]() @ st.vs
+        rays.advance(col_t, col_s)
         if saved:
             for i, (it, p) in enumerate(zip(items, plans)):
                 if it["save"]:
@@ -972,7 +1093,10 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
                           not (any_stop or any_zern or any_map or (any_ap and not fuse_ap)))
             # ... the last surface -- or a surface behind which only inert ones follow (the image plane right behind a
             # saved slit): what the program stores here is what the chain ends with
-            ends_here = key == psf_at or (INERT_TAIL and pos + 1 >= inert_from and psf_at == order[-1])
+            # (only when this surface has no steps of its own: its lens / propagation would act on the field the inert
+            # surfaces receive -- a last mirror or lens some distance in front of the image plane)
+            ends_here = key == psf_at or (INERT_TAIL and pos + 1 >= inert_from and psf_at == order[-1] and
+                                          all(_identity_gates(it) for it in items))
             as_psf = (lean is not None and psf_at is not None and ends_here and only_saved and comp.pending()
                       and not dead[0])
             # a stop right behind the program needs the power of what the program stores; a saved surface whose
@@ -1117,11 +1241,13 @@ def run(pupil_diameter, wavelength, gridsize, zoom, field, opt_chain, precision=
 
 def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, precision="fp64",
               device=0, outputs=("psf",), dev=None, sync=True, stats=None, metrics_radii_px=None,
-              keep_psf=False, power=True, detector=None, detector_weights=None):
+              keep_psf=False, power=True, detector=None, detector_weights=None, detector_origin=None):
     """Propagate ``B = len(opt_chains)`` wavefronts together on one GPU.
 
     ``wavelengths[i]`` / ``opt_chains[i]`` describe wavefront ``i`` (chains must
-    contain the same surfaces).  Returns a list of ``B`` dicts
+    contain the same surfaces).  ``field`` is one field point ``{'us': slope_x, 'ut': slope_y}`` for every
+    wavefront, or a sequence of one such dict per wavefront (a field-of-view study in one batch); slopes must be
+    finite (``ValueError`` otherwise, and for a sequence of another length).  Returns a list of ``B`` dicts
     ``{num: {scalars..., 'power': sum|u|^2, ['psf'], ['wfo'], ['amplitude'], ['phase']}}``
     for saved surfaces (with ``sync=False`` the power is left as ``'power_ticket'``, a :class:`PowerTicket`:
     ``ticket.fetch()[i]`` -- or ``dev.norm2_fetch(ticket)[i]`` -- is item i's power; records whose powers come from one
@@ -1143,7 +1269,11 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     implies ``keep_psf``).  With ``detector_weights`` (one per item) ``w_i A_i`` is added, item after item, into the
     accumulator of ``dev`` (``dev.detector_fetch()`` reads it; a ``dev`` that is not on that detector yet is started
     there, ``dev.detector_begin``): nothing synchronises.  Without weights each item's record of the last surface gets
-    ``'detector'``, its image ``A_i`` as a (ny, nx) float64 array.
+    ``'detector'``, its image ``A_i`` as a (ny, nx) float64 array.  ``detector_origin`` says where each item's grid
+    centre lies in the image plane: None puts every one at the origin (the detector's ``(xc, yc)`` are then measured
+    from the grid centre); ``"chief_ray"`` puts item i's at its chief ray ``(vs_i[0], vt_i[0])`` at the last surface,
+    behind that surface's coordinate break and before its ABCD matrices (the point its apertures are centred on, so
+    ``(xc, yc)`` are measured from the optical axis); a (B, 2) array gives the positions ``(x0_i, y0_i)`` in metres.
     """
     nb = len(opt_chains)
     if len(wavelengths) != nb:
@@ -1168,13 +1298,28 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
         det_pitch = [None] * nb
     elif detector_weights is not None:
         raise ValueError("detector_weights without a detector")
-    states = [_Item(pupil_diameter, wl, gridsize, zoom, field) for wl in wavelengths]
+    det_origin, want_chief = None, isinstance(detector_origin, str)
+    if detector_origin is not None:
+        if detector is None:
+            raise ValueError("detector_origin without a detector")
+        if isinstance(detector_origin, str):
+            if detector_origin != "chief_ray":
+                raise ValueError(f"detector_origin must be None, 'chief_ray' or a (B, 2) array, got {detector_origin!r}")
+        else:
+            det_origin = np.array(detector_origin, dtype=np.float64)
+            if det_origin.shape != (nb, 2):
+                raise ValueError(f"detector_origin must have shape ({nb}, 2), got {det_origin.shape}")
+            if not np.all(np.isfinite(det_origin)):
+                raise ValueError("detector_origin must be finite")
+    fields = _fields_of(field, nb)
+    states = [_Item(pupil_diameter, wl, gridsize, zoom, f) for wl, f in zip(wavelengths, fields)]
     own = dev is None
     if own:
         dev = _lib.DeviceFields(int(gridsize), nb, precision, device)
     elif dev.batch != nb or dev.n != int(gridsize):
         raise ValueError("supplied DeviceFields does not match the batch")
     results = [dict() for _ in range(nb)]
+    chief = [None]  # detector_origin="chief_ray": the chief rays at the last surface
     what = {"psf": _lib.WHAT_INTENSITY, "wfo": _lib.WHAT_FIELD, "amplitude": _lib.WHAT_AMPLITUDE,
             "phase": _lib.WHAT_PHASE}
 
@@ -1239,6 +1384,8 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
         if det_pitch is not None and key == last_key:
             for i, plan in enumerate(plans):
                 det_pitch[i] = (plan["scalars"]["dx"], plan["scalars"]["dy"])
+            if want_chief:
+                chief[0] = plans.chief_ray
         # the last pass has stored |u|^2 and enqueued its sum -- for this surface, or for good (inert surfaces behind it)
         fused = (lean.psf_ticket if lean.psf_ticket is not None else lean.final_ticket) if lean is not None else None
         rows = lean.rows if lean is not None else None
@@ -1285,10 +1432,12 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
             dys = [p[1] for p in det_pitch]
             if getattr(dev, "detector", None) != detector:
                 dev.detector_begin(detector)
+            origins = chief[0] if want_chief else det_origin
+            placed = {} if origins is None else {"origins": origins}  # (paos_detector_*_placed)
             if detector_weights is not None:
-                dev.detector_add(dxs, dys, detector_weights)
+                dev.detector_add(dxs, dys, detector_weights, **placed)
             else:
-                images = dev.detector_images(dxs, dys)
+                images = dev.detector_images(dxs, dys, **placed)
                 for i in range(nb):
                     results[i][opt_chains[i][last_key]["num"]]["detector"] = images[i]
         if sync or own:
