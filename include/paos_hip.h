@@ -268,6 +268,34 @@ int paos_stw(paos_ctx* ctx, const double* params, int inverse);
 /* WFO.wts (wfo.py:528-545): fftshift(FFT(ifftshift(exp(i coef (x^2+y^2)) u))); sx, sy =
  * dx, dy; coef = pi / (dz wl). */
 int paos_wts(paos_ctx* ctx, const double* params, int inverse);
+/* ---- through-focus stacks (README.md, "Through-focus stacks") --------------------------------------------------------- */
+/* WFO.ptp (wfo.py:445-472) from ONE field to MANY defocus planes: u(dz) = ifft2(exp(-i coef (fx^2 + fy^2)) fft2(u)),
+ * ortho norms, shifts cancelled (wfo.py:462-472), with the forward transform done once and kept.  The reference's own
+ * precondition holds -- the wavefront is planar, C == 0 (wfo.py:458-460) -- and is the caller's to check
+ * (paos_amd/run.py), like the scalars of every other operator.
+ *
+ * paos_focus_begin: allocates, on first use, one more batch-sized complex buffer (the context's precision, the field's
+ * layout; freed by paos_focus_end and paos_ctx_destroy) and writes fft2 of every item's field into it: a pass along rows
+ * that reads the field and writes the buffer, then a pass along columns in place on the buffer.  The field is read, not
+ * modified (a pending deferred stop factor, paos_stop_defer_last_power, is applied first, as by every other reader of the
+ * field); it must be the complete field: rows and columns that merely stand for zeros (paos_start_rows / paos_start_box)
+ * have to be consumed by a pass program or made zeros (paos_zero_outside_box) before.  Enqueues only.
+ * PAOS_EINVAL when a stack is already open. */
+int paos_focus_begin(paos_ctx* ctx);
+/* The context's field <- u(dz) of every item, built from the kept spectrum: a pass along columns that reads the spectrum,
+ * applies the transfer function and the inverse transform and writes the field, then the inverse pass along rows in place
+ * on the field -- half the line transforms of paos_ptp, and no copy to restore the field.  params:
+ * [batch][PAOS_PHASE_STRIDE] = enable, sx, sy, coef, sgn as for paos_ptp (sx, sy = 1/(n dx), 1/(n dy), coef = pi wl dz,
+ * sgn = -1); enable = 0: no transfer function on that item (it receives its field back, up to the rounding of the two
+ * transforms).  Afterwards every entry point that reads the field works on the plane (paos_psf_keep[_power],
+ * paos_psf_metrics, paos_export*, paos_norm2*, paos_detector_* through the kept PSF); what the context knew about the
+ * field before (a power reduced on the way out of a pass program, a deferred stop) is dropped.  Any number of calls
+ * after one paos_focus_begin, in any order of dz: a plane does not depend on the planes computed before it.  Enqueues
+ * only.  PAOS_EINVAL without an open stack or for a parameter that is not finite (the context stays usable). */
+int paos_focus_plane(paos_ctx* ctx, const double* params);
+/* Releases the spectrum (waits for the planes enqueued so far).  The field keeps the last plane.  PAOS_EINVAL without
+ * an open stack. */
+int paos_focus_end(paos_ctx* ctx);
 /* A whole stretch of the propagation loop (run.py:193-207 over consecutive surfaces) as a
  * program of passes: lens phases (wfo.py:359-366), the checkerboard signs that replace
  * fftshift/ifftshift, the quadratic phases and ortho scalings of ptp / stw / wts

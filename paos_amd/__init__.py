@@ -10,6 +10,10 @@ gfx950 reached through a ctypes C-ABI (``libpaoship.so``, include/paos_hip.h).
 Importing the package does not need a GPU; creating a ``WFO`` or calling
 ``run`` loads the HIP library and fails loudly when it (or a GPU) is missing --
 there is no CPU fallback in the product path.
+
+``run_batch(..., focus_planes=[dz, ...])`` adds a through-focus stack behind the last surface: K defocus planes
+(``WFO.ptp(dz)`` of the last-surface field, on the image plane's sampling) from one chain walk and one forward
+transform, each with its power, arrays, metrics and detector image (README.md, "Through-focus stacks").
 """
 from .abcd import ABCD
 from .coordinate_break import coordinate_break

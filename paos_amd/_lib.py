@@ -85,6 +85,9 @@ SYMBOLS = {
     "paos_ptp": (ctypes.c_int, [_c_ctx, _dbl_p]),
     "paos_stw": (ctypes.c_int, [_c_ctx, _dbl_p, ctypes.c_int]),
     "paos_wts": (ctypes.c_int, [_c_ctx, _dbl_p, ctypes.c_int]),
+    "paos_focus_begin": (ctypes.c_int, [_c_ctx]),
+    "paos_focus_plane": (ctypes.c_int, [_c_ctx, _dbl_p]),
+    "paos_focus_end": (ctypes.c_int, [_c_ctx]),
     "paos_run_passes": (ctypes.c_int, [_c_ctx, ctypes.POINTER(Pass), ctypes.c_int, _dbl_p, ctypes.c_int]),
     "paos_copy_yardstick": (ctypes.c_int, [_c_ctx, ctypes.c_int, _dbl_p, _dbl_p]),
     "paos_record_set_stats": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
@@ -585,6 +588,21 @@ class DeviceFields:
     def wts(self, blocks, inverse):
         b = as_blocks(blocks, self.batch, PHASE_STRIDE)
         self._check(self._lib.paos_wts(self._ctx, _dptr(b), int(bool(inverse))), "paos_wts")
+
+    # -- through-focus stacks (paos_focus_*: README.md, "Through-focus stacks") -------------------------------------
+    def focus_begin(self):
+        """Keep fft2 of every item's field in a buffer of its own; the field is only read.  Enqueued only."""
+        self._check(self._lib.paos_focus_begin(self._ctx), "paos_focus_begin")
+
+    def focus_plane(self, blocks):
+        """field <- ifft2(exp(-i coef (fx^2 + fy^2)) * kept spectrum) per item; ``blocks`` as for ``ptp``
+        ([batch][5]: enable, 1/(n dx), 1/(n dy), pi wl dz, -1).  Any number of times after one ``focus_begin``."""
+        b = as_blocks(blocks, self.batch, PHASE_STRIDE)
+        self._check(self._lib.paos_focus_plane(self._ctx, _dptr(b)), "paos_focus_plane")
+
+    def focus_end(self):
+        """Release the kept spectrum; the field keeps the last plane."""
+        self._check(self._lib.paos_focus_end(self._ctx), "paos_focus_end")
 
     def copy_yardstick(self, reps=10):
         """(ms per launch, bytes per launch) of an in-place copy of the whole batch (measurement aid)."""

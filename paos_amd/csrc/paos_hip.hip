@@ -27,6 +27,7 @@
 
 #include "frugal_pass.h"
 #if PAOS_PART <= 0
+#include "focus_pass.h"
 #include "pointwise.h"
 #endif
 
@@ -98,6 +99,10 @@ struct paos_ctx {
   unsigned pitch = 0, item_stride = 0;
   hipStream_t stream = nullptr;
   double* psf = nullptr;  // batch x item_stride intensities kept on the device, blocked like the field (paos_psf_keep)
+  // a through-focus stack (paos_focus_begin .. paos_focus_end): the forward 2-D spectrum of every item's field, complex<T>
+  // of the context's precision in the field's own layout; allocated by the first paos_focus_begin
+  void* focus_spec = nullptr;
+  bool focus_open = false;
   double* map_dev = nullptr;      // one n x n phase map kept on the device (paos_phase_map_items) and the key it was uploaded under
   unsigned long long map_key = 0;
   // (round 5) the power sums of the last start, kept with everything they depend on (shape, constant, aperture records,
@@ -1714,6 +1719,57 @@ int fft_op(paos_ctx* c, FftOp op, const double* params, int inverse) {
                     (int)(g.blocks.size() / ((size_t)c->batch * FP_STRIDE)));
 }
 
+// ---- through-focus stacks: the out-of-place passes of focus_pass.h ----------------------
+// the generic pass kernel's geometry (FftCfg: one tile shape per grid size and type, 64 .. 4096)
+template <typename T, int N, int AXIS>
+int focus_launch(paos_ctx* c, const FocusArgs& a) {
+  using C = FftCfg<T, N>;
+  constexpr int LINES = AXIS == 0 ? C::ROW_LINES : C::COL_LINES;
+  constexpr int TILES = AXIS == 0 ? C::ROW_TILES : C::COL_TILES;
+  constexpr bool SPLIT = AXIS == 0 ? C::ROW_SPLIT : C::COL_SPLIT;
+  const dim3 grid(N / LINES / TILES, c->batch), block(TILES * LINES * N / C::E);
+  const size_t lds = (size_t)TILES * LINES * line_lds_bytes<T, N, SPLIT>();
+  auto kern = focus_pass_kernel<T, N, C::E, LINES, TILES, AXIS, C::BR, C::BC, SPLIT, C::MINW>;
+  if (lds > 48 * 1024) {
+    int rc = opt_in_lds(c, (const void*)kern, lds);
+    if (rc) return rc;
+  }
+  // for the launch timer: a full pass -- every line of every item is loaded, transformed once and stored
+  c->prof_next_tag = 0;
+  c->prof_next_bytes = (double)c->batch * N * N * 2.0 * (double)elem_bytes(c);
+  c->prof_next_lines = (double)c->batch * N;
+  const bool timed = timed_launch_begin(c, AXIS == 0 ? PAOS_KERNEL_PASS_ROWS : PAOS_KERNEL_PASS_COLS);
+  hipLaunchKernelGGL(kern, grid, block, lds, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  if (timed) HIPCHK(c, timed_launch_end(c, 0));
+  return PAOS_OK;
+}
+
+template <typename T>
+int focus_pass_t(paos_ctx* c, int axis, const FocusArgs& a) {
+  switch (c->n) {
+#define PAOS_FOCUS_CASE(N) case N: return axis == 0 ? focus_launch<T, N, 0>(c, a) : focus_launch<T, N, 1>(c, a)
+    PAOS_FOCUS_CASE(64);
+    PAOS_FOCUS_CASE(128);
+    PAOS_FOCUS_CASE(256);
+    PAOS_FOCUS_CASE(512);
+    PAOS_FOCUS_CASE(1024);
+    PAOS_FOCUS_CASE(2048);
+    PAOS_FOCUS_CASE(4096);
+#undef PAOS_FOCUS_CASE
+  }
+  return fail(c, PAOS_EUNSUPPORTED, "grid size must be a power of two in 64..4096");
+}
+
+int focus_pass(paos_ctx* c, int axis, int mode, const void* src, void* dst, const double* dparams) {
+  FocusArgs a{};
+  a.src = src; a.dst = dst; a.tw = c->tw; a.params = dparams;
+  a.scale = 1.0 / c->n;
+  a.mode = mode;
+  a.pitch = c->pitch; a.item_stride = c->item_stride;
+  return c->precision == PAOS_F64 ? focus_pass_t<double>(c, axis, a) : focus_pass_t<float>(c, axis, a);
+}
+
 template <typename T>
 std::vector<std::complex<T>> twiddles(int n) {
   std::vector<std::complex<T>> tw(n);
@@ -1910,6 +1966,7 @@ int paos_ctx_destroy(paos_ctx* c) {
   if (c->norm2) (void)hipFree(c->norm2);
   if (c->norm2_host) (void)hipHostFree(c->norm2_host);
   if (c->psf) (void)hipFree(c->psf);
+  if (c->focus_spec) (void)hipFree(c->focus_spec);
   if (c->map_dev) (void)hipFree(c->map_dev);
   if (c->psd_scratch) (void)hipFree(c->psd_scratch);
   if (c->start_norm2) (void)hipFree(c->start_norm2);
@@ -2779,6 +2836,49 @@ int paos_stw(paos_ctx* c, const double* params, int inverse) {
 int paos_wts(paos_ctx* c, const double* params, int inverse) {
   if (c) (void)hipSetDevice(c->device);  // one process may drive several GPUs
   return fft_op(c, OP_WTS, params, inverse);
+}
+
+// ---- through-focus stacks (include/paos_hip.h) --------------------------------------------
+int paos_focus_begin(paos_ctx* c) {
+  SETTLE_SCALE(c);  // a deferred stop factor belongs to the field the spectrum is taken of
+  if (c) (void)hipSetDevice(c->device);
+  if (!c) return fail(c, PAOS_EINVAL, "null context");
+  if (c->focus_open) return fail(c, PAOS_EINVAL, "paos_focus_begin: a focus stack is already open (paos_focus_end first)");
+  if (!c->focus_spec) HIPCHK(c, hipMalloc(&c->focus_spec, (size_t)c->item_stride * c->batch * elem_bytes(c)));
+  int rc = focus_pass(c, 0, FOCUS_FORWARD, c->field, c->focus_spec, nullptr);
+  if (rc) return rc;
+  rc = focus_pass(c, 1, FOCUS_FORWARD, c->focus_spec, c->focus_spec, nullptr);
+  if (rc) return rc;
+  c->focus_open = true;
+  return PAOS_OK;
+}
+
+int paos_focus_plane(paos_ctx* c, const double* params) {
+  if (c) (void)hipSetDevice(c->device);
+  if (!c || !params) return fail(c, PAOS_EINVAL, "null argument");
+  if (!c->focus_open) return fail(c, PAOS_EINVAL, "paos_focus_plane: no focus stack is open (paos_focus_begin first)");
+  for (int i = 0; i < c->batch; ++i)
+    for (int k = 0; k < FP_STRIDE; ++k)
+      if (!std::isfinite(params[(size_t)i * FP_STRIDE + k]))
+        return fail(c, PAOS_EINVAL, "paos_focus_plane: non-finite parameter of item " + std::to_string(i));
+  DROP_SCALE(c);  // the field is overwritten: what the context knew about it (its power, a pending factor) is void
+  const double* dparams = nullptr;
+  int rc = arena_push(c, params, (size_t)c->batch * FP_STRIDE, &dparams);
+  if (rc) return rc;
+  rc = focus_pass(c, 1, FOCUS_TRANSFER, c->focus_spec, c->field, dparams);
+  if (rc) return rc;
+  return focus_pass(c, 0, FOCUS_INVERSE, c->field, c->field, nullptr);
+}
+
+int paos_focus_end(paos_ctx* c) {
+  if (c) (void)hipSetDevice(c->device);
+  if (!c) return fail(c, PAOS_EINVAL, "null context");
+  if (!c->focus_open) return fail(c, PAOS_EINVAL, "paos_focus_end: no focus stack is open");
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the planes enqueued so far still read the spectrum
+  HIPCHK(c, hipFree(c->focus_spec));
+  c->focus_spec = nullptr;
+  c->focus_open = false;
+  return PAOS_OK;
 }
 
 static int zernike_apply(paos_ctx* c, int nmax, int kdim, const double* table, const double* params,

@@ -1239,9 +1239,114 @@ def run(pupil_diameter, wavelength, gridsize, zoom, field, opt_chain, precision=
     return retval
 
 
+class _FocusPlan:
+    """What ``run_batch(focus_planes=...)`` needs of the pilot beams behind the last surface: ``beams`` (the BeamBatch as
+    the whole chain leaves it) and ``planes`` (the defocus values, in the caller's order)."""
+
+    def __init__(self, beams, planes):
+        self.beams, self.planes = beams, planes
+
+
+def _plan_focus(states, chains, focus_planes, last_key):
+    """Every check of ``focus_planes`` -- on the scalars alone, so before anything is launched: the pilot beams are taken
+    through the chain the way ``_walk`` takes them (one planner call per surface), the field is not."""
+    try:
+        planes = [float(dz) for dz in focus_planes]
+    except TypeError:
+        raise ValueError("focus_planes must be a sequence of defocus values in metres") from None
+    if not all(math.isfinite(dz) for dz in planes):
+        raise ValueError("focus_planes must be finite")
+    if len(set(planes)) != len(planes):
+        raise ValueError("focus_planes must be distinct")
+    if last_key is None or not all(chain[last_key]["save"] for chain in chains):
+        raise ValueError("focus_planes need the last surface of the chain to be saved")
+    keys = [list(c.keys()) for c in chains]
+    if any(k != keys[0] for k in keys[1:]):
+        raise ValueError("batched chains must list the same surfaces (same keys, same order)")
+    st0 = states[0]
+    beams = BeamBatch(st0.pupil_diameter, [st.wavelength for st in states], st0.gridsize, st0.zoom)
+    for key in keys[0]:
+        items = [c[key] for c in chains]
+        beams.surface(*_gate_arrays([it["ABCDt"] for it in items], [it["ABCDs"] for it in items]))
+    n, state = beams.n, beams.state
+    for i in range(len(states)):
+        wl, dx, dy = (float(state[i, k]) for k in (beams.WL, beams.DX, beams.DY))
+        if state[i, beams.C] != 0.0:
+            raise ValueError(f"focus_planes: the wavefront of item {i} is not planar behind the last surface "
+                             f"(C = {float(state[i, beams.C])!r}); PTP wavefront should be planar")
+        limit = min(n * dx * dx / wl, n * dy * dy / wl)
+        for dz in planes:
+            if dz != 0.0 and abs(dz) < 0.001 * wl:
+                raise ValueError(f"focus_planes: |dz| = {abs(dz)!r} m is below a thousandth of item {i}'s wavelength "
+                                 f"({wl!r} m): the reference would skip that plane")
+            if abs(dz) > limit:
+                raise ValueError(f"focus_planes: |dz| = {abs(dz)!r} m exceeds N d^2 / wl = {limit!r} m of item {i}: "
+                                 "the plane would be aliased")
+    return _FocusPlan(beams, planes)
+
+
+def _focus_stack(dev, focus, outputs, what, metrics_radii_px, power, detector, placed):
+    """The planes of ``focus`` from the field ``dev`` holds behind the walk: [item][plane] dicts, planes in the caller's
+    order.  The nominal plane (dz = 0) is read first, from the untouched field; then one ``focus_begin`` and one
+    ``focus_plane`` per other plane."""
+    beams, nb = focus.beams, dev.batch
+    state = beams.state
+    z0 = state[:, beams.Z].copy()
+    wls, dxs, dys = (state[:, k].tolist() for k in (beams.WL, beams.DX, beams.DY))
+    stacks = [[None] * len(focus.planes) for _ in range(nb)]
+
+    def read(k, dz):
+        state[:, beams.Z] = z0 + dz
+        try:
+            wz, dtf = beams.readout()
+            zs = state[:, beams.Z].tolist()
+        finally:
+            state[:, beams.Z] = z0
+        recs = [{"dz": dz, "z": zs[i], "distancetofocus": float(dtf[i]), "wz": float(wz[i])} for i in range(nb)]
+        for i, rec in enumerate(recs):
+            for name in outputs:
+                rec[name] = dev.download(i, what[name])
+        if metrics_radii_px is not None:
+            for rec, met in zip(recs, dev.psf_metrics(metrics_radii_px)):
+                rec["metrics"] = met
+        ticket = None
+        if detector is not None:
+            if power:
+                ticket = dev.psf_keep_power()
+            else:
+                dev.psf_keep()
+            for rec, image in zip(recs, dev.detector_images(dxs, dys, **placed)):
+                rec["detector"] = image
+        elif power:
+            ticket = dev.norm2_enqueue()
+        if ticket is not None:
+            for rec, p in zip(recs, dev.norm2_fetch(ticket)):
+                rec["power"] = float(p)
+        for i, rec in enumerate(recs):
+            stacks[i][k] = rec
+
+    order = sorted(range(len(focus.planes)), key=lambda k: focus.planes[k] != 0.0)  # (stable: the nominal plane first)
+    opened = False
+    try:
+        for k in order:
+            dz = focus.planes[k]
+            if dz != 0.0:
+                if not opened:
+                    dev.focus_begin()
+                    opened = True
+                blocks = [[1.0, 1.0 / (beams.n * dxs[i]), 1.0 / (beams.n * dys[i]), (np.pi * wls[i] * dz), -1.0]
+                          for i in range(nb)]  # (PilotBeam.ptp's block: wfo.py:462-472)
+                dev.focus_plane(blocks)
+            read(k, dz)
+    finally:
+        if opened:
+            dev.focus_end()
+    return stacks
+
+
 def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, precision="fp64",
               device=0, outputs=("psf",), dev=None, sync=True, stats=None, metrics_radii_px=None,
-              keep_psf=False, power=True, detector=None, detector_weights=None, detector_origin=None):
+              keep_psf=False, power=True, detector=None, detector_weights=None, detector_origin=None, focus_planes=None):
     """Propagate ``B = len(opt_chains)`` wavefronts together on one GPU.
 
     ``wavelengths[i]`` / ``opt_chains[i]`` describe wavefront ``i`` (chains must
@@ -1274,6 +1379,28 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     from the grid centre); ``"chief_ray"`` puts item i's at its chief ray ``(vs_i[0], vt_i[0])`` at the last surface,
     behind that surface's coordinate break and before its ABCD matrices (the point its apertures are centred on, so
     ``(xc, yc)`` are measured from the optical axis); a (B, 2) array gives the positions ``(x0_i, y0_i)`` in metres.
+
+    ``focus_planes`` (K distinct finite defocus values in metres, positive along the propagation direction) adds a
+    through-focus stack behind the LAST surface, which must be saved (README.md, "Through-focus stacks"): with u_i, wl_i,
+    dx_i, dy_i and the pilot beam (z, zw0, zr, C) of item i as everything the last surface does leaves them, plane ``dz`` is
+    ``ifft2(exp(-i pi wl_i dz (fx^2 + fy^2)) fft2(u_i))`` -- ``WFO.ptp(dz)``, wfo.py:445-472, ortho norms, ``fx, fy`` from
+    ``np.fft.fftfreq(N, dx_i)`` / ``(N, dy_i)`` -- on the unchanged sampling, at ``z + dz``.  The chain is walked once and
+    the forward transform is done once (``paos_focus_begin``); a plane costs one inverse 2-D transform
+    (``paos_focus_plane``).  The nominal records are what they are without the keyword; the last surface's record of each
+    item additionally gets ``'focus'``, a list of K dicts in the order given: ``dz``, ``z``, ``distancetofocus``, ``wz``
+    (the planner's formulas at ``z + dz``), ``power`` (unless ``power=False``), the arrays named in ``outputs``,
+    ``'metrics'`` with ``metrics_radii_px`` and ``'detector'`` (the plane's image ``A_i``) with a detector.  ``dz == 0.0`` is
+    served from the untouched last-surface field, before any other plane is computed.  ``ValueError``, before anything is
+    launched: a last surface that is not saved; values that are not finite or not distinct; an item whose wavefront is not
+    planar behind the last surface (``C != 0``, the reference's own precondition, wfo.py:458-460); ``0 < |dz| < wl_i /
+    1000`` (the reference would skip that ``ptp``, wfo.py:454, for some items of a batch and not for others);
+    ``|dz| > N dx_i^2 / wl_i`` or ``N dy_i^2 / wl_i`` (beyond it the transfer function's phase steps by more than pi
+    between neighbouring frequency samples at the band edge: the plane would be aliased); ``detector_weights`` (what the
+    accumulator should hold across planes is ambiguous).  The reference's ``propagate`` switches to ``wts`` and rescales
+    the grid once ``|z + dz - zw0| >= 2 zr`` (wfo.py:280-302, 547-572); a focus stack keeps ``ptp`` and the
+    detector-plane sampling on purpose -- inside ``2 zr`` the two coincide.  The planes synchronise (their powers are
+    fetched as they are made); afterwards the field of ``dev`` holds the last plane computed and, with a detector, its
+    PSF buffer that plane's PSF.
     """
     nb = len(opt_chains)
     if len(wavelengths) != nb:
@@ -1313,6 +1440,11 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
                 raise ValueError("detector_origin must be finite")
     fields = _fields_of(field, nb)
     states = [_Item(pupil_diameter, wl, gridsize, zoom, f) for wl, f in zip(wavelengths, fields)]
+    focus = None
+    if focus_planes is not None:
+        if detector_weights is not None:
+            raise ValueError("focus_planes with detector_weights: what the accumulator should hold across planes is ambiguous")
+        focus = _plan_focus(states, list(opt_chains), focus_planes, last_key)
     own = dev is None
     if own:
         dev = _lib.DeviceFields(int(gridsize), nb, precision, device)
@@ -1325,7 +1457,8 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
 
     # nobody reads an array at a saved surface: the walk may skip writing dead rows at the start and store the PSF
     # straight from the last pass (csrc/frugal_pass.h: STORE)
-    lean = _WalkState() if (not outputs and metrics_radii_px is None) else None
+    # (a focus stack needs the field of the last surface: the ordinary walk)
+    lean = _WalkState() if (not outputs and metrics_radii_px is None and focus is None) else None
     tickets = []  # (_Reduction, [(item index, record)], post): powers are fetched after the walk, so the
     # host keeps planning while the GPU works (no mid-chain synchronisation) -- except when a chain
     # saves more surfaces than the library has ticket slots: then the oldest are fetched early
@@ -1440,6 +1573,13 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
                 images = dev.detector_images(dxs, dys, **placed)
                 for i in range(nb):
                     results[i][opt_chains[i][last_key]["num"]]["detector"] = images[i]
+        if focus is not None:
+            placed = {}
+            if detector is not None and (chief[0] if want_chief else det_origin) is not None:
+                placed = {"origins": chief[0] if want_chief else det_origin}
+            stacks = _focus_stack(dev, focus, outputs, what, metrics_radii_px, power, detector, placed)
+            for i in range(nb):
+                results[i][opt_chains[i][last_key]["num"]]["focus"] = stacks[i]
         if sync or own:
             drain()
         else:  # caller synchronises later: hand out handles to the reductions still outstanding (nothing waits here)
