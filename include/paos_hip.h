@@ -296,6 +296,36 @@ int paos_focus_plane(paos_ctx* ctx, const double* params);
 /* Releases the spectrum (waits for the planes enqueued so far).  The field keeps the last plane.  PAOS_EINVAL without
  * an open stack. */
 int paos_focus_end(paos_ctx* ctx);
+/* ---- transfer functions: OTF / MTF of the kept PSFs (README.md, "Transfer functions") ---------------------------------- */
+/* No reference counterpart: the reference hands out PSFs and leaves their transforms to the user.  With P_i[k][j] the kept
+ * PSF of item i (paos_psf_keep, paos_psf_keep_power or a pass program with final_intensity; rows k along y, grid centre at
+ * pixel N/2):
+ *   S_i[ky][kx]   = sum_k sum_j P_i[k][j] exp(-2 pi i ((j - N/2)(kx - N/2) + (k - N/2)(ky - N/2)) / N)
+ *   OTF_i[ky][kx] = S_i[ky][kx] / S_i[N/2][N/2],   MTF_i = |OTF_i|
+ * = fftshift(fft2(ifftshift(P_i))) over its zero-frequency value, zero frequency at pixel [N/2][N/2]; pixel [ky][kx] is the
+ * spatial frequency ((kx - N/2) / (N dx_i), (ky - N/2) / (N dy_i)) in cycles per metre.  The PSF is real, so two of its rows
+ * are packed into one complex line and only the columns 0 .. N/2 of the spectrum are transformed a second time: about N line
+ * transforms per item where a complex 2-D transform runs 2 N (csrc/otf_pass.h).  The other half is handed out as the exact
+ * conjugate mirror: the arrays are Hermitian, and the MTF point-symmetric, bit for bit.  OTF[N/2][N/2] is exactly 1 + 0 i;
+ * an item whose PSF sums to zero gets zeros (scale = DC != 0 ? 1 / DC : 0), not NaN.  The transforms run in the context's
+ * precision (fp32 contexts read the double PSFs and transform in float); normalisation, modulus and results are doubles. */
+enum { PAOS_OTF_MTF = 0, PAOS_OTF_COMPLEX = 1 };
+/* The spectra of every item's kept PSF into a batch-sized complex buffer of the context's precision (the field's layout;
+ * allocated on first use, freed by paos_ctx_destroy): a pass along rows that reads the PSFs and writes the buffer, a pass
+ * along columns in place on the buffer.  The PSF buffer and the field are only read.  Enqueues only (no synchronisation).
+ * PAOS_EINVAL before any PSF was kept.  Whatever stores PSFs afterwards (paos_psf_keep, paos_psf_keep_power, a pass
+ * program with final_intensity) makes the result stale: paos_otf_fetch / paos_otf_cuts then fail with PAOS_EINVAL until
+ * the next paos_otf_compute, rather than serve the transform of an older PSF. */
+int paos_otf_compute(paos_ctx* ctx);
+/* One item to the host, row-major [ky][kx]: what = PAOS_OTF_MTF: N x N doubles; PAOS_OTF_COMPLEX: N x N complex128.
+ * Synchronises.  PAOS_EINVAL for a bad item or `what`, a null buffer, before paos_otf_compute or when its result is
+ * stale (the context stays usable). */
+int paos_otf_fetch(paos_ctx* ctx, int item, int what, void* host_out);
+/* MTF cuts of EVERY item in one launch and one copy: host_out[batch][2][N/2 + 1] = |OTF| along fy = 0, fx >= 0 (pixels
+ * [N/2][N/2 + m]) and along fx = 0, fy >= 0 (pixels [N/2 + m][N/2]), m = 0 (zero frequency) .. N/2 (Nyquist, pixel 0 of
+ * the fetched array by the mirror symmetry) -- bit for bit the values paos_otf_fetch hands out.  Synchronises.
+ * PAOS_EINVAL as for paos_otf_fetch. */
+int paos_otf_cuts(paos_ctx* ctx, double* host_out);
 /* A whole stretch of the propagation loop (run.py:193-207 over consecutive surfaces) as a
  * program of passes: lens phases (wfo.py:359-366), the checkerboard signs that replace
  * fftshift/ifftshift, the quadratic phases and ortho scalings of ptp / stw / wts

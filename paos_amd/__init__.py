@@ -14,6 +14,9 @@ there is no CPU fallback in the product path.
 ``run_batch(..., focus_planes=[dz, ...])`` adds a through-focus stack behind the last surface: K defocus planes
 (``WFO.ptp(dz)`` of the last-surface field, on the image plane's sampling) from one chain walk and one forward
 transform, each with its power, arrays, metrics and detector image (README.md, "Through-focus stacks").
+
+``run_batch(..., outputs=("mtf", "otf"), mtf_cuts=True)`` hands out the transfer functions of the last surface's PSFs,
+computed on the GPU by a packed real-input 2-D transform (README.md, "Transfer functions").
 """
 from .abcd import ABCD
 from .coordinate_break import coordinate_break

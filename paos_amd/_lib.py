@@ -24,6 +24,7 @@ PW_SIGN, PW_QPHASE_CENTRED, PW_QPHASE_NATURAL, PW_SCALE, PW_MASK = 1, 2, 3, 4, 5
 PWF_MUL2PI = 1
 PWF_X_ONLY, PWF_Y_ONLY = 2, 4  # PW_SIGN: (-1)^column / (-1)^row instead of the checkerboard (-1)^(row + column)
 MAX_PW = 6
+OTF_MTF, OTF_COMPLEX = 0, 1  # paos_otf_fetch: |OTF| as doubles / the complex OTF
 NORM_SLOTS = 64  # PAOS_NORM_SLOTS: tickets of paos_norm2_enqueue that may be outstanding
 
 
@@ -88,6 +89,9 @@ SYMBOLS = {
     "paos_focus_begin": (ctypes.c_int, [_c_ctx]),
     "paos_focus_plane": (ctypes.c_int, [_c_ctx, _dbl_p]),
     "paos_focus_end": (ctypes.c_int, [_c_ctx]),
+    "paos_otf_compute": (ctypes.c_int, [_c_ctx]),
+    "paos_otf_fetch": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "paos_otf_cuts": (ctypes.c_int, [_c_ctx, _dbl_p]),
     "paos_run_passes": (ctypes.c_int, [_c_ctx, ctypes.POINTER(Pass), ctypes.c_int, _dbl_p, ctypes.c_int]),
     "paos_copy_yardstick": (ctypes.c_int, [_c_ctx, ctypes.c_int, _dbl_p, _dbl_p]),
     "paos_record_set_stats": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
@@ -603,6 +607,30 @@ class DeviceFields:
     def focus_end(self):
         """Release the kept spectrum; the field keeps the last plane."""
         self._check(self._lib.paos_focus_end(self._ctx), "paos_focus_end")
+
+    # -- transfer functions (paos_otf_*: README.md, "Transfer functions") -------------------------------------------
+    def otf_compute(self):
+        """The spectra of every item's kept PSF (``psf_keep``, ``psf_keep_power`` or a pass program that stored the PSF):
+        a packed real-input 2-D transform, about N line transforms per item.  Enqueued only."""
+        self._check(self._lib.paos_otf_compute(self._ctx), "paos_otf_compute")
+
+    def otf_fetch(self, item=0, what="mtf"):
+        """One item's transfer function, zero frequency at pixel [N/2][N/2] and normalised to 1 there: ``"mtf"`` --
+        (N, N) float64 ``|OTF|``; ``"otf"`` -- (N, N) complex128.  Synchronises.  Refused (``PaosHipError``) before
+        ``otf_compute`` and after the PSFs were stored anew without another ``otf_compute``."""
+        if what not in ("mtf", "otf"):
+            raise ValueError(f"what must be 'mtf' or 'otf', got {what!r}")
+        out = np.empty((self.n, self.n), dtype=np.float64 if what == "mtf" else np.complex128)
+        self._check(self._lib.paos_otf_fetch(self._ctx, int(item), OTF_MTF if what == "mtf" else OTF_COMPLEX,
+                                             out.ctypes.data_as(ctypes.c_void_p)), "paos_otf_fetch")
+        return out
+
+    def otf_cuts(self):
+        """(batch, 2, N/2 + 1) float64: every item's MTF along +fx (``[:, 0]``) and along +fy (``[:, 1]``), from zero
+        frequency to Nyquist -- one launch and one small copy for the whole batch.  Synchronises."""
+        out = np.empty((self.batch, 2, self.n // 2 + 1), dtype=np.float64)
+        self._check(self._lib.paos_otf_cuts(self._ctx, _dptr(out)), "paos_otf_cuts")
+        return out
 
     def copy_yardstick(self, reps=10):
         """(ms per launch, bytes per launch) of an in-place copy of the whole batch (measurement aid)."""

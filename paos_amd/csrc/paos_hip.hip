@@ -28,6 +28,7 @@
 #include "frugal_pass.h"
 #if PAOS_PART <= 0
 #include "focus_pass.h"
+#include "otf_pass.h"
 #include "pointwise.h"
 #endif
 
@@ -103,6 +104,12 @@ struct paos_ctx {
   // of the context's precision in the field's own layout; allocated by the first paos_focus_begin
   void* focus_spec = nullptr;
   bool focus_open = false;
+  // transfer functions (paos_otf_compute): the spectra of the kept PSFs, complex<T> of the context's precision in the
+  // field's own layout (columns 0 .. N/2 hold the spectrum, otf_pass.h); allocated by the first paos_otf_compute.
+  // otf_valid: the buffer was computed from what the PSF buffer holds NOW -- cleared by everything that stores a PSF
+  void* otf_spec = nullptr;
+  bool otf_computed = false, otf_valid = false;
+  double* otf_cuts = nullptr;  // [batch][2][N/2 + 1], allocated by the first paos_otf_cuts
   double* map_dev = nullptr;      // one n x n phase map kept on the device (paos_phase_map_items) and the key it was uploaded under
   unsigned long long map_key = 0;
   // (round 5) the power sums of the last start, kept with everything they depend on (shape, constant, aperture records,
@@ -1495,6 +1502,7 @@ int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const do
   }
   if (final_ticket && final_mode != 2) {
     if (!c->psf) HIPCHK(c, hipMalloc(&c->psf, (size_t)c->batch * c->item_stride * sizeof(double)));
+    c->otf_valid = false;  // a new PSF: the transfer functions computed from the previous one are stale
     fused_store = n_passes > 0 && low[n_passes - 1].ok && low[n_passes - 1].kpre <= 1 && low[n_passes - 1].kmid <= 1;
     if (fused_store)
       for (const FrugalItem& fi : low[n_passes - 1].items) fused_store = fused_store && fi.active != 0.0;
@@ -1770,6 +1778,71 @@ int focus_pass(paos_ctx* c, int axis, int mode, const void* src, void* dst, cons
   return c->precision == PAOS_F64 ? focus_pass_t<double>(c, axis, a) : focus_pass_t<float>(c, axis, a);
 }
 
+// ---- transfer functions: the packed real-input passes of otf_pass.h -----------------------
+// the generic pass kernel's geometry again; rows: the N/2 packed lines, columns: 0 .. N/2 rounded up to whole workgroups
+template <typename T, int N, int AXIS>
+int otf_launch(paos_ctx* c, const OtfArgs& a) {
+  using C = FftCfg<T, N>;
+  constexpr int LINES = AXIS == 0 ? C::ROW_LINES : C::COL_LINES;
+  constexpr int TILES = AXIS == 0 ? C::ROW_TILES : C::COL_TILES;
+  constexpr bool SPLIT = AXIS == 0 ? C::ROW_SPLIT : C::COL_SPLIT;
+  constexpr int PER_WG = LINES * TILES;
+  constexpr int WGS = AXIS == 0 ? N / 2 / PER_WG : (N / 2 + 1 + PER_WG - 1) / PER_WG;
+  const dim3 grid(WGS, c->batch), block(TILES * LINES * N / C::E);
+  const size_t lds = (size_t)TILES * LINES * line_lds_bytes<T, N, SPLIT>();
+  auto kern = [] {
+    if constexpr (AXIS == 0) return otf_row_kernel<T, N, C::E, LINES, TILES, C::BR, C::BC, SPLIT, C::MINW>;
+    else return otf_col_kernel<T, N, C::E, LINES, TILES, C::BR, C::BC, SPLIT, C::MINW>;
+  }();
+  if (lds > 48 * 1024) {
+    int rc = opt_in_lds(c, (const void*)kern, lds);
+    if (rc) return rc;
+  }
+  // for the launch timer: the lines the launch transforms (the column launch: those of its last workgroup that lie beyond
+  // column N/2 included) and the bytes it moves (rows: N/2 x 2 PSF rows in, N/2 lines out; columns: N/2 rows of the
+  // column and of its mirror in, N rows out)
+  const double eb = (double)elem_bytes(c);
+  c->prof_next_tag = 0;
+  c->prof_next_lines = (double)c->batch * WGS * PER_WG;
+  c->prof_next_bytes = AXIS == 0 ? (double)c->batch * N * (N * 8.0 + N / 2 * eb) : (double)c->batch * (N / 2 + 1) * 2.0 * N * eb;
+  const bool timed = timed_launch_begin(c, AXIS == 0 ? PAOS_KERNEL_PASS_ROWS : PAOS_KERNEL_PASS_COLS);
+  hipLaunchKernelGGL(kern, grid, block, lds, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  if (timed) HIPCHK(c, timed_launch_end(c, 0));
+  return PAOS_OK;
+}
+
+template <typename T>
+int otf_pass_t(paos_ctx* c, int axis, const OtfArgs& a) {
+  switch (c->n) {
+#define PAOS_OTF_CASE(N) case N: return axis == 0 ? otf_launch<T, N, 0>(c, a) : otf_launch<T, N, 1>(c, a)
+    PAOS_OTF_CASE(64);
+    PAOS_OTF_CASE(128);
+    PAOS_OTF_CASE(256);
+    PAOS_OTF_CASE(512);
+    PAOS_OTF_CASE(1024);
+    PAOS_OTF_CASE(2048);
+    PAOS_OTF_CASE(4096);
+#undef PAOS_OTF_CASE
+  }
+  return fail(c, PAOS_EUNSUPPORTED, "grid size must be a power of two in 64..4096");
+}
+
+int otf_pass(paos_ctx* c, int axis) {
+  OtfArgs a{};
+  a.psf = c->psf; a.spec = c->otf_spec; a.tw = c->tw;
+  a.pitch = c->pitch; a.item_stride = c->item_stride;
+  return c->precision == PAOS_F64 ? otf_pass_t<double>(c, axis, a) : otf_pass_t<float>(c, axis, a);
+}
+
+// fetch and cuts share their preconditions
+int otf_ready(paos_ctx* c, const char* who) {
+  if (!c->otf_spec || !c->otf_computed) return fail(c, PAOS_EINVAL, std::string(who) + ": no transfer functions computed (paos_otf_compute)");
+  if (!c->otf_valid)
+    return fail(c, PAOS_EINVAL, std::string(who) + ": the PSFs were stored anew since paos_otf_compute: the transfer functions are stale (compute again)");
+  return PAOS_OK;
+}
+
 template <typename T>
 std::vector<std::complex<T>> twiddles(int n) {
   std::vector<std::complex<T>> tw(n);
@@ -1967,6 +2040,8 @@ int paos_ctx_destroy(paos_ctx* c) {
   if (c->norm2_host) (void)hipHostFree(c->norm2_host);
   if (c->psf) (void)hipFree(c->psf);
   if (c->focus_spec) (void)hipFree(c->focus_spec);
+  if (c->otf_spec) (void)hipFree(c->otf_spec);
+  if (c->otf_cuts) (void)hipFree(c->otf_cuts);
   if (c->map_dev) (void)hipFree(c->map_dev);
   if (c->psd_scratch) (void)hipFree(c->psd_scratch);
   if (c->start_norm2) (void)hipFree(c->start_norm2);
@@ -2254,6 +2329,7 @@ int paos_psf_keep(paos_ctx* c) {
   if (!c) return fail(c, PAOS_EINVAL, "null context");
   if (!c->psf) HIPCHK(c, hipMalloc(&c->psf, (size_t)c->batch * c->item_stride * sizeof(double)));
   c->psf_zero_axis = -1;  // the whole buffer is rewritten
+  c->otf_valid = false;   // ... and the transfer functions computed from the previous PSFs are stale
   const dim3 grid(pw_blocks(c), c->batch), block(kPwThreads);
   if (c->precision == PAOS_F64)
     hipLaunchKernelGGL((intensity_kernel<double, BR, Lay<double>::BC>), grid, block, 0, c->stream,
@@ -2484,6 +2560,7 @@ int psf_keep_power_impl(paos_ctx* c, int* ticket) {
     return fail(c, PAOS_EINVAL, "64 power reductions outstanding: fetch earlier tickets (paos_norm2_fetch) first");
   if (!c->psf) HIPCHK(c, hipMalloc(&c->psf, (size_t)c->batch * c->item_stride * sizeof(double)));
   c->psf_zero_axis = -1;  // the whole buffer is rewritten
+  c->otf_valid = false;   // ... and the transfer functions computed from the previous PSFs are stale
   const dim3 grid(c->nparts, c->batch), block(kPwThreads);
   if (c->precision == PAOS_F64)
     hipLaunchKernelGGL((intensity_power_kernel<double, BR, Lay<double>::BC>), grid, block, 0, c->stream,
@@ -2879,6 +2956,59 @@ int paos_focus_end(paos_ctx* c) {
   c->focus_spec = nullptr;
   c->focus_open = false;
   return PAOS_OK;
+}
+
+// ---- transfer functions (include/paos_hip.h) ------------------------------------------------
+int paos_otf_compute(paos_ctx* c) {
+  if (c) (void)hipSetDevice(c->device);
+  if (!c) return fail(c, PAOS_EINVAL, "null context");
+  if (!c->psf) return fail(c, PAOS_EINVAL, "paos_otf_compute: no PSF kept (paos_psf_keep)");
+  if (!c->otf_spec) HIPCHK(c, hipMalloc(&c->otf_spec, (size_t)c->item_stride * c->batch * elem_bytes(c)));
+  c->otf_valid = false;
+  int rc = otf_pass(c, 0);
+  if (rc) return rc;
+  rc = otf_pass(c, 1);
+  if (rc) return rc;
+  c->otf_computed = c->otf_valid = true;
+  return PAOS_OK;
+}
+
+int paos_otf_fetch(paos_ctx* c, int item, int what, void* host_out) {
+  if (c) (void)hipSetDevice(c->device);
+  if (!c || !host_out || item < 0 || item >= c->batch || (what != PAOS_OTF_MTF && what != PAOS_OTF_COMPLEX))
+    return fail(c, PAOS_EINVAL, "paos_otf_fetch: bad item/what or null buffer");
+  int rc = otf_ready(c, "paos_otf_fetch");
+  if (rc) return rc;
+  const int cplx = what == PAOS_OTF_COMPLEX;
+  const size_t n2 = (size_t)c->n * c->n;
+  const dim3 grid((unsigned)std::min<size_t>((n2 + kPwThreads - 1) / kPwThreads, 2048)), block(kPwThreads);
+  if (c->precision == PAOS_F64)
+    hipLaunchKernelGGL((otf_fetch_kernel<double, BR, Lay<double>::BC>), grid, block, 0, c->stream,
+                       (const cx<double>*)c->otf_spec + (size_t)item * c->item_stride, c->staging, c->n, c->pitch, cplx);
+  else
+    F32_BR_SWITCH(c, hipLaunchKernelGGL((otf_fetch_kernel<float, FBR, Lay<float>::BC>), grid, block, 0, c->stream,
+                       (const cx<float>*)c->otf_spec + (size_t)item * c->item_stride, c->staging, c->n, c->pitch, cplx));
+  HIPCHK(c, hipGetLastError());
+  return copy_to_host(c, host_out, c->staging, n2 * (cplx ? 16 : 8));
+}
+
+int paos_otf_cuts(paos_ctx* c, double* host_out) {
+  if (c) (void)hipSetDevice(c->device);
+  if (!c || !host_out) return fail(c, PAOS_EINVAL, "paos_otf_cuts: null argument");
+  int rc = otf_ready(c, "paos_otf_cuts");
+  if (rc) return rc;
+  const int len = c->n / 2 + 1;
+  const size_t bytes = (size_t)c->batch * 2 * len * sizeof(double);
+  if (!c->otf_cuts) HIPCHK(c, hipMalloc(&c->otf_cuts, bytes));
+  const dim3 grid((2 * len + kPwThreads - 1) / kPwThreads, c->batch), block(kPwThreads);
+  if (c->precision == PAOS_F64)
+    hipLaunchKernelGGL((otf_cuts_kernel<double, BR, Lay<double>::BC>), grid, block, 0, c->stream,
+                       (const cx<double>*)c->otf_spec, c->otf_cuts, c->n, c->pitch, c->item_stride);
+  else
+    F32_BR_SWITCH(c, hipLaunchKernelGGL((otf_cuts_kernel<float, FBR, Lay<float>::BC>), grid, block, 0, c->stream,
+                       (const cx<float>*)c->otf_spec, c->otf_cuts, c->n, c->pitch, c->item_stride));
+  HIPCHK(c, hipGetLastError());
+  return copy_to_host(c, host_out, c->otf_cuts, bytes);
 }
 
 static int zernike_apply(paos_ctx* c, int nmax, int kdim, const double* table, const double* params,

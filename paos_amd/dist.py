@@ -136,6 +136,8 @@ def run_sharded(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, 
     from . import _lib
     from .run import run_batch
 
+    if {"mtf", "otf"} & set(outputs):  # (README.md, "Transfer functions": run_batch only)
+        raise ValueError("run_sharded does not hand out transfer functions ('mtf' / 'otf'): use run_batch")
     rank = comm.rank if comm is not None else 0
     world = comm.size if comm is not None else 1
     if rank == 0:

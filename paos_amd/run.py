@@ -1285,10 +1285,35 @@ def _plan_focus(states, chains, focus_planes, last_key):
     return _FocusPlan(beams, planes)
 
 
-def _focus_stack(dev, focus, outputs, what, metrics_radii_px, power, detector, placed):
+class _OtfRequest:
+    """What ``run_batch`` hands out of the transfer functions of the kept PSFs: the full arrays named in ``arrays``
+    ('mtf', 'otf') and, with ``cuts``, the two MTF cuts with their frequency axes."""
+
+    def __init__(self, arrays, cuts):
+        self.arrays, self.cuts = tuple(arrays), bool(cuts)
+
+    def __bool__(self):
+        return bool(self.arrays) or self.cuts
+
+    def attach(self, dev, recs, dxs, dys):
+        """``recs[i]`` gets item i's entries, from the PSFs ``dev`` keeps right now.  Synchronises."""
+        dev.otf_compute()
+        for i, rec in enumerate(recs):
+            for name in self.arrays:
+                rec[name] = dev.otf_fetch(i, name)
+        if self.cuts:
+            cuts = dev.otf_cuts()
+            m = np.arange(dev.n // 2 + 1, dtype=np.float64)
+            for i, rec in enumerate(recs):
+                rec["mtf_x"], rec["mtf_y"] = cuts[i, 0].copy(), cuts[i, 1].copy()
+                rec["freq_x"], rec["freq_y"] = m / (dev.n * dxs[i]), m / (dev.n * dys[i])
+
+
+def _focus_stack(dev, focus, outputs, what, metrics_radii_px, power, detector, placed, otf=None):
     """The planes of ``focus`` from the field ``dev`` holds behind the walk: [item][plane] dicts, planes in the caller's
     order.  The nominal plane (dz = 0) is read first, from the untouched field; then one ``focus_begin`` and one
-    ``focus_plane`` per other plane."""
+    ``focus_plane`` per other plane.  ``otf`` (an ``_OtfRequest``): every plane's PSF is kept and its transfer functions
+    are attached to the plane's dict."""
     beams, nb = focus.beams, dev.batch
     state = beams.state
     z0 = state[:, beams.Z].copy()
@@ -1310,13 +1335,16 @@ def _focus_stack(dev, focus, outputs, what, metrics_radii_px, power, detector, p
             for rec, met in zip(recs, dev.psf_metrics(metrics_radii_px)):
                 rec["metrics"] = met
         ticket = None
-        if detector is not None:
+        if detector is not None or otf:
             if power:
                 ticket = dev.psf_keep_power()
             else:
                 dev.psf_keep()
-            for rec, image in zip(recs, dev.detector_images(dxs, dys, **placed)):
-                rec["detector"] = image
+            if detector is not None:
+                for rec, image in zip(recs, dev.detector_images(dxs, dys, **placed)):
+                    rec["detector"] = image
+            if otf:
+                otf.attach(dev, recs, dxs, dys)
         elif power:
             ticket = dev.norm2_enqueue()
         if ticket is not None:
@@ -1346,7 +1374,8 @@ def _focus_stack(dev, focus, outputs, what, metrics_radii_px, power, detector, p
 
 def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, precision="fp64",
               device=0, outputs=("psf",), dev=None, sync=True, stats=None, metrics_radii_px=None,
-              keep_psf=False, power=True, detector=None, detector_weights=None, detector_origin=None, focus_planes=None):
+              keep_psf=False, power=True, detector=None, detector_weights=None, detector_origin=None, focus_planes=None,
+              mtf_cuts=False):
     """Propagate ``B = len(opt_chains)`` wavefronts together on one GPU.
 
     ``wavelengths[i]`` / ``opt_chains[i]`` describe wavefront ``i`` (chains must
@@ -1401,16 +1430,37 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     detector-plane sampling on purpose -- inside ``2 zr`` the two coincide.  The planes synchronise (their powers are
     fetched as they are made); afterwards the field of ``dev`` holds the last plane computed and, with a detector, its
     PSF buffer that plane's PSF.
+
+    ``'mtf'`` / ``'otf'`` in ``outputs`` and ``mtf_cuts=True`` hand out the transfer functions of every item's PSF at the
+    LAST surface, which must be saved (README.md, "Transfer functions"; computed on the GPU from the kept PSFs by a packed
+    real-input transform, ``paos_otf_compute``; any of the three implies ``keep_psf``): ``'mtf'`` a (N, N) float64 array
+    ``|OTF|`` and ``'otf'`` the (N, N) complex128 OTF, zero frequency at pixel [N/2][N/2] and exactly 1 there, attached to
+    the last surface's record only; ``mtf_cuts`` gives that record ``'mtf_x'``, ``'mtf_y'`` -- the MTF along ``fy = 0, fx
+    >= 0`` and along ``fx = 0, fy >= 0``, N/2 + 1 values each from zero frequency to Nyquist, fetched for the whole batch
+    in one small copy -- and ``'freq_x'``, ``'freq_y'`` = ``m / (N dx_i)``, ``m / (N dy_i)`` in cycles per metre with the
+    item's sampling at the last surface.  ``outputs=()`` with ``mtf_cuts=True`` runs on the lean walk.  With
+    ``focus_planes`` every plane's dict gets the same keys (through-focus MTF); the ``dz == 0.0`` plane's arrays equal the
+    nominal record's bit for bit.  They synchronise: with ``sync=False`` any of the three is a ``ValueError``, as is a last
+    surface that is not saved -- before anything is launched.
     """
     nb = len(opt_chains)
     if len(wavelengths) != nb:
         raise ValueError("one wavelength per chain is required")
     if nb == 0:
         return []
-    unknown = set(outputs) - {"psf", "wfo", "amplitude", "phase"}
+    unknown = set(outputs) - {"psf", "wfo", "amplitude", "phase", "mtf", "otf"}
     if unknown:
         raise ValueError(f"unknown outputs {sorted(unknown)}")
     last_key = list(opt_chains[0].keys())[-1] if len(opt_chains[0]) else None
+    # the transfer functions of the last surface's PSFs: not arrays of the field (they are not downloaded per saved surface)
+    otf = _OtfRequest([name for name in ("mtf", "otf") if name in outputs], mtf_cuts)
+    outputs = tuple(name for name in outputs if name not in ("mtf", "otf"))
+    if otf:
+        if not sync:
+            raise ValueError("'mtf' / 'otf' outputs and mtf_cuts synchronise: they cannot be combined with sync=False")
+        if last_key is None or not all(chain[last_key]["save"] for chain in opt_chains):
+            raise ValueError("'mtf' / 'otf' outputs and mtf_cuts need the last surface of the chain to be saved")
+        keep_psf = True
     det_pitch = None
     if detector is not None:
         if last_key is None or not all(chain[last_key]["save"] for chain in opt_chains):
@@ -1573,11 +1623,14 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
                 images = dev.detector_images(dxs, dys, **placed)
                 for i in range(nb):
                     results[i][opt_chains[i][last_key]["num"]]["detector"] = images[i]
+        if otf:  # (before a focus stack, whose planes store their own PSFs)
+            recs = [results[i][opt_chains[i][last_key]["num"]] for i in range(nb)]
+            otf.attach(dev, recs, [rec["dx"] for rec in recs], [rec["dy"] for rec in recs])
         if focus is not None:
             placed = {}
             if detector is not None and (chief[0] if want_chief else det_origin) is not None:
                 placed = {"origins": chief[0] if want_chief else det_origin}
-            stacks = _focus_stack(dev, focus, outputs, what, metrics_radii_px, power, detector, placed)
+            stacks = _focus_stack(dev, focus, outputs, what, metrics_radii_px, power, detector, placed, otf)
             for i in range(nb):
                 results[i][opt_chains[i][last_key]["num"]]["focus"] = stacks[i]
         if sync or own:
