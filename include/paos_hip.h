@@ -153,6 +153,15 @@ int paos_zero_outside_rows(paos_ctx* ctx, const double* live_rows);
  * touch the field. */
 int paos_start_box(paos_ctx* ctx, double re, double im, int shape, const double* aperture, const double* stop,
                    const double* write_rows, const double* write_cols);
+/* paos_start_box and the Zernike surface right behind it (paos_zernike's nmax, kdim, table, params, param_stride) in ONE write
+ * of the field: what the two calls leave inside the box, bit for bit -- the weight is evaluated once per group of items with
+ * one start field, the polynomials once per group of items with one wfe map inside it -- without storing the start field and
+ * reading it back.  For callers that let nothing read the field between the two surfaces.  power_ticket (may be NULL): the
+ * power of the start field itself, summed from the weights exactly as paos_norm2_enqueue_box(write_rows, write_cols, same_as
+ * = items with one start field) would sum it from memory -- a saved first surface reports it. */
+int paos_start_zernike_box(paos_ctx* ctx, double re, double im, int shape, const double* aperture, const double* stop,
+                           const double* write_rows, const double* write_cols, int nmax, int kdim, const double* table,
+                           const double* params, int param_stride, int* power_ticket);
 /* make everything outside the box rows x cols of every item real zeros (live_cols may be NULL: whole rows) */
 int paos_zero_outside_box(paos_ctx* ctx, const double* live_rows, const double* live_cols);
 /* host row-major complex128 -> batch item (WFO._wfo assignment in notebooks/tests) */

@@ -116,6 +116,8 @@ SYMBOLS = {
     "paos_phase_map_items": (ctypes.c_int, [_c_ctx, _dbl_p, ctypes.c_ulonglong, ctypes.c_int, _dbl_p, _dbl_p]),
     "paos_psd_screen": (ctypes.c_int, [_c_ctx, _dbl_p, _dbl_p, _dbl_p, ctypes.c_ulonglong, _dbl_p]),
     "paos_start_box": (ctypes.c_int, [_c_ctx, ctypes.c_double, ctypes.c_double, ctypes.c_int, _dbl_p, _dbl_p, _dbl_p, _dbl_p]),
+    "paos_start_zernike_box": (ctypes.c_int, [_c_ctx, ctypes.c_double, ctypes.c_double, ctypes.c_int, _dbl_p, _dbl_p, _dbl_p, _dbl_p,
+                                              ctypes.c_int, ctypes.c_int, _dbl_p, _dbl_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "paos_zero_outside_box": (ctypes.c_int, [_c_ctx, _dbl_p, _dbl_p]),
     "paos_norm2_enqueue_box": (ctypes.c_int, [_c_ctx, _dbl_p, _dbl_p, _dbl_p, ctypes.POINTER(ctypes.c_int)]),
     "paos_norm2_enqueue_rows": (ctypes.c_int, [_c_ctx, _dbl_p, ctypes.POINTER(ctypes.c_int)]),
@@ -735,6 +737,30 @@ class DeviceFields:
             return
         self._check(self._lib.paos_start(self._ctx, v.real, v.imag, int(shape), _dptr(b),
                                          _dptr(st) if st is not None else None), "paos_start")
+
+    def start_zernike(self, value, shape, blocks, stop, write_rows, write_cols, nmax, kdim, table, zblocks, power=False):
+        """``start(..., write_rows, write_cols)`` followed by ``zernike(nmax, kdim, table, zblocks)`` in one write of the
+        field (paos_start_zernike_box): for a caller that lets nothing read the field in between.  ``power``: also
+        enqueue the power of the start field itself (what ``norm2_enqueue(write_rows, same_as, write_cols)`` would sum
+        between the two calls) and return its ticket."""
+        b = np.ascontiguousarray(blocks, dtype=np.float64)
+        if b.shape != (self.batch, APERTURE_STRIDE):
+            raise ValueError("aperture blocks must be [batch][8]")
+        st = None if stop is None else np.ascontiguousarray(stop, dtype=np.float64)
+        if st is not None and st.shape != (self.batch,):
+            raise ValueError("stop flags must be [batch]")
+        t = np.ascontiguousarray(table, dtype=np.float64).reshape(-1)
+        zb = np.ascontiguousarray(zblocks, dtype=np.float64)
+        if zb.ndim != 2 or zb.shape[0] != self.batch:
+            raise ValueError("zernike blocks must be [batch][stride]")
+        v = complex(value)
+        ticket = ctypes.c_int(-1)
+        self._check(self._lib.paos_start_zernike_box(self._ctx, v.real, v.imag, int(shape), _dptr(b),
+                                                     _dptr(st) if st is not None else None, _dptr(self._rows(write_rows)),
+                                                     _dptr(self._rows(write_cols)), int(nmax), int(kdim), _dptr(t), _dptr(zb),
+                                                     int(zb.shape[1]), ctypes.byref(ticket) if power else None),
+                    "paos_start_zernike_box")
+        return ticket.value if power else None
 
     def pupil_aperture(self, shape, blocks):
         """Pupil = pixels where the exact mask of the aperture object is non-zero (run.py:136-141)."""

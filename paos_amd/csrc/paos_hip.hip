@@ -2125,11 +2125,25 @@ static std::vector<double> rounded_cols(const paos_ctx* c, const double* cols) {
   return out;
 }
 
+// The Zernike surface right behind the start, applied while the start field is written (paos_start_zernike_box)
+struct StartZernike {
+  int nmax, kdim, param_stride;
+  const double *table, *params;
+  int* power_ticket;  // optional: the power of the start field itself, as paos_norm2_enqueue_box would sum it
+};
+static int zernike_check(paos_ctx* c, int nmax, int kdim, const double* table, const double* params, int param_stride);
+
 static int start_impl(paos_ctx* c, double re, double im, int shape, const double* aperture, const double* stop,
-                      const double* write_rows, const double* write_cols = nullptr) {
+                      const double* write_rows, const double* write_cols = nullptr, const StartZernike* zk = nullptr) {
   if (c) (void)hipSetDevice(c->device);
   if (!c || !aperture) return fail(c, PAOS_EINVAL, "null argument");
   if (shape != PAOS_SHAPE_ELLIPSE && shape != PAOS_SHAPE_RECT) return fail(c, PAOS_EINVAL, "unknown aperture shape");
+  if (zk) {
+    int rcz = zernike_check(c, zk->nmax, zk->kdim, zk->table, zk->params, zk->param_stride);
+    if (rcz) return rcz;
+    if (zk->power_ticket && c->norm_busy[next_norm_slot(c)])
+      return fail(c, PAOS_EINVAL, "64 power reductions outstanding: fetch earlier tickets (paos_norm2_fetch) first");
+  }
   std::vector<double> flags(c->batch, 0.0);
   bool any_stop = false;
   if (stop)
@@ -2184,6 +2198,57 @@ static int start_impl(paos_ctx* c, double re, double im, int shape, const double
       glen[i] = (double)members.size() - goff[i];
     }
   }
+  // ... and, with a Zernike surface riding on the write, inside each of them the groups of items with one wfe map: records equal
+  // in everything but the wavelength (zernike_apply's rule, PAOS_SHARE_WFE); items without a Zernike record form one more
+  const double *dzt = nullptr, *dzp = nullptr, *dsubs = nullptr, *dlead = nullptr, *dsame = nullptr;
+  if (zk) {
+    static const bool share_wfe = [] { const char* e = getenv("PAOS_SHARE_WFE"); return !(e && e[0] == '0'); }();
+    const int ps = zk->param_stride;
+    auto same_map = [&](int a, int b) {
+      const double *qa = zk->params + (size_t)a * ps, *qb = zk->params + (size_t)b * ps;
+      for (int k = 0; k < ps; ++k)
+        if (k != ZP_INV_WL && std::memcmp(qa + k, qb + k, sizeof(double))) return false;
+      return true;
+    };
+    std::vector<double> subs, sub_members, lead(c->batch, 0.0), same(c->batch, 0.0);
+    for (int i = 0; i < c->batch; ++i) {
+      const int g0 = (int)goff[i], gl = (int)glen[i];
+      for (int g = 0; g < gl; ++g) { same[(int)members[g0 + g]] = (double)i; }
+      if (gl == 0) continue;
+      lead[i] = 1.0;
+      const size_t first_sub = subs.size() / 3;
+      std::vector<char> placed(gl, 0);
+      for (int g = 0; g < gl; ++g) {
+        if (placed[g]) continue;
+        const int a = (int)members[g0 + g];
+        const bool off = zk->params[(size_t)a * ps + ZP_ENABLE] == 0.0;
+        subs.push_back(off ? -1.0 : (double)a);
+        subs.push_back((double)sub_members.size());
+        size_t count = 0;
+        for (int h = g; h < gl; ++h) {
+          const int b = (int)members[g0 + h];
+          if (placed[h]) continue;
+          const bool b_off = zk->params[(size_t)b * ps + ZP_ENABLE] == 0.0;
+          if (h == g || (off && b_off) || (!off && !b_off && share_wfe && same_map(a, b))) {
+            placed[h] = 1;
+            sub_members.push_back((double)b);
+            ++count;
+          }
+        }
+        subs.push_back((double)count);
+      }
+      goff[i] = (double)first_sub;               // the leader's run of sub-group records ...
+      glen[i] = (double)(subs.size() / 3 - first_sub);  // ... and their number
+    }
+    members = sub_members;
+    if ((rc = arena_push(c, zk->table, (size_t)(zk->nmax + 1) * zk->kdim * 3, &dzt))) return rc;
+    if ((rc = arena_push(c, zk->params, (size_t)c->batch * ps, &dzp))) return rc;
+    if ((rc = arena_push(c, subs.data(), subs.size(), &dsubs))) return rc;
+    if (zk->power_ticket) {  // one sum per group of identical start fields (paos_norm2_enqueue_box: same_as)
+      if ((rc = arena_push(c, lead.data(), lead.size(), &dlead))) return rc;
+      if ((rc = arena_push(c, same.data(), same.size(), &dsame))) return rc;
+    }
+  }
   const double *dgoff = nullptr, *dglen = nullptr, *dmembers = nullptr;
   if ((rc = arena_push(c, goff.data(), goff.size(), &dgoff))) return rc;
   if ((rc = arena_push(c, glen.data(), glen.size(), &dglen))) return rc;
@@ -2215,9 +2280,27 @@ static int start_impl(paos_ctx* c, double re, double im, int shape, const double
       hipLaunchKernelGGL(norm2_final_kernel, dim3(c->batch), block, 0, c->stream, c->partial, c->norm2,   \
                          c->nparts, ds, 1, dpower_of);                                                  \
     }                                                                                                   \
-    hipLaunchKernelGGL((start_write_kernel<T, BRV, Lay<T>::BC, S>), dim3(pw_blocks(c), c->batch), block, 0, \
+    if (!zk)                                                                                            \
+      hipLaunchKernelGGL((start_write_kernel<T, BRV, Lay<T>::BC, S>), dim3(pw_blocks(c), c->batch), block, 0, \
+                         c->stream, (cx<T>*)c->field, dp, c->n, c->pitch, c->item_stride, re, im,        \
+                         (const double*)c->norm2, ds, drows, dgoff, dglen, dmembers, dcols);            \
+    else if (zk->nmax <= 8)                                                                             \
+      START_ZERNIKE_LAUNCH(T, BRV, S, 8);                                                               \
+    else                                                                                                \
+      START_ZERNIKE_LAUNCH(T, BRV, S, 0);                                                               \
+  } while (0)
+  // (orders up to 8 run on the unrolled build, like zernike_kernel) ... and the power of the start field from the weights,
+  // before the reduction behind it rewrites c->norm2
+#define START_ZERNIKE_LAUNCH(T, BRV, S, NC)                                                             \
+  do {                                                                                                  \
+    hipLaunchKernelGGL((zernike_start_write_kernel<T, BRV, Lay<T>::BC, S, NC>), dim3(pw_blocks(c), c->batch), block, 0, \
                        c->stream, (cx<T>*)c->field, dp, c->n, c->pitch, c->item_stride, re, im,          \
-                       (const double*)c->norm2, ds, drows, dgoff, dglen, dmembers, dcols);              \
+                       (const double*)c->norm2, ds, drows, dcols, dgoff, dglen, dsubs, dmembers, dzt, dzp, \
+                       zk->param_stride, zk->nmax, zk->kdim);                                           \
+    if (zk->power_ticket)                                                                               \
+      hipLaunchKernelGGL((start_norm2_partial_kernel<T, BRV, Lay<T>::BC, S>), dim3(c->nparts, c->batch), block, 0, \
+                         c->stream, c->partial, dp, c->n, c->pitch, c->item_stride, re, im,              \
+                         (const double*)c->norm2, ds, dlead, drows, dcols);                             \
   } while (0)
   if (c->precision == PAOS_F64) {
     if (shape == PAOS_SHAPE_ELLIPSE) START_LAUNCH(double, BR, 0); else START_LAUNCH(double, BR, 1);
@@ -2225,11 +2308,13 @@ static int start_impl(paos_ctx* c, double re, double im, int shape, const double
     if (shape == PAOS_SHAPE_ELLIPSE) F32_BR_SWITCH(c, START_LAUNCH(float, FBR, 0)); else F32_BR_SWITCH(c, START_LAUNCH(float, FBR, 1));
   }
 #undef START_LAUNCH
+#undef START_ZERNIKE_LAUNCH
   HIPCHK(c, hipGetLastError());
   if (any_stop && !power_found && !c->start_key.empty()) {  // keep the sums just evaluated (c->norm2 is rewritten by every reduction)
     if (!c->start_norm2) HIPCHK(c, hipMalloc(&c->start_norm2, (size_t)c->batch * sizeof(double)));
     HIPCHK(c, hipMemcpyAsync(c->start_norm2, c->norm2, (size_t)c->batch * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   }
+  if (zk && zk->power_ticket) return psf_power_ticket(c, c->partial, c->nparts, zk->power_ticket, dsame);
   return PAOS_OK;
 }
 
@@ -2248,6 +2333,15 @@ int paos_start_box(paos_ctx* c, double re, double im, int shape, const double* a
                    const double* write_rows, const double* write_cols) {
   DROP_SCALE(c);
   return start_impl(c, re, im, shape, aperture, stop, write_rows, write_cols);
+}
+
+int paos_start_zernike_box(paos_ctx* c, double re, double im, int shape, const double* aperture, const double* stop,
+                           const double* write_rows, const double* write_cols, int nmax, int kdim, const double* table,
+                           const double* params, int param_stride, int* power_ticket) {
+  DROP_SCALE(c);
+  if (c && (!write_rows || !write_cols)) return fail(c, PAOS_EINVAL, "paos_start_zernike_box: null window");
+  const StartZernike zk{nmax, kdim, param_stride, table, params, power_ticket};
+  return start_impl(c, re, im, shape, aperture, stop, write_rows, write_cols, &zk);
 }
 
 int paos_zero_outside_box(paos_ctx* c, const double* live_rows, const double* live_cols) {
@@ -3011,12 +3105,10 @@ int paos_otf_cuts(paos_ctx* c, double* host_out) {
   return copy_to_host(c, host_out, c->otf_cuts, bytes);
 }
 
-static int zernike_apply(paos_ctx* c, int nmax, int kdim, const double* table, const double* params,
-                         int param_stride, double* host_wfe, bool use_pupil, const double* same_as = nullptr) {
+static int zernike_check(paos_ctx* c, int nmax, int kdim, const double* table, const double* params, int param_stride) {
   if (!c || !table || !params) return fail(c, PAOS_EINVAL, "null argument");
   if (nmax < 0 || kdim < nmax / 2 + 1 || param_stride < ZP_HEAD + 2 * (nmax + 1) * kdim)
     return fail(c, PAOS_EINVAL, "inconsistent Zernike table dimensions");
-  if (use_pupil && !c->mask) return fail(c, PAOS_EINVAL, "no pupil defined (paos_pupil_aperture / paos_pupil_upload)");
   // NaN is the kernel's "outside the disk" marker in the wfe map: a record that would make NaN inside the disk (a
   // non-finite coefficient, offset or sampling, a radius <= 0) must not come back looking masked
   for (int i = 0; i < c->batch; ++i) {
@@ -3026,8 +3118,16 @@ static int zernike_apply(paos_ctx* c, int nmax, int kdim, const double* table, c
     for (int k = ZP_DX; k < param_stride; ++k)
       if (!std::isfinite(q[k])) return fail(c, PAOS_EINVAL, "non-finite Zernike parameter");
   }
+  return PAOS_OK;
+}
+
+static int zernike_apply(paos_ctx* c, int nmax, int kdim, const double* table, const double* params,
+                         int param_stride, double* host_wfe, bool use_pupil, const double* same_as = nullptr) {
+  int rc = zernike_check(c, nmax, kdim, table, params, param_stride);
+  if (rc) return rc;
+  if (use_pupil && !c->mask) return fail(c, PAOS_EINVAL, "no pupil defined (paos_pupil_aperture / paos_pupil_upload)");
   const double *dt = nullptr, *dp = nullptr;
-  int rc = arena_push(c, table, (size_t)(nmax + 1) * kdim * 3, &dt);
+  rc = arena_push(c, table, (size_t)(nmax + 1) * kdim * 3, &dt);
   if (rc) return rc;
   rc = arena_push(c, params, (size_t)c->batch * param_stride, &dp);
   if (rc) return rc;

@@ -1138,6 +1138,66 @@ __global__ void __launch_bounds__(kMaskWaves * 64) mask_lines_kernel(MaskJobs jo
 //                  then coefC[am][k], coefS[am][k]] with the (-1)^k norm Z product folded in.
 enum : int { ZP_ENABLE = 0, ZP_DX, ZP_DY, ZP_RADIUS, ZP_ORIGIN_Y, ZP_COS_OFF, ZP_SIN_OFF, ZP_INV_WL, ZP_HEAD };
 
+// The Zernike sum of one pixel inside the unit disk (rho <= 1): zernike_kernel and zernike_start_write_kernel share it, so that
+// both form the wfe by the same operations in the same order.
+template <int NMAXC>
+__device__ __forceinline__ double zernike_wfe(const double* table, const double* coef_c, const double* coef_s, int nmax, int kdim,
+                                              double x, double y, double rr, double rho, bool origin_y, double co, double so) {
+  double wfe = 0.0;
+  double c1 = 1.0, s1 = 0.0;
+  if (rr > 0.0) {
+    c1 = (origin_y ? y : x) / rr;
+    s1 = (origin_y ? x : y) / rr;
+  }
+  const double cr = c1 * co - s1 * so, sr = s1 * co + c1 * so;
+  const double xj = 1.0 - 2.0 * rho * rho;
+  double rho_pow = 1.0, cm = 1.0, sm = 0.0;
+  auto order = [&](int am, int k_end) __attribute__((always_inline)) {
+    double pkm1 = 0.0, pk = 1.0;
+    for (int k = 0; k <= k_end; ++k) {
+      if (k > 0) {
+        const double* abc = table + ((size_t)am * kdim + k) * 3;
+        const double pn = (abc[0] * xj + abc[1]) * pk - abc[2] * pkm1;
+        pkm1 = pk;
+        pk = pn;
+      }
+      const size_t ci = (size_t)am * kdim + k;
+      wfe += (rho_pow * pk) * (coef_c[ci] * cm + coef_s[ci] * sm);
+    }
+    rho_pow *= rho;
+    const double cn = cm * cr - sm * sr;
+    sm = sm * cr + cm * sr;
+    cm = cn;
+  };
+  if constexpr (NMAXC > 0) {  // same operations in the same order, loops unrolled
+#pragma unroll
+    for (int am = 0; am <= NMAXC; ++am) {
+      if (am > nmax) break;
+      const int kmax = (nmax - am) / 2;
+      double pkm1 = 0.0, pk = 1.0;
+#pragma unroll
+      for (int k = 0; k <= (NMAXC - am) / 2; ++k) {
+        if (k > kmax) break;
+        if (k > 0) {
+          const double* abc = table + ((size_t)am * kdim + k) * 3;
+          const double pn = (abc[0] * xj + abc[1]) * pk - abc[2] * pkm1;
+          pkm1 = pk;
+          pk = pn;
+        }
+        const size_t ci = (size_t)am * kdim + k;
+        wfe += (rho_pow * pk) * (coef_c[ci] * cm + coef_s[ci] * sm);
+      }
+      rho_pow *= rho;
+      const double cn = cm * cr - sm * sr;
+      sm = sm * cr + cm * sr;
+      cm = cn;
+    }
+  } else {
+    for (int am = 0; am <= nmax; ++am) order(am, (nmax - am) / 2);
+  }
+  return wfe;
+}
+
 // NMAXC > 0: the loops over the azimuthal order and the radial index are unrolled for orders up to NMAXC (the host
 // picks this build when nmax <= NMAXC): the recurrence constants and coefficients of a whole order are then fetched
 // in one go instead of five dependent scalar loads per term (round 3: the kernel waited four times as long as it
@@ -1179,57 +1239,7 @@ __global__ void zernike_kernel(cx<T>* field, const double* table, const double* 
     const bool masked = rho > 1.0 || (pupil && pupil[(size_t)item * item_stride + m] == 0.0);
     double wfe = 0.0;
     if (!masked) {
-      double c1 = 1.0, s1 = 0.0;
-      if (rr > 0.0) {
-        c1 = (origin_y ? y : x) / rr;
-        s1 = (origin_y ? x : y) / rr;
-      }
-      const double cr = c1 * co - s1 * so, sr = s1 * co + c1 * so;
-      const double xj = 1.0 - 2.0 * rho * rho;
-      double rho_pow = 1.0, cm = 1.0, sm = 0.0;
-      auto order = [&](int am, int k_end) __attribute__((always_inline)) {
-        double pkm1 = 0.0, pk = 1.0;
-        for (int k = 0; k <= k_end; ++k) {
-          if (k > 0) {
-            const double* abc = table + ((size_t)am * kdim + k) * 3;
-            const double pn = (abc[0] * xj + abc[1]) * pk - abc[2] * pkm1;
-            pkm1 = pk;
-            pk = pn;
-          }
-          const size_t ci = (size_t)am * kdim + k;
-          wfe += (rho_pow * pk) * (coef_c[ci] * cm + coef_s[ci] * sm);
-        }
-        rho_pow *= rho;
-        const double cn = cm * cr - sm * sr;
-        sm = sm * cr + cm * sr;
-        cm = cn;
-      };
-      if constexpr (NMAXC > 0) {  // same operations in the same order, loops unrolled
-#pragma unroll
-        for (int am = 0; am <= NMAXC; ++am) {
-          if (am > nmax) break;
-          const int kmax = (nmax - am) / 2;
-          double pkm1 = 0.0, pk = 1.0;
-#pragma unroll
-          for (int k = 0; k <= (NMAXC - am) / 2; ++k) {
-            if (k > kmax) break;
-            if (k > 0) {
-              const double* abc = table + ((size_t)am * kdim + k) * 3;
-              const double pn = (abc[0] * xj + abc[1]) * pk - abc[2] * pkm1;
-              pkm1 = pk;
-              pk = pn;
-            }
-            const size_t ci = (size_t)am * kdim + k;
-            wfe += (rho_pow * pk) * (coef_c[ci] * cm + coef_s[ci] * sm);
-          }
-          rho_pow *= rho;
-          const double cn = cm * cr - sm * sr;
-          sm = sm * cr + cm * sr;
-          cm = cn;
-        }
-      } else {
-        for (int am = 0; am <= nmax; ++am) order(am, (nmax - am) / 2);
-      }
+      wfe = zernike_wfe<NMAXC>(table, coef_c, coef_s, nmax, kdim, x, y, rr, rho, origin_y, co, so);
       const double turns = __dmul_rn(6.283185307179586, wfe);
       // (round 5) eight members at a time, their loads issued before the first store: the fields of different items never
       // alias, which the compiler cannot know -- one load -> sincos -> store chain per member was a 32-deep latency chain
@@ -1276,6 +1286,164 @@ __global__ void zernike_kernel(cx<T>* field, const double* table, const double* 
     }
     if (wfe_out && item == 0) wfe_out[(size_t)r * n + c] = masked ? __longlong_as_double(0x7ff8000000000000LL) : wfe;
   }
+}
+
+// ---- the first surface and the Zernike surface right behind it in one write of the field -------------------------
+// A lean sweep or Monte-Carlo batch opens with aperture -> stop -> Zernike, and nothing reads the field in between:
+// start_write_kernel stored the same masked, normalised constant for every item and zernike_kernel read one copy back and
+// stored all of them again.  Here the field is stored once, as what that pair leaves.
+//
+// What start_write_kernel stores at a pixel of weight w, read back the way zernike_kernel / norm2_partial_kernel read it
+template <typename T>
+__device__ __forceinline__ cx<double> start_value(double w, double v0re, double v0im, bool scaled, double s) {
+  double x = w == 1.0 ? v0re : (w == 0.0 ? 0.0 : (double)(T)__dmul_rn(v0re, w));
+  double y = w == 1.0 ? v0im : (w == 0.0 ? 0.0 : (double)(T)__dmul_rn(v0im, w));
+  if (scaled) { x = __dmul_rn(x, s); y = __dmul_rn(y, s); }
+  return {(double)(T)x, (double)(T)y};
+}
+
+// The groups are start_write_kernel's (same aperture record, stop flag and window: one evaluation of the weight per pixel);
+// a group's leader walks its sub-groups -- zernike_kernel's groups among the members, records that differ in the wavelength
+// only: one evaluation of the polynomials per pixel -- subs[3 q ...] = [item whose Zernike record describes the map, or -1:
+// no Zernike on these members; first member in `members`; number of members].  Per member the operations are those of the
+// two kernels: fl(fl(2 pi wfe) / lambda), sincos_fast, the unfused complex product.  Pixels outside the unit disk and the
+// padding keep what the start stores; outside the box (rows, cols: as in start_write_kernel) nothing is written.
+// (The name keeps "start_write_kernel" in it: a step of a sweep is recognised in a kernel trace by the kernel that writes the
+// start field.)
+template <typename T, int BR, int BC, int SHAPE, int NMAXC>
+__global__ void __launch_bounds__(kPwThreads) zernike_start_write_kernel(cx<T>* field, const double* params, int n, unsigned pitch, unsigned item_stride,
+                                           double vre, double vim, const double* norm2, const double* stop,
+                                           const double* rows, const double* cols, const double* grp_off,
+                                           const double* grp_len, const double* subs, const double* members,
+                                           const double* table, const double* zparams, int param_stride, int nmax, int kdim) {
+  const int item = blockIdx.y;
+  const int nsub = (int)grp_len[item];
+  if (nsub == 0) return;
+  const double* sub = subs + 3 * (int)grp_off[item];
+  const double* p = params + (size_t)item * AP_STRIDE;
+  ApertureEval<SHAPE> ap;
+  ap.init(p, p + AP_THETA);
+  const bool on = p[AP_ENABLE] != 0.0;
+  const bool scaled = stop[item] != 0.0;
+  const double s = scaled ? 1.0 / sqrt(norm2[item]) : 1.0;
+  const double v0re = (double)(T)vre, v0im = (double)(T)vim;
+  size_t total = item_stride, first = 0;
+  if (rows) {
+    first = (size_t)((int)rows[2 * item] / BR) * pitch;
+    total = (size_t)(((int)rows[2 * item + 1] + BR - 1) / BR) * pitch;
+    if (total > item_stride) total = item_stride;
+  }
+  unsigned in_lo = 0, span = pitch;
+  if (cols) {
+    in_lo = (unsigned)((int)cols[2 * item] / BC) * (BR * BC);
+    unsigned h = (unsigned)(((int)cols[2 * item + 1] + BC - 1) / BC) * (BR * BC);
+    if (h > (unsigned)n * BR) h = (unsigned)n * BR;
+    span = h > in_lo ? h - in_lo : 0;
+  }
+  const size_t nbr = (total - first) / pitch;
+  const size_t work = cols ? nbr * span : total - first;
+  for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < work; j += (size_t)gridDim.x * blockDim.x) {
+    const size_t m = cols ? first + (j / span) * pitch + in_lo + (j % span) : first + j;
+    int r, c;
+    const bool pixel = layout_unmap<BR, BC>(m, n, pitch, r, c);
+    cx<double> u = {0.0, 0.0};
+    if (pixel) u = start_value<T>(on ? ap.weight(ap.mask(r, c)) : 1.0, v0re, v0im, scaled, s);
+    for (int q = 0; q < nsub; ++q) {
+      const int zl = (int)sub[3 * q], glen = (int)sub[3 * q + 2];
+      const double* mem = members + (int)sub[3 * q + 1];
+      bool masked = true;
+      double turns = 0.0;
+      if (pixel && zl >= 0) {
+        const double* zp = zparams + (size_t)zl * param_stride;
+        const double x = (double)(c - n / 2) * zp[ZP_DX], y = (double)(r - n / 2) * zp[ZP_DY];
+        const double rr = sqrt(__dadd_rn(__dmul_rn(x, x), __dmul_rn(y, y)));
+        const double rho = rr / zp[ZP_RADIUS];
+        masked = rho > 1.0;
+        if (!masked) {
+          const double* coef_c = zp + ZP_HEAD;
+          const double wfe = zernike_wfe<NMAXC>(table, coef_c, coef_c + (size_t)(nmax + 1) * kdim, nmax, kdim, x, y, rr, rho,
+                                                zp[ZP_ORIGIN_Y] != 0.0, zp[ZP_COS_OFF], zp[ZP_SIN_OFF]);
+          turns = __dmul_rn(6.283185307179586, wfe);
+        }
+      }
+      if (masked) {
+        for (int g = 0; g < glen; ++g) field[(size_t)(int)mem[g] * item_stride + m] = {(T)u.x, (T)u.y};
+        continue;
+      }
+      // (the members' wavelengths -- uniform loads -- are fetched eight at a time ahead of the stores, like zernike_kernel's
+      // kZernikeGroup: the compiler cannot know that the field never aliases the records)
+      constexpr int kGroup = 8;
+      int g = 0;
+      for (; g + kGroup <= glen; g += kGroup) {
+        int it[kGroup];
+        double iw[kGroup];
+#pragma unroll
+        for (int k = 0; k < kGroup; ++k) {
+          it[k] = (int)mem[g + k];
+          iw[k] = zparams[(size_t)it[k] * param_stride + ZP_INV_WL];
+        }
+#pragma unroll
+        for (int k = 0; k < kGroup; ++k) {
+          double sn, cs;
+          sincos_fast(__dmul_rn(turns, iw[k]), &sn, &cs);
+          field[(size_t)it[k] * item_stride + m] = {(T)__dsub_rn(__dmul_rn(u.x, cs), __dmul_rn(u.y, sn)),
+                                                    (T)__dadd_rn(__dmul_rn(u.x, sn), __dmul_rn(u.y, cs))};
+        }
+      }
+      for (; g < glen; ++g) {
+        const int it = (int)mem[g];
+        double sn, cs;
+        sincos_fast(__dmul_rn(turns, zparams[(size_t)it * param_stride + ZP_INV_WL]), &sn, &cs);
+        field[(size_t)it * item_stride + m] = {(T)__dsub_rn(__dmul_rn(u.x, cs), __dmul_rn(u.y, sn)),
+                                                (T)__dadd_rn(__dmul_rn(u.x, sn), __dmul_rn(u.y, cs))};
+      }
+    }
+  }
+}
+
+// The partial sums norm2_partial_kernel would form over the box of the start field (same grid, same walk, same order of
+// additions), from the weights instead of from memory: the power of a saved first surface whose field is never stored on its
+// own (zernike_start_write_kernel).  ``lead``: 0 = this item's sum is another item's (norm2_final_kernel: source).
+template <typename T, int BR, int BC, int SHAPE>
+__global__ void start_norm2_partial_kernel(double* partial, const double* params, int n, unsigned pitch, unsigned item_stride,
+                                           double vre, double vim, const double* norm2, const double* stop, const double* lead,
+                                           const double* rows, const double* cols) {
+  const int item = blockIdx.y;
+  if (lead && lead[item] == 0.0) return;
+  __shared__ double sh[kPwThreads / 64];
+  const double* p = params + (size_t)item * AP_STRIDE;
+  ApertureEval<SHAPE> ap;
+  ap.init(p, p + AP_THETA);
+  const bool on = p[AP_ENABLE] != 0.0;
+  const bool scaled = stop[item] != 0.0;
+  const double s = scaled ? 1.0 / sqrt(norm2[item]) : 1.0;
+  const double v0re = (double)(T)vre, v0im = (double)(T)vim;
+  size_t total = item_stride, first = 0;
+  if (rows) {
+    first = (size_t)((int)rows[2 * item] / BR) * pitch;
+    total = (size_t)(((int)rows[2 * item + 1] + BR - 1) / BR) * pitch;
+    if (total > item_stride) total = item_stride;
+  }
+  double acc = 0.0;
+  const size_t step = (size_t)gridDim.x * blockDim.x;
+  size_t m = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (m < first) m += (first - m + step - 1) / step * step;
+  unsigned in_lo = 0, in_hi = (unsigned)n * BR;
+  if (cols) {
+    in_lo = (unsigned)((int)cols[2 * item] / BC) * (BR * BC);
+    const unsigned h = (unsigned)(((int)cols[2 * item + 1] + BC - 1) / BC) * (BR * BC);
+    in_hi = h < in_hi ? h : in_hi;
+  }
+  for (; m < total; m += step) {
+    const unsigned off = (unsigned)(m % pitch);
+    if (off >= in_hi || off < in_lo) continue;
+    int r, c;
+    if (!layout_unmap<BR, BC>(m, n, pitch, r, c)) continue;  // (never inside [in_lo, in_hi): the padding lies behind n BR)
+    const cx<double> u = start_value<T>(on ? ap.weight(ap.mask(r, c)) : 1.0, v0re, v0im, scaled, s);
+    acc += __dadd_rn(__dmul_rn(u.x, u.x), __dmul_rn(u.y, u.y));
+  }
+  const double sum = block_sum(acc, sh);
+  if (threadIdx.x == 0) partial[(size_t)item * gridDim.x + blockIdx.x] = sum;
 }
 
 // ---- PolyOrthoNorm: Gram sums of the Zernike polynomials over the pupil -----------------------

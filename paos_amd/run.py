@@ -65,6 +65,10 @@ START_BOX = _os.environ.get("PAOS_START_BOX", "1") != "0"
 # wavelength touches them: a Zernike surface right behind the start reads one field per group of copies (paos_zernike_like,
 # round 5).  PAOS_TWIN_FIELDS=0: every item's field is read.
 TWIN_FIELDS = _os.environ.get("PAOS_TWIN_FIELDS", "1") != "0"
+# ... and where that Zernike surface follows the start with nothing in between, a lean walk writes the first field once, with
+# the phase already on it (paos_start_zernike_box) -- instead of the masked constant, read back and rewritten by the Zernike
+# kernel.  PAOS_FUSE_START=0: the two calls.
+FUSE_START = _os.environ.get("PAOS_FUSE_START", "1") != "0"
 _MASK_RUN = 192  # kMaskW of csrc/frugal_pass.h
 
 
@@ -713,17 +717,14 @@ def _launch_apertures(dev, plans):
             dev.aperture(code, blocks)
 
 
-def _launch_zernike(dev, plans, want_wfe=False, same_as=None):
-    if isinstance(plans, _Plans) and not plans.summary()[1]:
-        return None
+def _zernike_tables(plans):
+    """(zs, nmax, kdim, table, build) of a surface's Zernike plans: ``build(coeffs)`` forms the [batch][stride] parameter
+    blocks of paos_zernike from per-item coefficient vectors."""
     zs = [p["zernike"] for p in plans]
-    if not any(z is not None for z in zs):
-        return None
     nmax = max(int(z["n"].max()) for z in zs if z is not None)
     kdim = nmax // 2 + 1
     stride = _lib.ZERNIKE_HEAD + 2 * (nmax + 1) * kdim
     table = jacobi_recurrence(nmax)
-    ortho = [z is not None and z["pupil"] is not None for z in zs]
 
     def build(coeffs):
         blocks = np.zeros((len(plans), stride), dtype=np.float64)
@@ -745,6 +746,16 @@ def _launch_zernike(dev, plans, want_wfe=False, same_as=None):
             row[1], row[2], row[3], row[7] = z["dx"], z["dy"], z["radius"], 1.0 / z["wl"]
         return blocks
 
+    return zs, nmax, kdim, table, build
+
+
+def _launch_zernike(dev, plans, want_wfe=False, same_as=None):
+    if isinstance(plans, _Plans) and not plans.summary()[1]:
+        return None
+    if not any(p["zernike"] is not None for p in plans):
+        return None
+    zs, nmax, kdim, table, build = _zernike_tables(plans)
+    ortho = [z is not None and z["pupil"] is not None for z in zs]
     coeffs = [z["Z"] if z is not None else None for z in zs]
     if not any(ortho):
         if same_as is not None:  # (the items named hold copies of one field: the surface right behind the start)
@@ -851,7 +862,7 @@ def _queue_steps(comp, lens, stw, ptp, wts, inv_stw, inv_wts):
     comp.wts(wts, inv_wts != 0.0)
 
 
-def _start_field(dev, plans, value, write_rows=None, write_cols=None):
+def _start_field(dev, plans, value, write_rows=None, write_cols=None, defer=None):
     """The wavefront is still the constant ``value`` (wfo.py:118).  When every item opens with a
     stand-alone aperture of one shape, ones -> aperture -> [make_stop] is a single write of the
     field (paos_start); otherwise fill and let the surface run as usual.  Returns False, or -- when the
@@ -872,7 +883,9 @@ def _start_field(dev, plans, value, write_rows=None, write_cols=None):
         code = _lib.SHAPE_ELLIPSE if isinstance(aps[0][0], EllipticalAperture) else _lib.SHAPE_RECT
         blocks = [a[0].block(obscuration=a[1]) for a in aps]
     stops = [1.0 if p["stop"] else 0.0 for p in plans]
-    if write_rows is None:
+    if defer is not None:  # (the caller launches later: _walk, a Zernike surface may ride on the write)
+        defer.update(value=value, code=code, blocks=blocks, stops=stops, rows=write_rows, cols=write_cols)
+    elif write_rows is None:
         dev.start(value, code, blocks, stops)
     elif write_cols is None:
         dev.start(value, code, blocks, stops, write_rows=write_rows)
@@ -901,6 +914,9 @@ class _WalkState:
         # set once a pass program has stored the PSF for good (nothing but inert surfaces follows): the saved surfaces
         # still to come report this ticket's power, and the PSF is already where keep_psf wants it
         self.final_ticket = None
+        # a dict while the start field of the walk has not been launched yet (it waits for the surface behind it, whose Zernike
+        # phase may ride on the write): ``on_saved`` leaves the reduction that will hold the start field's power under "power"
+        self.deferred_start = None
 
 
 def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_at=None, power_state=None):
@@ -928,6 +944,7 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
     stale = [False]  # rows outside ``live`` hold old data that stands for zeros (lean start)
     stale_cols = [None]  # ... and, while ``stale``, so do the columns outside these [lo, hi) per item (paos_start_box)
     dead = [False]   # the field has been given up for its PSF (lean end): nothing may run on it any more
+    fused_start = [0]  # 1: the first field was written with the Zernike phase of the next surface on it (launch_start)
 
     prog_power = [None]  # ticket of the power of the field a program has just stored (flush(final_power=True))
     factor_cols_t, factor_cols_s = [], []  # [surface][item] ABCD factors met so far (run.py:215-219)
@@ -952,6 +969,41 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
         (the PSF and its power came out NaN on the model device)."""
         if psf_at is not None and key == psf_at and lean.psf_ticket is None:
             settle()
+
+    def zernike_rides(d, plans, items):
+        """May this surface's Zernike phase be applied while the deferred start field ``d`` is written?  Every item carries
+        an ordinary Zernike expansion whose unit disk lies inside the start's box, nothing else of the surface comes in
+        front of it (aperture, stop), nothing is queued, and nobody wants the wfe map."""
+        any_stop, any_zern, _, any_ap = plans.summary()
+        if not any_zern or any_stop or any_ap or comp.pending() or (len(plans) == 1 and bool(items[0]["save"])):
+            return False
+        for p, rows, cols in zip(plans, d["rows"], d["cols"]):
+            z = p["zernike"]
+            if z is None or z["pupil"] is not None or not (z["radius"] > 0 and z["dx"] > 0 and z["dy"] > 0):
+                return False
+            hx, hy = z["radius"] / z["dx"], z["radius"] / z["dy"]
+            if not (cols[0] <= dev.n // 2 - hx and dev.n // 2 + hx <= cols[1] - 1 and
+                    rows[0] <= dev.n // 2 - hy and dev.n // 2 + hy <= rows[1] - 1):
+                return False
+        return True
+
+    def launch_start(plans=None, items=None):
+        """Launch the deferred start field -- with the Zernike phase of ``plans`` on it when that is possible (True: the
+        surface's Zernike is done), else as the walk would have launched it at the first surface."""
+        d, lean.deferred_start = lean.deferred_start, None
+        power = d.get("power")
+        if plans is not None and zernike_rides(d, plans, items):
+            zs, nmax, kdim, table, build = _zernike_tables(plans)
+            slot = dev.start_zernike(d["value"], d["code"], d["blocks"], d["stops"], d["rows"], d["cols"], nmax, kdim, table,
+                                     build([z["Z"] for z in zs]), power=power is not None)
+            if power is not None:
+                power.slot = int(slot)
+            fused_start[0] += 1
+            return True
+        dev.start(d["value"], d["code"], d["blocks"], d["stops"], write_rows=d["rows"], write_cols=d["cols"])
+        if power is not None:
+            power.slot = int(dev.norm2_enqueue(d["rows"], same_as=d["like"], live_cols=d["cols"]))
+        return False
 
     def flush(final_intensity=False, final_power=False):
         if dead[0]:
@@ -1028,6 +1080,9 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
                     p["ABCDt"] = ABCDProduct(tuple(col[i] for col in factor_cols_t))
                     p["ABCDs"] = ABCDProduct(tuple(col[i] for col in factor_cols_s))
 
+        zernike_done = False
+        if lean is not None and lean.deferred_start is not None:
+            zernike_done = launch_start(plans, items)
         if fresh is not None and not saved and all(_inert(it) for it in items):
             # (coordinate breaks in front of the first mirror: the field is still the constant it will be filled with;
             # the first surface that does something -- usually aperture + stop -- then writes it in one go, _start_field)
@@ -1043,15 +1098,25 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
                     rows0 = trial
                     if START_BOX:  # ... and whole columns: the field is written inside the aperture's box only
                         cols0 = _live_cols_of(plans, dev.n)
-            same_as = _start_field(dev, plans, value, write_rows=rows0, write_cols=cols0)
+            # still copies of each other unless this surface puts a wavefront error on them
+            untouched = not any(p["zernike"] is not None or p["phase_map"] is not None for p in plans)
+            # A box start with nothing else on its surface and a surface behind it waits for that surface: if it is a Zernike
+            # surface, the field is written once with the phase on it (launch_start).  Nothing reads the field meanwhile: a
+            # lean walk's saved surface wants its power only, which the deferred launch brings along.
+            defer = None
+            if (FUSE_START and cols0 is not None and untouched and hasattr(dev, "start_zernike") and pos + 1 < len(order)
+                    and not (psf_at is not None and key == psf_at) and all(_identity_gates(it) for it in items)):
+                defer = {}
+            same_as = _start_field(dev, plans, value, write_rows=rows0, write_cols=cols0, defer=defer)
             if same_as is not None:
                 _live_rows_after(plans, live, dev.n)
                 stale[0] = rows0 is not None
                 stale_cols[0] = cols0 if stale[0] else None
                 want_wfe = len(plans) == 1 and bool(items[0]["save"])
-                # still copies of each other unless this surface puts a wavefront error on them
-                untouched = not any(p["zernike"] is not None or p["phase_map"] is not None for p in plans)
                 copies = same_as if len(set(same_as)) < len(same_as) else None
+                if defer is not None:
+                    defer["like"] = copies
+                    lean.deferred_start = defer
                 wfe = _launch_zernike(dev, plans, want_wfe=want_wfe, same_as=copies if TWIN_FIELDS else None)
                 wfe = _launch_phase_maps(dev, plans, wfe)
                 if saved:
@@ -1064,6 +1129,8 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
                     if lean is not None:
                         lean.same_as, lean.cols = None, None
                 _queue_steps(comp, lens, stw, ptp, wts, inv_stw, inv_wts)
+                if lean is not None and lean.deferred_start is not None and comp.pending():
+                    launch_start()  # (the surface has queued something after all: the field must exist first)
                 # (round 5) ... and they stay copies until something wavelength-dependent is applied or queued: a Zernike surface
                 # right behind the start (SYN20's S02) reads one field per group of them (paos_zernike_like)
                 twins = copies if (TWIN_FIELDS and untouched and not comp.pending()) else None
@@ -1133,7 +1200,7 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
         want_wfe = len(plans) == 1 and bool(items[0]["save"])
         if twins is not None and (comp.pending() or fuse_ap or any_ap or any_stop):
             twins = None  # (something has been applied to the fields, or waits to be)
-        wfe = _launch_zernike(dev, plans, want_wfe=want_wfe, same_as=twins)
+        wfe = None if zernike_done else _launch_zernike(dev, plans, want_wfe=want_wfe, same_as=twins)
         if any_zern or any_map:
             twins = None
         wfe = _launch_phase_maps(dev, plans, wfe)
@@ -1153,12 +1220,15 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
     if power_state is not None and power_state["ticket"] is not None and not power_state.get("used"):
         dev.norm2_release(power_state["ticket"])  # (taken for a stop on the last surface, which nobody saved)
         power_state["ticket"] = None
+    if lean is not None and lean.deferred_start is not None:
+        launch_start()
     if fresh is not None:  # an empty chain still yields the initial wavefront
         dev.fill(fresh)
     npass += flush()
     settle()
     if stats is not None:
         stats["fused_passes"] = npass
+        stats["fused_start"] = fused_start[0]
 
 
 # One idle single-wavefront context per (grid, precision, device) is kept between run() calls:
@@ -1586,6 +1656,10 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
                     dev.norm2_release(power_state["ticket"])
                     power_state["used"] = True
                 tickets.append((reduction_of(dev.psf_keep_power()), pending, None))
+            elif lean is not None and lean.deferred_start is not None:
+                # the start field is launched at the next surface (_walk: launch_start), which enqueues this sum and names its slot
+                red = lean.deferred_start["power"] = _Reduction(dev, -1)
+                tickets.append((red, pending, None))
             else:
                 like = lean.same_as if lean is not None else None
                 cols = lean.cols if lean is not None else None
