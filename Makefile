@@ -11,13 +11,13 @@ all: $(LIB)
 
 # The library is one source file compiled as six translation units (make -j6: ~1.5 min instead of 4):
 # part 0 = everything but the frugal pass-kernel families, parts 1..5 = one (type, N) family each.
-DEPS = $(CSRC)/paos_hip.hip $(CSRC)/fft_core.h $(CSRC)/fft_kernels.h $(CSRC)/frugal_pass.h $(CSRC)/pointwise.h $(CSRC)/focus_pass.h $(CSRC)/otf_pass.h include/paos_hip.h
+DEPS = $(CSRC)/paos_hip.hip $(CSRC)/fft_core.h $(CSRC)/fft_kernels.h $(CSRC)/frugal_pass.h $(CSRC)/pointwise.h $(CSRC)/focus_pass.h $(CSRC)/otf_pass.h $(CSRC)/zoom_pass.h include/paos_hip.h
 PARTS = 0 1 2 3 4 5
 OBJS = $(foreach k,$(PARTS),build/obj/part$(k).o) build/obj/comm.o build/obj/plan.o build/obj/srchash.o
 
 # What the library was built from: sha256 over its sources in this order (paos_source_hash(); __graft_entry__.build() compares
 # it with the tree and rebuilds on a mismatch -- a prebuilt .so that travelled with the tree cannot silently be stale)
-HASHED = $(CSRC)/paos_hip.hip $(CSRC)/fft_core.h $(CSRC)/fft_kernels.h $(CSRC)/frugal_pass.h $(CSRC)/pointwise.h $(CSRC)/focus_pass.h $(CSRC)/otf_pass.h \
+HASHED = $(CSRC)/paos_hip.hip $(CSRC)/fft_core.h $(CSRC)/fft_kernels.h $(CSRC)/frugal_pass.h $(CSRC)/pointwise.h $(CSRC)/focus_pass.h $(CSRC)/otf_pass.h $(CSRC)/zoom_pass.h \
          $(CSRC)/paos_comm.cpp $(CSRC)/paos_plan.cpp include/paos_hip.h include/paos_comm.h include/paos_plan.h
 build/obj/srchash.o: $(HASHED)
 	mkdir -p build/obj

@@ -335,6 +335,46 @@ int paos_otf_fetch(paos_ctx* ctx, int item, int what, void* host_out);
  * the fetched array by the mirror symmetry) -- bit for bit the values paos_otf_fetch hands out.  Synchronises.
  * PAOS_EINVAL as for paos_otf_fetch. */
 int paos_otf_cuts(paos_ctx* ctx, double* host_out);
+/* ---- zoomed PSF windows: the field interpolated exactly onto a finer grid (README.md, "Zoomed PSFs") ------------------- */
+/* No reference counterpart.  With u[k][j] the N x N field of item i (rows k along y), its band-limited interpolant with the
+ * Nyquist term split evenly is u(y, x) = sum_k sum_j u[k][j] d(y - k) d(x - j), d(t) = sin(pi t) / (N tan(pi t / N)),
+ * d = 1 for t = 0 (mod N), period N.  A window has M fine samples per side at 1 / s of the grid pitch about a centre
+ * (cx_i, cy_i) in pixel-index units (pixel N/2 is the grid centre): fine column q lies at x_q = cx + (q - M/2) / s, row p
+ * likewise along y, and psf_zoom[p][q] = |u(y_p, x_q)|^2 -- samples of the same intensity as the PSF, not divided by s^2.
+ * The interpolant is periodic: a window that runs over the grid edge wraps.  The window is Wy u Wx^T with REAL weights,
+ * two dense contractions on the fp64 matrix instruction (csrc/zoom_pass.h), in fp64 for either kind of context (an fp32
+ * context's complex64 field is widened on load); the results are doubles.
+ *
+ * paos_zoom_weights: the weights of one axis for the fractional part `frac` in [0, 1) of a centre, host only, evaluated in
+ * long double and rounded to double once.  Per axis c = ci + frac with ci = floor(c); q - M/2 = s a + b with 0 <= b < s
+ * (floor division); the phase offset is phi_b = frac + b / s, minus 1 with carry[b] = 1 when it reaches 1 (the carry goes
+ * into a); the sample's weight on grid pixel j is w[b][m mod n] with m = ci + a + carry[b] - j wrapped to [-n/2, n/2):
+ *   w[b][m] = [m == 0] when phi_b == 0, else (-1)^m sin(pi phi_b) / (n tan(pi (m + phi_b) / n)).
+ * So column 0 of a row is m = 0 and columns n/2 .. n-1 are m = -n/2 .. -1, and a fine sample that falls on a grid pixel
+ * has a unit-vector row: it is a copy of the field's sample, bit for bit.  w[s][n], carry[s].  PAOS_EINVAL for n odd or
+ * outside 2 .. 2^20, s outside 1 .. 64, frac outside [0, 1) and null pointers. */
+int paos_zoom_weights(int n, int s, double frac, double* w, int* carry);
+enum { PAOS_ZOOM_PSF = 0, PAOS_ZOOM_FIELD = 1 };
+/* The m x m windows of EVERY item of the field as it is now, oversampling s, about centres[item][2] = (cx, cy) (NULL: the
+ * grid centre N/2, N/2 for every item): |u|^2 into a buffer [batch][m][m] of doubles and, with want_field, u itself into a
+ * second one of complex128.  Two launches (columns contracted into a scratch of 16 batch m N bytes, then rows), no
+ * atomics, a fixed summation order: a repeated call gives the same bits, and an item's window does not depend on the batch
+ * size or on its place in the batch.  The scratch and the windows are allocated on first use, again when m changes, and
+ * freed by paos_ctx_destroy; one phase table (s x N doubles) per distinct fractional part of a centre is built on the host,
+ * uploaded once and reused by later calls with the same s (the context keeps up to 256 tables; when a call's new ones
+ * do not fit beside them, the kept ones are dropped first -- never in the middle of a call).  Enqueues only (a call that has to build a table copies it
+ * before it returns; one that has to move or drop tables, or to reallocate, waits for the windows enqueued before).  A
+ * pending deferred stop factor (paos_stop_defer_last_power) is applied first, as by every reader of the field; the field
+ * is only read and must be the complete field, as for paos_focus_begin.  PAOS_EINVAL (the context stays usable): m not a
+ * multiple of 16 or outside 16 .. 1024, m > s N, s outside 1 .. 64, a centre that is not finite or outside [0, N), more
+ * than 256 distinct fractional parts among the centres of one call.
+ * PAOS_EHIP when the scratch cannot be allocated (the context stays usable; no window is available then). */
+int paos_zoom_compute(paos_ctx* ctx, int m, int s, const double* centres, int want_field);
+/* One item's window to the host, row-major [p][q]: PAOS_ZOOM_PSF m x m doubles, PAOS_ZOOM_FIELD m x m complex128.
+ * Synchronises.  The buffers are a snapshot of the field at the time of paos_zoom_compute: nothing tracks whether the
+ * field has changed since.  PAOS_EINVAL before any paos_zoom_compute, for a bad item or `what`, a null buffer, and for
+ * PAOS_ZOOM_FIELD when the last paos_zoom_compute was not asked for it. */
+int paos_zoom_fetch(paos_ctx* ctx, int item, int what, void* host_out);
 /* A whole stretch of the propagation loop (run.py:193-207 over consecutive surfaces) as a
  * program of passes: lens phases (wfo.py:359-366), the checkerboard signs that replace
  * fftshift/ifftshift, the quadratic phases and ortho scalings of ptp / stw / wts

@@ -17,6 +17,9 @@ transform, each with its power, arrays, metrics and detector image (README.md, "
 
 ``run_batch(..., outputs=("mtf", "otf"), mtf_cuts=True)`` hands out the transfer functions of the last surface's PSFs,
 computed on the GPU by a packed real-input 2-D transform (README.md, "Transfer functions").
+
+``run_batch(..., psf_zoom=PsfWindow(size, oversample))`` adds a window of the last surface's PSF on a finer grid: the
+exact band-limited interpolant of the field, two fp64 matrix-instruction contractions (README.md, "Zoomed PSFs").
 """
 from .abcd import ABCD
 from .coordinate_break import coordinate_break
@@ -25,7 +28,7 @@ from .zernike import Zernike
 
 from .raytrace import raytrace
 
-__all__ = ["ABCD", "Detector", "WFO", "Zernike", "coordinate_break", "parse_config", "raytrace", "run_batch",
+__all__ = ["ABCD", "Detector", "PsfWindow", "WFO", "Zernike", "coordinate_break", "parse_config", "raytrace", "run_batch",
            "run_broadband", "run_sharded"]
 __version__ = "0.1.0"
 
@@ -42,6 +45,8 @@ def __getattr__(name):
         return importlib.import_module(".run", __name__).run_batch
     if name in ("Detector", "run_broadband"):
         return getattr(importlib.import_module(".detector", __name__), name)
+    if name == "PsfWindow":
+        return importlib.import_module(".zoom", __name__).PsfWindow
     if name == "run_sharded":
         return importlib.import_module(".dist", __name__).run_sharded
     raise AttributeError(name)

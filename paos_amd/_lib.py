@@ -25,6 +25,8 @@ PWF_MUL2PI = 1
 PWF_X_ONLY, PWF_Y_ONLY = 2, 4  # PW_SIGN: (-1)^column / (-1)^row instead of the checkerboard (-1)^(row + column)
 MAX_PW = 6
 OTF_MTF, OTF_COMPLEX = 0, 1  # paos_otf_fetch: |OTF| as doubles / the complex OTF
+ZOOM_PSF, ZOOM_FIELD = 0, 1  # paos_zoom_fetch: |u|^2 of the window as doubles / the complex window
+ZOOM_MAX_TABLES = 256  # phase tables a context keeps; the most distinct fractional parts among the centres of one call
 NORM_SLOTS = 64  # PAOS_NORM_SLOTS: tickets of paos_norm2_enqueue that may be outstanding
 
 
@@ -92,6 +94,9 @@ SYMBOLS = {
     "paos_otf_compute": (ctypes.c_int, [_c_ctx]),
     "paos_otf_fetch": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "paos_otf_cuts": (ctypes.c_int, [_c_ctx, _dbl_p]),
+    "paos_zoom_weights": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_double, _dbl_p, ctypes.POINTER(ctypes.c_int)]),
+    "paos_zoom_compute": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, _dbl_p, ctypes.c_int]),
+    "paos_zoom_fetch": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "paos_run_passes": (ctypes.c_int, [_c_ctx, ctypes.POINTER(Pass), ctypes.c_int, _dbl_p, ctypes.c_int]),
     "paos_copy_yardstick": (ctypes.c_int, [_c_ctx, ctypes.c_int, _dbl_p, _dbl_p]),
     "paos_record_set_stats": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
@@ -171,6 +176,31 @@ def as_blocks(blocks, batch, stride):
     if arr.shape != (batch, stride):
         raise ValueError(f"expected parameter blocks of shape {(batch, stride)}, got {arr.shape}")
     return arr
+
+
+def zoom_check(size, oversample, n):
+    """The rules of paos_zoom_compute for a window size and an oversampling on an n x n grid (``ValueError``)."""
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or size < 16 or size > 1024 or size % 16:
+        raise ValueError(f"a zoomed window's size must be an integer multiple of 16 in 16 .. 1024, got {size!r}")
+    if isinstance(oversample, bool) or not isinstance(oversample, (int, np.integer)) or not 1 <= oversample <= 64:
+        raise ValueError(f"a zoomed window's oversampling must be an integer in 1 .. 64, got {oversample!r}")
+    if size > oversample * n:
+        raise ValueError(f"a zoomed window of {size} samples at oversampling {oversample} is wider than the {n}-pixel grid")
+
+
+def zoom_centres(centres, batch, n):
+    """``centres`` as the (batch, 2) float64 array paos_zoom_compute takes: finite pixel positions in [0, n)."""
+    try:
+        ctr = np.ascontiguousarray(centres, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("zoomed-window centres must be a (batch, 2) array of pixel positions (x, y)") from None
+    if ctr.shape != (batch, 2):
+        raise ValueError(f"zoomed-window centres must have shape ({batch}, 2), got {ctr.shape}")
+    if not np.all(np.isfinite(ctr)) or np.any(ctr < 0.0) or np.any(ctr >= n):
+        raise ValueError(f"zoomed-window centres must be finite and lie in [0, {n})")
+    if np.unique(ctr - np.floor(ctr)).size > ZOOM_MAX_TABLES:
+        raise ValueError(f"the centres of one call may have at most {ZOOM_MAX_TABLES} distinct fractional parts")
+    return ctr
 
 
 # ---- page-locked result arrays ---------------------------------------------------------------
@@ -632,6 +662,29 @@ class DeviceFields:
         frequency to Nyquist -- one launch and one small copy for the whole batch.  Synchronises."""
         out = np.empty((self.batch, 2, self.n // 2 + 1), dtype=np.float64)
         self._check(self._lib.paos_otf_cuts(self._ctx, _dptr(out)), "paos_otf_cuts")
+        return out
+
+    # -- zoomed windows (paos_zoom_*: README.md, "Zoomed PSFs") ------------------------------------------------------
+    def zoom_compute(self, size, oversample, centres=None, field=False):
+        """The ``size`` x ``size`` windows of every item's field at ``1 / oversample`` of the grid pitch, about
+        ``centres`` ((batch, 2) pixel positions ``(x, y)``; None: the grid centre): the exact band-limited interpolant,
+        two fp64 matrix-instruction contractions.  ``field``: keep the complex windows too.  Enqueued only."""
+        ctr = None if centres is None else zoom_centres(centres, self.batch, self.n)
+        zoom_check(size, oversample, self.n)
+        self._check(self._lib.paos_zoom_compute(self._ctx, int(size), int(oversample), _dptr(ctr) if ctr is not None else None,
+                                                1 if field else 0), "paos_zoom_compute")
+        self._zoom_size = int(size)  # (what zoom_fetch sizes its arrays by: the last call that succeeded)
+
+    def zoom_fetch(self, item=0, what="psf"):
+        """One item's window of the last ``zoom_compute``: ``"psf"`` -- (size, size) float64 ``|u|^2``; ``"field"`` --
+        (size, size) complex128 (needs ``zoom_compute(field=True)``).  A snapshot of the field as it was then.
+        Synchronises."""
+        if what not in ("psf", "field"):
+            raise ValueError(f"what must be 'psf' or 'field', got {what!r}")
+        m = getattr(self, "_zoom_size", 1)
+        out = np.empty((m, m), dtype=np.float64 if what == "psf" else np.complex128)
+        self._check(self._lib.paos_zoom_fetch(self._ctx, int(item), ZOOM_PSF if what == "psf" else ZOOM_FIELD,
+                                              out.ctypes.data_as(ctypes.c_void_p)), "paos_zoom_fetch")
         return out
 
     def copy_yardstick(self, reps=10):

@@ -116,7 +116,7 @@ def _unpack_results(flat):
 
 def run_sharded(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, batch=8,
                 precision="fp64", device=None, outputs=(), metrics_radii_px=None, gather=True,
-                make_device=None, comm=None):
+                make_device=None, comm=None, psf_zoom=None):
     """The reference's fan-out over wavelengths / Monte-Carlo draws (pipeline.py:139-150,
     joblib workers on one host) on N GPUs: call from every rank of ``comm`` (a ``paos_amd.comm.Comm``;
     None = single process).  Rank 0 supplies ``wavelengths`` and ``opt_chains`` (other ranks may pass
@@ -138,6 +138,8 @@ def run_sharded(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, 
 
     if {"mtf", "otf"} & set(outputs):  # (README.md, "Transfer functions": run_batch only)
         raise ValueError("run_sharded does not hand out transfer functions ('mtf' / 'otf'): use run_batch")
+    if psf_zoom is not None:  # (README.md, "Zoomed PSFs": run_batch only)
+        raise ValueError("run_sharded does not hand out zoomed PSF windows (psf_zoom): use run_batch")
     rank = comm.rank if comm is not None else 0
     world = comm.size if comm is not None else 1
     if rank == 0:

@@ -1379,11 +1379,11 @@ class _OtfRequest:
                 rec["freq_x"], rec["freq_y"] = m / (dev.n * dxs[i]), m / (dev.n * dys[i])
 
 
-def _focus_stack(dev, focus, outputs, what, metrics_radii_px, power, detector, placed, otf=None):
+def _focus_stack(dev, focus, outputs, what, metrics_radii_px, power, detector, placed, otf=None, zoom=None):
     """The planes of ``focus`` from the field ``dev`` holds behind the walk: [item][plane] dicts, planes in the caller's
     order.  The nominal plane (dz = 0) is read first, from the untouched field; then one ``focus_begin`` and one
     ``focus_plane`` per other plane.  ``otf`` (an ``_OtfRequest``): every plane's PSF is kept and its transfer functions
-    are attached to the plane's dict."""
+    are attached to the plane's dict.  ``zoom`` (a ``PsfWindow``): every plane's dict gets the plane's zoomed window."""
     beams, nb = focus.beams, dev.batch
     state = beams.state
     z0 = state[:, beams.Z].copy()
@@ -1420,6 +1420,8 @@ def _focus_stack(dev, focus, outputs, what, metrics_radii_px, power, detector, p
         if ticket is not None:
             for rec, p in zip(recs, dev.norm2_fetch(ticket)):
                 rec["power"] = float(p)
+        if zoom is not None:  # (paos_focus_plane leaves the plane in the field)
+            zoom.attach(dev, recs, dxs, dys)
         for i, rec in enumerate(recs):
             stacks[i][k] = rec
 
@@ -1445,7 +1447,7 @@ def _focus_stack(dev, focus, outputs, what, metrics_radii_px, power, detector, p
 def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, precision="fp64",
               device=0, outputs=("psf",), dev=None, sync=True, stats=None, metrics_radii_px=None,
               keep_psf=False, power=True, detector=None, detector_weights=None, detector_origin=None, focus_planes=None,
-              mtf_cuts=False):
+              mtf_cuts=False, psf_zoom=None):
     """Propagate ``B = len(opt_chains)`` wavefronts together on one GPU.
 
     ``wavelengths[i]`` / ``opt_chains[i]`` describe wavefront ``i`` (chains must
@@ -1512,6 +1514,18 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     ``focus_planes`` every plane's dict gets the same keys (through-focus MTF); the ``dz == 0.0`` plane's arrays equal the
     nominal record's bit for bit.  They synchronise: with ``sync=False`` any of the three is a ``ValueError``, as is a last
     surface that is not saved -- before anything is launched.
+
+    ``psf_zoom`` (a :class:`paos_amd.PsfWindow`) adds a window of every item's PSF at the LAST surface, which must be
+    saved, on a grid ``oversample`` times finer (README.md, "Zoomed PSFs"): the exact band-limited interpolant of the
+    field, ``|Wy u Wx^T|^2`` with real Dirichlet-kernel weights, contracted on the GPU by the fp64 matrix instruction
+    (``paos_zoom_compute``).  The last surface's record gets ``'psf_zoom'`` (size x size float64, samples of the same
+    intensity as ``'psf'``, not divided by ``oversample^2``), ``'zoom_dx'``, ``'zoom_dy'`` (``dx_i / oversample``,
+    ``dy_i / oversample``), ``'zoom_centre'`` (the window's centre ``(x, y)`` in pixels; fine sample ``[size/2][size/2]``
+    lies there) and, with ``field=True``, ``'wfo_zoom'`` (complex128).  Fine samples that fall on grid pixels equal the
+    field's samples bit for bit; a window that runs over the grid edge wraps.  With ``focus_planes`` every plane's dict
+    gets the same keys.  It needs the field of the last surface, so the run takes the ordinary walk, and it synchronises:
+    ``sync=False``, a last surface that is not saved, a size, oversampling or centres that ``paos_zoom_compute`` would
+    refuse are a ``ValueError`` -- before anything is launched.
     """
     nb = len(opt_chains)
     if len(wavelengths) != nb:
@@ -1531,6 +1545,16 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
         if last_key is None or not all(chain[last_key]["save"] for chain in opt_chains):
             raise ValueError("'mtf' / 'otf' outputs and mtf_cuts need the last surface of the chain to be saved")
         keep_psf = True
+    if psf_zoom is not None:
+        from .zoom import PsfWindow
+
+        if not isinstance(psf_zoom, PsfWindow):
+            raise ValueError(f"psf_zoom must be a paos_amd.PsfWindow, got {psf_zoom!r}")
+        if not sync:
+            raise ValueError("psf_zoom synchronises: it cannot be combined with sync=False")
+        if last_key is None or not all(chain[last_key]["save"] for chain in opt_chains):
+            raise ValueError("psf_zoom needs the last surface of the chain to be saved")
+        psf_zoom.check(nb, int(gridsize))
     det_pitch = None
     if detector is not None:
         if last_key is None or not all(chain[last_key]["save"] for chain in opt_chains):
@@ -1577,8 +1601,8 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
 
     # nobody reads an array at a saved surface: the walk may skip writing dead rows at the start and store the PSF
     # straight from the last pass (csrc/frugal_pass.h: STORE)
-    # (a focus stack needs the field of the last surface: the ordinary walk)
-    lean = _WalkState() if (not outputs and metrics_radii_px is None and focus is None) else None
+    # (a focus stack and a zoomed window need the field of the last surface: the ordinary walk)
+    lean = _WalkState() if (not outputs and metrics_radii_px is None and focus is None and psf_zoom is None) else None
     tickets = []  # (_Reduction, [(item index, record)], post): powers are fetched after the walk, so the
     # host keeps planning while the GPU works (no mid-chain synchronisation) -- except when a chain
     # saves more surfaces than the library has ticket slots: then the oldest are fetched early
@@ -1700,11 +1724,14 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
         if otf:  # (before a focus stack, whose planes store their own PSFs)
             recs = [results[i][opt_chains[i][last_key]["num"]] for i in range(nb)]
             otf.attach(dev, recs, [rec["dx"] for rec in recs], [rec["dy"] for rec in recs])
+        if psf_zoom is not None:  # (before a focus stack, which overwrites the field)
+            recs = [results[i][opt_chains[i][last_key]["num"]] for i in range(nb)]
+            psf_zoom.attach(dev, recs, [rec["dx"] for rec in recs], [rec["dy"] for rec in recs])
         if focus is not None:
             placed = {}
             if detector is not None and (chief[0] if want_chief else det_origin) is not None:
                 placed = {"origins": chief[0] if want_chief else det_origin}
-            stacks = _focus_stack(dev, focus, outputs, what, metrics_radii_px, power, detector, placed, otf)
+            stacks = _focus_stack(dev, focus, outputs, what, metrics_radii_px, power, detector, placed, otf, psf_zoom)
             for i in range(nb):
                 results[i][opt_chains[i][last_key]["num"]]["focus"] = stacks[i]
         if sync or own:
