@@ -139,6 +139,66 @@ class PowerTicket:
         return f"PowerTicket(slot {self._red.slot}, {state}{', derived' if self._post is not None else ''})"
 
 
+class _PowerLedger:
+    """The powers of the saved surfaces of one ``run_batch``: ``entries`` holds (_Reduction, [(item index, record)], post)
+    in the order taken, ``post`` deriving the reported powers from the reduced ones.  They are fetched after the walk, so
+    the host keeps planning while the GPU works -- except when a chain saves more surfaces than the library has ticket
+    slots: then the oldest are fetched early (``make_room``).  Every ticket is a reduction of its own (a slot number does
+    not say which: the library hands a slot out again once it was fetched or released) -- except the one a pass program
+    left behind when it stored the PSF for good (``lean.final_ticket``), which answers for every saved surface from there
+    on: those entries share ONE _Reduction (``final``), fetched once, also when a mid-walk drain has already read it.
+    The walk ``offer``s the power a pass program summed while it stored a surface's field (csrc/frugal_pass.h:
+    pow_partial); ``on_saved`` may ``claim`` it for that surface's records, and what nobody claimed is given back
+    (``decline``) when the next surface begins and when the walk ends."""
+
+    def __init__(self, dev):
+        self.dev, self.entries, self.drained, self._final, self.offered = dev, [], 0, {}, None
+
+    def final(self, ticket):
+        return self._final.setdefault(ticket, _Reduction(self.dev, ticket))
+
+    def record(self, ticket, pending, post=None, final=False):
+        red = self.final(ticket) if final else _Reduction(self.dev, ticket)
+        self.entries.append((red, pending, post))
+        return red
+
+    def offer(self, ticket, post=None):
+        self.offered = (ticket, post)
+
+    def claim(self, pending):
+        (ticket, post), self.offered = self.offered, None
+        self.record(ticket, pending, post)
+
+    def decline(self):
+        if self.offered is not None:
+            self.dev.norm2_release(self.offered[0])
+            self.offered = None
+
+    def outstanding(self):
+        return sum(1 for e in self.entries[self.drained:] if e[0].raw is None and not e[0].released)
+
+    def drain(self):
+        for red, pending, post in self.entries[self.drained:]:
+            values = red.values()
+            if post is not None:
+                values = post(values)
+            for i, rec in pending:
+                rec["power"] = float(values[i])
+        self.drained = len(self.entries)
+
+    def make_room(self, spare=2):
+        """Before a ticket is taken: fetch what is pending when the library's ring is about to fill."""
+        if self.outstanding() >= _lib.NORM_SLOTS - spare:
+            self.drain()
+
+    def hand_out(self):
+        """``sync=False``: handles to the reductions still outstanding instead of their values (nothing waits here)."""
+        for red, pending, post in self.entries[self.drained:]:
+            handle = PowerTicket(red, post)
+            for i, rec in pending:
+                rec["power_ticket"] = handle
+
+
 class _BatchApertures:
     """The apertures of one surface for every wavefront of a batch as arrays (round 5: ``_plan_batch``): pixel-unit centres
     and sizes, shape, obscuration flag -- what the library's parameter blocks, the line-record test and the live-row
@@ -862,42 +922,66 @@ def _queue_steps(comp, lens, stw, ptp, wts, inv_stw, inv_wts):
     comp.wts(wts, inv_wts != 0.0)
 
 
-def _start_field(dev, plans, value, write_rows=None, write_cols=None, defer=None):
-    """The wavefront is still the constant ``value`` (wfo.py:118).  When every item opens with a
-    stand-alone aperture of one shape, ones -> aperture -> [make_stop] is a single write of the
-    field (paos_start); otherwise fill and let the surface run as usual.  Returns False, or -- when the
-    first surface's aperture and stop are done -- per item the index of the first item with the same field.  ``write_rows`` ([lo, hi) per item): only these rows are
-    written, the others are left standing for zeros (paos_start_rows)."""
+def _given(**kw):
+    """The keywords that are not None: a device call names only those that apply."""
+    return {k: v for k, v in kw.items() if v is not None}
+
+
+def _enqueue_power(dev, rows=None, like=None, cols=None):
+    """Enqueue sum |u|^2 of every item; returns the ticket.  ``rows`` (and ``cols`` with them): only these may be non-zero,
+    the others are not read; ``like``: per item the index of an item that holds the same field."""
+    if rows is None:
+        return dev.norm2_enqueue()
+    if cols is not None:
+        return dev.norm2_enqueue(rows, same_as=like, live_cols=cols)
+    return dev.norm2_enqueue(rows, **_given(same_as=like))
+
+
+def _start_field(dev, fs, plans, value, lean, may_defer):
+    """The wavefront is still the constant ``value`` (wfo.py:118) at the first surface that does something.  When every
+    item opens with a stand-alone aperture of one shape, ones -> aperture -> [make_stop] is a single write of the field
+    (paos_start) -- in a lean walk inside the aperture's rows only, the others left standing for zeros (paos_start_rows),
+    and with ``START_BOX`` inside its columns as well.  Returns (True, copies): the surface's aperture and stop are done,
+    ``copies`` names per item the first item with the same field (None: all differ).  Otherwise fill, and (False, None):
+    the surface runs as usual.  ``may_defer``: a box start is not launched but left as ``lean.deferred_start``."""
+    rows = cols = None
+    if lean is not None and hasattr(dev, "zero_outside_rows"):
+        trial = [[0, dev.n] for _ in plans]
+        _live_rows_after(plans, trial, dev.n)
+        # worth it only when every item's aperture leaves whole rows dark
+        if all(r[0] > 0 or r[1] < dev.n for r in trial) and all(r[0] < r[1] for r in trial):
+            rows = trial
+            if START_BOX:  # ... and whole columns: the field is written inside the aperture's box only
+                cols = _live_cols_of(plans, dev.n)
     batch_ap = getattr(plans, "ap", None)
     if batch_ap is not None:
         if bool(batch_ap.rect.any()) and not bool(batch_ap.rect.all()):
             dev.fill(value)
-            return None
+            return False, None
         code = _lib.SHAPE_RECT if bool(batch_ap.rect.all()) else _lib.SHAPE_ELLIPSE
         blocks = batch_ap.blocks()[0].tolist()
     else:
         aps = [p["aperture"] for p in plans]
         if any(a is None for a in aps) or len({isinstance(a[0], EllipticalAperture) for a in aps}) != 1:
             dev.fill(value)
-            return None
+            return False, None
         code = _lib.SHAPE_ELLIPSE if isinstance(aps[0][0], EllipticalAperture) else _lib.SHAPE_RECT
         blocks = [a[0].block(obscuration=a[1]) for a in aps]
     stops = [1.0 if p["stop"] else 0.0 for p in plans]
-    if defer is not None:  # (the caller launches later: _walk, a Zernike surface may ride on the write)
-        defer.update(value=value, code=code, blocks=blocks, stops=stops, rows=write_rows, cols=write_cols)
-    elif write_rows is None:
-        dev.start(value, code, blocks, stops)
-    elif write_cols is None:
-        dev.start(value, code, blocks, stops, write_rows=write_rows)
-    else:
-        dev.start(value, code, blocks, stops, write_rows=write_rows, write_cols=write_cols)
-    # which items now hold the same field: same aperture record, stop flag and row window
+    # which items now hold the same field: same aperture record, stop flag and window
     seen, same_as = {}, []
     for i, (b, st) in enumerate(zip(blocks, stops)):
-        key = (tuple(float(x) for x in b), st, tuple(write_rows[i]) if write_rows is not None else None,
-               tuple(write_cols[i]) if write_cols is not None else None)
+        key = (tuple(float(x) for x in b), st, tuple(rows[i]) if rows is not None else None,
+               tuple(cols[i]) if cols is not None else None)
         same_as.append(seen.setdefault(key, i))
-    return same_as
+    copies = same_as if len(set(same_as)) < len(same_as) else None
+    if may_defer and cols is not None:  # (launched later: _launch_start, a Zernike surface may ride on the write)
+        lean.deferred_start = dict(value=value, code=code, blocks=blocks, stops=stops, rows=rows, cols=cols, like=copies)
+    else:
+        dev.start(value, code, blocks, stops, **_given(write_rows=rows, write_cols=cols))
+    _live_rows_after(plans, fs.live, dev.n)
+    fs.stale, fs.stale_cols = rows is not None, cols if rows is not None else None
+    return True, copies
 
 
 class _WalkState:
@@ -919,12 +1003,108 @@ class _WalkState:
         self.deferred_start = None
 
 
-def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_at=None, power_state=None):
+class _FieldState:
+    """What the walk knows about the fields in memory:
+    ``live`` -- per item the rows [lo, hi) outside which the field is exactly zero: set by stand-alone apertures, kept by
+    what multiplies (stops, Zernike, phase screens), skipped by the next pass program and forgotten once it has run;
+    ``stale`` -- the rows outside ``live`` hold old data that stands for zeros (lean start), as do, with ``stale_cols``,
+    the columns outside these [lo, hi) per item (paos_start_box);
+    ``dead`` -- the field has been given up for its PSF (lean end): nothing may run on it any more;
+    ``twins`` -- per item the index of an item whose field is a copy of its own (None: nothing known);
+    ``power`` -- the ticket of the power of the field a pass program has just stored (``flush(final_power=True)``)."""
+
+    def __init__(self, n, batch):
+        self.n, self.live = n, [[0, n] for _ in range(batch)]
+        self.stale, self.stale_cols, self.dead, self.twins, self.power = False, None, False, None, None
+
+    def known_rows(self):
+        return [list(r) for r in self.live] if any(r[0] > 0 or r[1] < self.n for r in self.live) else None
+
+    def stale_cols_for(self, rows):
+        """The columns that go with ``rows`` (``known_rows()``, or None) for somebody who reads those rows only."""
+        return self.stale_cols if (self.stale and rows is not None) else None
+
+    def settle(self, dev):
+        """Before anything reads whole fields: rows that stand for zeros become zeros."""
+        if self.stale:
+            if self.stale_cols is not None:
+                dev.zero_outside_rows(self.live, self.stale_cols)
+            else:
+                dev.zero_outside_rows(self.live)
+            self.stale, self.stale_cols = False, None
+
+    def flush(self, dev, comp, lean, ledger, final_intensity=False, final_power=False):
+        """Run what the compiler has queued.  ``final_intensity``: the last pass stores the PSF instead of the field, which
+        is given up; ``final_power``: it sums |u|^2 while it stores the field (paos_run_program: final_intensity = 2) -- the
+        surface reached is saved (or a stop) and nothing but the program touches its field first, so no sweep has to read
+        the field back.  Returns the number of passes run."""
+        if self.dead:
+            comp.program()  # drop what was queued behind the PSF store
+            return 0
+        rows = self.known_rows()
+        if not comp.pending():
+            return 0
+        store = True if final_intensity else (2 if final_power else False)
+        if store == 2 and ledger is not None:
+            ledger.make_room()  # (the ticket is taken inside)
+        out = comp.flush(dev, live_rows=rows, rows_stale=self.stale and rows is not None, final_intensity=store,
+                         live_cols=self.stale_cols_for(rows))
+        done, ticket = out if store else (out, None)
+        if final_intensity:
+            lean.psf_ticket = lean.final_ticket = ticket
+            self.dead = True
+        elif final_power:
+            self.power = ticket if done else None
+        if done:  # the program has written every row and column: nothing stands for zeros, nothing is known to be zero
+            self.stale, self.stale_cols = False, None
+            for r in self.live:
+                r[0], r[1] = 0, self.n
+        return done
+
+
+def _zernike_rides(d, plans, items, n, pending):
+    """May this surface's Zernike phase be applied while the deferred start field ``d`` is written?  Every item carries
+    an ordinary Zernike expansion whose unit disk lies inside the start's box, nothing else of the surface comes in
+    front of it (aperture, stop), nothing is queued (``pending``), and nobody wants the wfe map."""
+    any_stop, any_zern, _, any_ap = plans.summary()
+    if not any_zern or any_stop or any_ap or pending or (len(plans) == 1 and bool(items[0]["save"])):
+        return False
+    for p, rows, cols in zip(plans, d["rows"], d["cols"]):
+        z = p["zernike"]
+        if z is None or z["pupil"] is not None or not (z["radius"] > 0 and z["dx"] > 0 and z["dy"] > 0):
+            return False
+        hx, hy = z["radius"] / z["dx"], z["radius"] / z["dy"]
+        if not (cols[0] <= n // 2 - hx and n // 2 + hx <= cols[1] - 1 and
+                rows[0] <= n // 2 - hy and n // 2 + hy <= rows[1] - 1):
+            return False
+    return True
+
+
+def _launch_start(dev, lean, plans=None, items=None, pending=True):
+    """Launch the deferred start field -- with the Zernike phase of ``plans`` on it when that is possible (True: the
+    surface's Zernike is done), else as the walk would have launched it at the first surface."""
+    d, lean.deferred_start = lean.deferred_start, None
+    power = d.get("power")
+    if plans is not None and _zernike_rides(d, plans, items, dev.n, pending):
+        zs, nmax, kdim, table, build = _zernike_tables(plans)
+        slot = dev.start_zernike(d["value"], d["code"], d["blocks"], d["stops"], d["rows"], d["cols"], nmax, kdim, table,
+                                 build([z["Z"] for z in zs]), power=power is not None)
+        if power is not None:
+            power.slot = int(slot)
+        return True
+    dev.start(d["value"], d["code"], d["blocks"], d["stops"], write_rows=d["rows"], write_cols=d["cols"])
+    if power is not None:
+        power.slot = int(_enqueue_power(dev, d["rows"], d["like"], d["cols"]))
+    return False
+
+
+def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_at=None, ledger=None):
     """Drive all items through their chains in lock-step, one surface at a time.  ``fresh``: the
     constant the field is meant to hold but has not been filled with yet (see _start_field).
     ``lean`` (a _WalkState, optional): the caller reads no arrays at saved surfaces, only powers (through
     ``lean.rows`` / ``lean.psf_ticket``) -- the walk may then leave dead rows unwritten at the start and, when
-    ``psf_at`` names the last surface, have the last pass store the PSF instead of the field."""
+    ``psf_at`` names the last surface, have the last pass store the PSF instead of the field.  ``ledger`` (a
+    ``_PowerLedger``, optional): the power a pass program sums while it stores a saved surface's field is offered there."""
     _SAG_SEEN.clear()  # (a Grid Sag array is hashed once per walk, not once per item)
     keys = [list(c.keys()) for c in chains]
     if any(k != keys[0] for k in keys[1:]):
@@ -935,105 +1115,10 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
     beams = BeamBatch(st0.pupil_diameter, [st.wavelength for st in states], st0.gridsize, st0.zoom)
     state, n = beams.state, beams.n
     comp = (SeparableCompiler if _passes.SEPARABLE else PassCompiler)(len(states), dev.n)
-    npass = 0
-    twins = None  # per item the index of an item whose field is a copy of its own (None: nothing known)
-    # rows of each item known to be exactly zero in memory (outside [lo, hi)): set by stand-alone
-    # apertures, kept by stops / Zernike / phase screens (they multiply), handed to the next pass
-    # program (which skips them) and forgotten once that program has run
-    live = [[0, dev.n] for _ in states]
-    stale = [False]  # rows outside ``live`` hold old data that stands for zeros (lean start)
-    stale_cols = [None]  # ... and, while ``stale``, so do the columns outside these [lo, hi) per item (paos_start_box)
-    dead = [False]   # the field has been given up for its PSF (lean end): nothing may run on it any more
-    fused_start = [0]  # 1: the first field was written with the Zernike phase of the next surface on it (launch_start)
-
-    prog_power = [None]  # ticket of the power of the field a program has just stored (flush(final_power=True))
+    fs = _FieldState(dev.n, len(states))
+    npass = fused_start = 0  # fused_start: the first field was written with the Zernike phase of the next surface on it
     factor_cols_t, factor_cols_s = [], []  # [surface][item] ABCD factors met so far (run.py:215-219)
     rays = _Rays(states)  # the paraxial rays of every item (_plan_batch plans from them, `advance` moves them)
-
-    def known_rows():
-        return [list(r) for r in live] if any(r[0] > 0 or r[1] < dev.n for r in live) else None
-
-    def settle():
-        """Before anything reads whole fields: rows that stand for zeros become zeros."""
-        if stale[0]:
-            if stale_cols[0] is not None:
-                dev.zero_outside_rows(live, stale_cols[0])
-            else:
-                dev.zero_outside_rows(live)
-            stale[0], stale_cols[0] = False, None
-
-    def keep_reads_field():
-        """The saved LAST surface of a lean walk that keeps its PSFs, reached without a pass program having stored
-        them (a single-surface chain; every hop shorter than lambda / 1000): ``on_saved`` then takes |u|^2 of the WHOLE
-        field (paos_psf_keep / paos_psf_keep_power), so rows that merely stand for zeros have to be zeros first
-        (the PSF and its power came out NaN on the model device)."""
-        if psf_at is not None and key == psf_at and lean.psf_ticket is None:
-            settle()
-
-    def zernike_rides(d, plans, items):
-        """May this surface's Zernike phase be applied while the deferred start field ``d`` is written?  Every item carries
-        an ordinary Zernike expansion whose unit disk lies inside the start's box, nothing else of the surface comes in
-        front of it (aperture, stop), nothing is queued, and nobody wants the wfe map."""
-        any_stop, any_zern, _, any_ap = plans.summary()
-        if not any_zern or any_stop or any_ap or comp.pending() or (len(plans) == 1 and bool(items[0]["save"])):
-            return False
-        for p, rows, cols in zip(plans, d["rows"], d["cols"]):
-            z = p["zernike"]
-            if z is None or z["pupil"] is not None or not (z["radius"] > 0 and z["dx"] > 0 and z["dy"] > 0):
-                return False
-            hx, hy = z["radius"] / z["dx"], z["radius"] / z["dy"]
-            if not (cols[0] <= dev.n // 2 - hx and dev.n // 2 + hx <= cols[1] - 1 and
-                    rows[0] <= dev.n // 2 - hy and dev.n // 2 + hy <= rows[1] - 1):
-                return False
-        return True
-
-    def launch_start(plans=None, items=None):
-        """Launch the deferred start field -- with the Zernike phase of ``plans`` on it when that is possible (True: the
-        surface's Zernike is done), else as the walk would have launched it at the first surface."""
-        d, lean.deferred_start = lean.deferred_start, None
-        power = d.get("power")
-        if plans is not None and zernike_rides(d, plans, items):
-            zs, nmax, kdim, table, build = _zernike_tables(plans)
-            slot = dev.start_zernike(d["value"], d["code"], d["blocks"], d["stops"], d["rows"], d["cols"], nmax, kdim, table,
-                                     build([z["Z"] for z in zs]), power=power is not None)
-            if power is not None:
-                power.slot = int(slot)
-            fused_start[0] += 1
-            return True
-        dev.start(d["value"], d["code"], d["blocks"], d["stops"], write_rows=d["rows"], write_cols=d["cols"])
-        if power is not None:
-            power.slot = int(dev.norm2_enqueue(d["rows"], same_as=d["like"], live_cols=d["cols"]))
-        return False
-
-    def flush(final_intensity=False, final_power=False):
-        if dead[0]:
-            comp.program()  # drop what was queued behind the PSF store
-            return 0
-        rows = known_rows()
-        if not comp.pending():
-            return 0
-        cols = stale_cols[0] if (stale[0] and rows is not None) else None
-        if final_intensity:
-            done, ticket = comp.flush(dev, live_rows=rows, rows_stale=stale[0] and rows is not None, final_intensity=True,
-                                      live_cols=cols)
-            lean.psf_ticket = lean.final_ticket = ticket
-            dead[0] = True
-        elif final_power:
-            # the surface reached by this program is saved (or a stop) and nothing but the program touches its field
-            # first: the last pass sums |u|^2 while it stores (paos_run_program: final_intensity = 2) -- no sweep that
-            # reads the field back
-            if power_state is not None:
-                power_state["before"]()  # (the ticket is taken inside: room in the ring first)
-            done, ticket = comp.flush(dev, live_rows=rows, rows_stale=stale[0] and rows is not None, final_intensity=2,
-                                      live_cols=cols)
-            prog_power[0] = ticket if done else None
-        else:
-            done = comp.flush(dev, live_rows=rows, rows_stale=stale[0] and rows is not None, live_cols=cols)
-        if done:
-            stale[0], stale_cols[0] = False, None
-            for r in live:
-                r[0], r[1] = 0, dev.n
-        return done
 
     # from which surface on nothing touches the field any more (index into keys[0]; len = never)
     order = keys[0]
@@ -1042,10 +1127,8 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
         inert_from -= 1
     for pos, key in enumerate(order):
         items = [c[key] for c in chains]
-        if power_state is not None:
-            if power_state["ticket"] is not None and not power_state.get("used"):
-                dev.norm2_release(power_state["ticket"])  # (taken for a stop on a surface nobody saved)
-            power_state["ticket"], power_state["post"], power_state["used"] = None, None, False  # (a ticket belongs to its surface)
+        if ledger is not None:
+            ledger.decline()  # (an offer belongs to its surface: taken for a stop on a surface nobody saved)
         dxs, dys, wls = state[:, beams.DX].tolist(), state[:, beams.DY].tolist(), state[:, beams.WL].tolist()
         readout = []
 
@@ -1055,6 +1138,10 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
             return readout
 
         plans = _plan_batch(states, items, n, dxs, dys, wls, lambda i: wz_dtf()[0][i], rays=rays)
+        # (the ray-transfer factors met so far, one column per surface; a saved surface gets its product -- lazily)
+        col_t, col_s = [it["ABCDt"] for it in items], [it["ABCDs"] for it in items]
+        factor_cols_t.append(col_t)
+        factor_cols_s.append(col_s)
         saved = any(it["save"] for it in items)
         if saved:  # push_results scalars (run.py:12-27) are those BEFORE magnification / lens / propagate
             # ... and so is the chief ray: behind this surface's coordinate break, before its ABCD matrices (run.py:209-210)
@@ -1066,169 +1153,132 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
                     p["scalars"] = {"wz": float(wz[i]), "distancetofocus": float(dtf[i]), "fratio": fr[i],
                                     "dx": dxs[i], "dy": dys[i], "wl": wls[i], "extent": ext[i],
                                     "propagator": props[i]}
-        # the pilot beams of the whole batch through this surface (one C call), the rays and the
-        # accumulated ABCD factors of each item
-        # (the ray-transfer factors met so far, one column per surface; a saved surface gets its product -- lazily)
-        col_t, col_s = [it["ABCDt"] for it in items], [it["ABCDs"] for it in items]
-        factor_cols_t.append(col_t)
-        factor_cols_s.append(col_s)
-        lens, stw, ptp, wts, inv_stw, inv_wts = beams.surface(*_gate_arrays(col_t, col_s))
-        rays.advance(col_t, col_s)
-        if saved:
-            for i, (it, p) in enumerate(zip(items, plans)):
-                if it["save"]:
                     p["ABCDt"] = ABCDProduct(tuple(col[i] for col in factor_cols_t))
                     p["ABCDs"] = ABCDProduct(tuple(col[i] for col in factor_cols_s))
-
-        zernike_done = False
-        if lean is not None and lean.deferred_start is not None:
-            zernike_done = launch_start(plans, items)
+        # the pilot beams of the whole batch (one C call) and the rays of each item through this surface
+        lens, stw, ptp, wts, inv_stw, inv_wts = beams.surface(*_gate_arrays(col_t, col_s))
+        rays.advance(col_t, col_s)
+        # (a start field that waited for this surface: written now, with this surface's Zernike phase on it if that may be)
+        zernike_done = (lean is not None and lean.deferred_start is not None
+                        and _launch_start(dev, lean, plans, items, comp.pending()))
+        fused_start += zernike_done
         if fresh is not None and not saved and all(_inert(it) for it in items):
             # (coordinate breaks in front of the first mirror: the field is still the constant it will be filled with;
             # the first surface that does something -- usually aperture + stop -- then writes it in one go, _start_field)
             continue
+        any_stop, any_zern, any_map, any_ap = plans.summary()
+        started, like = False, None  # like: the copies among the fields, for ``on_saved`` (``lean.same_as``)
         if fresh is not None:
             value, fresh = fresh, None
-            rows0 = cols0 = None
-            if lean is not None and hasattr(dev, "zero_outside_rows"):
-                trial = [[0, dev.n] for _ in states]
-                _live_rows_after(plans, trial, dev.n)
-                # worth it only when every item's aperture leaves whole rows dark
-                if all(r[0] > 0 or r[1] < dev.n for r in trial) and all(r[0] < r[1] for r in trial):
-                    rows0 = trial
-                    if START_BOX:  # ... and whole columns: the field is written inside the aperture's box only
-                        cols0 = _live_cols_of(plans, dev.n)
             # still copies of each other unless this surface puts a wavefront error on them
-            untouched = not any(p["zernike"] is not None or p["phase_map"] is not None for p in plans)
+            untouched = not (any_zern or any_map)
             # A box start with nothing else on its surface and a surface behind it waits for that surface: if it is a Zernike
-            # surface, the field is written once with the phase on it (launch_start).  Nothing reads the field meanwhile: a
+            # surface, the field is written once with the phase on it (_launch_start).  Nothing reads the field meanwhile: a
             # lean walk's saved surface wants its power only, which the deferred launch brings along.
-            defer = None
-            if (FUSE_START and cols0 is not None and untouched and hasattr(dev, "start_zernike") and pos + 1 < len(order)
-                    and not (psf_at is not None and key == psf_at) and all(_identity_gates(it) for it in items)):
-                defer = {}
-            same_as = _start_field(dev, plans, value, write_rows=rows0, write_cols=cols0, defer=defer)
-            if same_as is not None:
-                _live_rows_after(plans, live, dev.n)
-                stale[0] = rows0 is not None
-                stale_cols[0] = cols0 if stale[0] else None
-                want_wfe = len(plans) == 1 and bool(items[0]["save"])
-                copies = same_as if len(set(same_as)) < len(same_as) else None
-                if defer is not None:
-                    defer["like"] = copies
-                    lean.deferred_start = defer
-                wfe = _launch_zernike(dev, plans, want_wfe=want_wfe, same_as=copies if TWIN_FIELDS else None)
-                wfe = _launch_phase_maps(dev, plans, wfe)
-                if saved:
-                    if lean is not None:
-                        keep_reads_field()
-                        lean.rows = known_rows()
-                        lean.cols = stale_cols[0] if (stale[0] and lean.rows is not None) else None
-                        lean.same_as = copies if untouched else None
-                    on_saved(key, items, plans, wfe)
-                    if lean is not None:
-                        lean.same_as, lean.cols = None, None
-                _queue_steps(comp, lens, stw, ptp, wts, inv_stw, inv_wts)
-                if lean is not None and lean.deferred_start is not None and comp.pending():
-                    launch_start()  # (the surface has queued something after all: the field must exist first)
-                # (round 5) ... and they stay copies until something wavelength-dependent is applied or queued: a Zernike surface
+            may_defer = (FUSE_START and untouched and hasattr(dev, "start_zernike") and pos + 1 < len(order)
+                         and not (psf_at is not None and key == psf_at) and all(_identity_gates(it) for it in items))
+            started, copies = _start_field(dev, fs, plans, value, lean, may_defer)
+            if started:
+                # (round 5) they stay copies until something wavelength-dependent is applied or queued: a Zernike surface
                 # right behind the start (SYN20's S02) reads one field per group of them (paos_zernike_like)
-                twins = copies if (TWIN_FIELDS and untouched and not comp.pending()) else None
-                continue
-        fuse_ap = FUSE_APERTURES
-        any_stop, any_zern, any_map, any_ap = plans.summary()
-        own_breaker = saved or any_stop or any_zern or any_map
-        if fuse_ap == "auto":
-            # an aperture followed on its own surface by a stop / Zernike / save could only ride
-            # on a transform-free pass: the stand-alone aperture kernel is cheaper there
-            # -- unless the previous propagation left a pass open: then the aperture becomes the
-            # last operator of that pass (applied while the tile is stored) at no extra traffic
-            if plans.ap is not None:
-                fuse_ap = (not own_breaker or comp.open_takes_mask()) and plans.ap.fits_line_records(dev.n, dev.precision)
-            else:
-                aps = [p["aperture"] for p in plans if p["aperture"] is not None]
-                fuse_ap = (bool(aps) and (not own_breaker or comp.open_takes_mask()) and
-                           all(_aperture_fits_line_records(h, o, dev.n, dev.precision) for h, o in aps))
-        if fuse_ap:
-            _queue_apertures(comp, plans)
-        breaker = own_breaker or (any_ap and not fuse_ap)
-        if breaker:
-            # the field must be current before a non-fusable operator -- unless all this surface wants of it is the
-            # PSF of every item (a lean walk's last, saved surface with nothing else on it): then the last pass
-            # stores |u|^2 instead
-            only_saved = (saved and all(it["save"] for it in items) and
-                          not (any_stop or any_zern or any_map or (any_ap and not fuse_ap)))
-            # ... the last surface -- or a surface behind which only inert ones follow (the image plane right behind a
-            # saved slit): what the program stores here is what the chain ends with
-            # (only when this surface has no steps of its own: its lens / propagation would act on the field the inert
-            # surfaces receive -- a last mirror or lens some distance in front of the image plane)
-            ends_here = key == psf_at or (INERT_TAIL and pos + 1 >= inert_from and psf_at == order[-1] and
-                                          all(_identity_gates(it) for it in items))
-            as_psf = (lean is not None and psf_at is not None and ends_here and only_saved and comp.pending()
-                      and not dead[0])
-            # a stop right behind the program needs the power of what the program stores; a saved surface whose
-            # field IS what the program stores reports it
-            stop_rides = (STOP_FROM_PROGRAM and any_stop and comp.pending() and not dead[0] and
-                          not (any_ap and not fuse_ap))
-            npass += flush(final_intensity=as_psf,
-                           final_power=(not as_psf and comp.pending() and not dead[0] and
-                                        (stop_rides or (power_state is not None and only_saved))))
-        if not fuse_ap and any_ap:
-            _launch_apertures(dev, plans)
-            if not comp.pending():
-                _live_rows_after(plans, live, dev.n)
-        if any_stop:
-            settle()
-            flags = [1.0 if p["stop"] else 0.0 for p in plans]
-            if prog_power[0] is not None:  # the program's last pass has summed the power on its way out
-                dev.make_stop(flags, power_known=True, defer=STOP_DEFERRED)
-                if power_state is not None:
-                    # should the surface be saved: the power BEHIND the stop is P (1 / sqrt P)^2 where the stop applies
-                    power_state["ticket"] = prog_power[0]
-                    power_state["post"] = lambda v, f=np.array(flags): np.where(f != 0.0, v * (1.0 / np.sqrt(v)) ** 2, v)
+                like, fs.twins = (copies if untouched else None), (copies if TWIN_FIELDS else None)
+        if not started:
+            fuse_ap = FUSE_APERTURES
+            own_breaker = saved or any_stop or any_zern or any_map
+            if fuse_ap == "auto":
+                # an aperture followed on its own surface by a stop / Zernike / save could only ride
+                # on a transform-free pass: the stand-alone aperture kernel is cheaper there
+                # -- unless the previous propagation left a pass open: then the aperture becomes the
+                # last operator of that pass (applied while the tile is stored) at no extra traffic
+                if plans.ap is not None:
+                    fuse_ap = (not own_breaker or comp.open_takes_mask()) and plans.ap.fits_line_records(dev.n, dev.precision)
                 else:
-                    dev.norm2_release(prog_power[0])
-                prog_power[0] = None
-            else:
-                dev.make_stop(flags)
-        elif prog_power[0] is not None:
-            if power_state is not None:
-                power_state["ticket"], power_state["post"] = prog_power[0], None
-            else:
-                dev.norm2_release(prog_power[0])
-            prog_power[0] = None
-        want_wfe = len(plans) == 1 and bool(items[0]["save"])
-        if twins is not None and (comp.pending() or fuse_ap or any_ap or any_stop):
-            twins = None  # (something has been applied to the fields, or waits to be)
-        wfe = None if zernike_done else _launch_zernike(dev, plans, want_wfe=want_wfe, same_as=twins)
+                    aps = [p["aperture"] for p in plans if p["aperture"] is not None]
+                    fuse_ap = (bool(aps) and (not own_breaker or comp.open_takes_mask()) and
+                               all(_aperture_fits_line_records(h, o, dev.n, dev.precision) for h, o in aps))
+            if fuse_ap:
+                _queue_apertures(comp, plans)
+            breaker = own_breaker or (any_ap and not fuse_ap)
+            if breaker:
+                # the field must be current before a non-fusable operator -- unless all this surface wants of it is the
+                # PSF of every item (a lean walk's last, saved surface with nothing else on it): then the last pass
+                # stores |u|^2 instead
+                only_saved = (saved and all(it["save"] for it in items) and
+                              not (any_stop or any_zern or any_map or (any_ap and not fuse_ap)))
+                # ... the last surface -- or a surface behind which only inert ones follow (the image plane right behind a
+                # saved slit): what the program stores here is what the chain ends with
+                # (only when this surface has no steps of its own: its lens / propagation would act on the field the inert
+                # surfaces receive -- a last mirror or lens some distance in front of the image plane)
+                ends_here = key == psf_at or (INERT_TAIL and pos + 1 >= inert_from and psf_at == order[-1] and
+                                              all(_identity_gates(it) for it in items))
+                as_psf = (lean is not None and psf_at is not None and ends_here and only_saved and comp.pending()
+                          and not fs.dead)
+                # a stop right behind the program needs the power of what the program stores; a saved surface whose
+                # field IS what the program stores reports it
+                stop_rides = (STOP_FROM_PROGRAM and any_stop and comp.pending() and not fs.dead and
+                              not (any_ap and not fuse_ap))
+                npass += fs.flush(dev, comp, lean, ledger, final_intensity=as_psf,
+                                  final_power=(not as_psf and comp.pending() and not fs.dead and
+                                               (stop_rides or (ledger is not None and only_saved))))
+            if not fuse_ap and any_ap:
+                _launch_apertures(dev, plans)
+                if not comp.pending():
+                    _live_rows_after(plans, fs.live, dev.n)
+            post = None
+            if any_stop:
+                fs.settle(dev)
+                flags = [1.0 if p["stop"] else 0.0 for p in plans]
+                if fs.power is not None:  # the program's last pass has summed the power on its way out
+                    dev.make_stop(flags, power_known=True, defer=STOP_DEFERRED)
+                    # should the surface be saved: the power BEHIND the stop is P (1 / sqrt P)^2 where the stop applies
+                    post = lambda v, f=np.array(flags): np.where(f != 0.0, v * (1.0 / np.sqrt(v)) ** 2, v)
+                else:
+                    dev.make_stop(flags)
+            if fs.power is not None:  # what the program has summed: this surface's to report, if somebody asks
+                if ledger is not None:
+                    ledger.offer(fs.power, post)
+                else:
+                    dev.norm2_release(fs.power)
+                fs.power = None
+            if fs.twins is not None and (comp.pending() or fuse_ap or any_ap or any_stop):
+                fs.twins = None  # (something has been applied to the fields, or waits to be)
+        # what is left of the surface, whichever way its aperture and stop were done
+        wfe = None if zernike_done else _launch_zernike(dev, plans, want_wfe=len(plans) == 1 and bool(items[0]["save"]),
+                                                        same_as=fs.twins)
         if any_zern or any_map:
-            twins = None
+            fs.twins = None
         wfe = _launch_phase_maps(dev, plans, wfe)
         if saved:
-            if lean is not None:
-                keep_reads_field()
-                lean.rows = known_rows() if not comp.pending() else None
-                lean.cols = stale_cols[0] if (stale[0] and lean.rows is not None) else None
+            if lean is None:
+                fs.settle(dev)
             else:
-                settle()
+                # The saved LAST surface of a lean walk that keeps its PSFs, reached without a pass program having stored
+                # them (a single-surface chain; every hop shorter than lambda / 1000): ``on_saved`` then takes |u|^2 of the
+                # WHOLE field (paos_psf_keep / paos_psf_keep_power), so rows that merely stand for zeros have to be zeros
+                # first (the PSF and its power came out NaN on the model device)
+                if psf_at is not None and key == psf_at and lean.psf_ticket is None:
+                    fs.settle(dev)
+                lean.rows = fs.known_rows() if not comp.pending() else None
+                lean.cols, lean.same_as = fs.stale_cols_for(lean.rows), like
             on_saved(key, items, plans, wfe)
             if lean is not None:
-                lean.rows, lean.psf_ticket, lean.cols = None, None, None
+                lean.rows, lean.psf_ticket, lean.cols, lean.same_as = None, None, None, None
         _queue_steps(comp, lens, stw, ptp, wts, inv_stw, inv_wts)
         if comp.pending():
-            twins = None
-    if power_state is not None and power_state["ticket"] is not None and not power_state.get("used"):
-        dev.norm2_release(power_state["ticket"])  # (taken for a stop on the last surface, which nobody saved)
-        power_state["ticket"] = None
+            fs.twins = None
+            if lean is not None and lean.deferred_start is not None:
+                _launch_start(dev, lean)  # (the surface has queued something after all: the field must exist first)
+    if ledger is not None:
+        ledger.decline()  # (taken for a stop on the last surface, which nobody saved)
     if lean is not None and lean.deferred_start is not None:
-        launch_start()
+        _launch_start(dev, lean)
     if fresh is not None:  # an empty chain still yields the initial wavefront
         dev.fill(fresh)
-    npass += flush()
-    settle()
+    npass += fs.flush(dev, comp, lean, ledger)
+    fs.settle(dev)
     if stats is not None:
         stats["fused_passes"] = npass
-        stats["fused_start"] = fused_start[0]
+        stats["fused_start"] = fused_start
 
 
 # One idle single-wavefront context per (grid, precision, device) is kept between run() calls:
@@ -1309,17 +1359,16 @@ def run(pupil_diameter, wavelength, gridsize, zoom, field, opt_chain, precision=
     return retval
 
 
-class _FocusPlan:
-    """What ``run_batch(focus_planes=...)`` needs of the pilot beams behind the last surface: ``beams`` (the BeamBatch as
-    the whole chain leaves it) and ``planes`` (the defocus values, in the caller's order)."""
-
-    def __init__(self, beams, planes):
-        self.beams, self.planes = beams, planes
+def _need_saved_last(chains, last_key, who):
+    """Every product of the last surface asks for this first -- before anything is launched."""
+    if last_key is None or not all(chain[last_key]["save"] for chain in chains):
+        raise ValueError(f"{who} the last surface of the chain to be saved")
 
 
 def _plan_focus(states, chains, focus_planes, last_key):
     """Every check of ``focus_planes`` -- on the scalars alone, so before anything is launched: the pilot beams are taken
-    through the chain the way ``_walk`` takes them (one planner call per surface), the field is not."""
+    through the chain the way ``_walk`` takes them (one planner call per surface), the field is not.  Returns (the
+    BeamBatch as the whole chain leaves it, the defocus values in the caller's order)."""
     try:
         planes = [float(dz) for dz in focus_planes]
     except TypeError:
@@ -1328,8 +1377,7 @@ def _plan_focus(states, chains, focus_planes, last_key):
         raise ValueError("focus_planes must be finite")
     if len(set(planes)) != len(planes):
         raise ValueError("focus_planes must be distinct")
-    if last_key is None or not all(chain[last_key]["save"] for chain in chains):
-        raise ValueError("focus_planes need the last surface of the chain to be saved")
+    _need_saved_last(chains, last_key, "focus_planes need")
     keys = [list(c.keys()) for c in chains]
     if any(k != keys[0] for k in keys[1:]):
         raise ValueError("batched chains must list the same surfaces (same keys, same order)")
@@ -1352,12 +1400,38 @@ def _plan_focus(states, chains, focus_planes, last_key):
             if abs(dz) > limit:
                 raise ValueError(f"focus_planes: |dz| = {abs(dz)!r} m exceeds N d^2 / wl = {limit!r} m of item {i}: "
                                  "the plane would be aliased")
-    return _FocusPlan(beams, planes)
+    return beams, planes
+
+
+# The products of the last surface -- detector images, transfer functions, zoomed windows (zoom.PsfWindow) -- share one
+# method: ``attach(dev, recs, dxs, dys)`` gives ``recs[i]`` item i's entries from what ``dev`` holds right now (the kept
+# PSFs: ``reads_psf``, or the field) on the samplings ``dxs`` / ``dys``.  ``_attach_products`` walks them.
+class _DetectorRequest:
+    """The kept PSFs rebinned onto ``detector`` (paos_detector_*): added into the accumulator of ``dev`` with ``weights``
+    (no record is touched), else every record gets its item's image.  ``origins``: every item's grid centre in the image
+    plane (None: the origin); with ``chief`` the chief rays at the last surface, which ``on_saved`` fills in there."""
+
+    reads_psf = True
+
+    def __init__(self, detector, weights, origins, chief):
+        self.detector, self.weights, self.origins, self.chief = detector, weights, origins, chief
+
+    def attach(self, dev, recs, dxs, dys):
+        if getattr(dev, "detector", None) != self.detector:
+            dev.detector_begin(self.detector)
+        placed = {} if self.origins is None else {"origins": self.origins}  # (paos_detector_*_placed)
+        if self.weights is not None:
+            dev.detector_add(dxs, dys, self.weights, **placed)
+        else:
+            for rec, image in zip(recs, dev.detector_images(dxs, dys, **placed)):
+                rec["detector"] = image
 
 
 class _OtfRequest:
     """What ``run_batch`` hands out of the transfer functions of the kept PSFs: the full arrays named in ``arrays``
     ('mtf', 'otf') and, with ``cuts``, the two MTF cuts with their frequency axes."""
+
+    reads_psf = True
 
     def __init__(self, arrays, cuts):
         self.arrays, self.cuts = tuple(arrays), bool(cuts)
@@ -1379,57 +1453,46 @@ class _OtfRequest:
                 rec["freq_x"], rec["freq_y"] = m / (dev.n * dxs[i]), m / (dev.n * dys[i])
 
 
-def _focus_stack(dev, focus, outputs, what, metrics_radii_px, power, detector, placed, otf=None, zoom=None):
-    """The planes of ``focus`` from the field ``dev`` holds behind the walk: [item][plane] dicts, planes in the caller's
-    order.  The nominal plane (dz = 0) is read first, from the untouched field; then one ``focus_begin`` and one
-    ``focus_plane`` per other plane.  ``otf`` (an ``_OtfRequest``): every plane's PSF is kept and its transfer functions
-    are attached to the plane's dict.  ``zoom`` (a ``PsfWindow``): every plane's dict gets the plane's zoomed window."""
-    beams, nb = focus.beams, dev.batch
+def _attach_products(dev, products, recs, dxs, dys, plane_power=None):
+    """Every product's entries onto ``recs``: first those that read the kept PSFs, then those that read the field.
+    ``plane_power`` (None: the nominal records -- the walk has kept the PSFs, the ledger has the powers): ``recs`` are a
+    focus plane's, whose PSFs are kept here first if a product reads them and whose power, if wanted, is summed along."""
+    from_psf = [p for p in products if p.reads_psf]
+    ticket = None
+    if plane_power is not None:
+        if from_psf and plane_power:
+            ticket = dev.psf_keep_power()
+        elif from_psf:
+            dev.psf_keep()
+        elif plane_power:
+            ticket = dev.norm2_enqueue()
+    for p in from_psf:
+        p.attach(dev, recs, dxs, dys)
+    if ticket is not None:
+        for rec, power in zip(recs, dev.norm2_fetch(ticket)):
+            rec["power"] = float(power)
+    for p in products:
+        if not p.reads_psf:
+            p.attach(dev, recs, dxs, dys)
+
+
+_WHAT = {"psf": _lib.WHAT_INTENSITY, "wfo": _lib.WHAT_FIELD, "amplitude": _lib.WHAT_AMPLITUDE, "phase": _lib.WHAT_PHASE}
+
+
+def _focus_stack(dev, focus, outputs, metrics_radii_px, power, products):
+    """The planes of ``focus`` (``_plan_focus``) from the field ``dev`` holds behind the walk: [item][plane] dicts, planes in
+    the caller's order.  The nominal plane (dz = 0) is read first, from the untouched field; then one ``focus_begin`` and
+    one ``focus_plane`` per other plane (paos_focus_plane leaves the plane in the field).  Every plane's dict gets the
+    arrays named in ``outputs``, its metrics, its power and the entries of ``products``."""
+    (beams, planes), nb = focus, dev.batch
     state = beams.state
     z0 = state[:, beams.Z].copy()
     wls, dxs, dys = (state[:, k].tolist() for k in (beams.WL, beams.DX, beams.DY))
-    stacks = [[None] * len(focus.planes) for _ in range(nb)]
-
-    def read(k, dz):
-        state[:, beams.Z] = z0 + dz
-        try:
-            wz, dtf = beams.readout()
-            zs = state[:, beams.Z].tolist()
-        finally:
-            state[:, beams.Z] = z0
-        recs = [{"dz": dz, "z": zs[i], "distancetofocus": float(dtf[i]), "wz": float(wz[i])} for i in range(nb)]
-        for i, rec in enumerate(recs):
-            for name in outputs:
-                rec[name] = dev.download(i, what[name])
-        if metrics_radii_px is not None:
-            for rec, met in zip(recs, dev.psf_metrics(metrics_radii_px)):
-                rec["metrics"] = met
-        ticket = None
-        if detector is not None or otf:
-            if power:
-                ticket = dev.psf_keep_power()
-            else:
-                dev.psf_keep()
-            if detector is not None:
-                for rec, image in zip(recs, dev.detector_images(dxs, dys, **placed)):
-                    rec["detector"] = image
-            if otf:
-                otf.attach(dev, recs, dxs, dys)
-        elif power:
-            ticket = dev.norm2_enqueue()
-        if ticket is not None:
-            for rec, p in zip(recs, dev.norm2_fetch(ticket)):
-                rec["power"] = float(p)
-        if zoom is not None:  # (paos_focus_plane leaves the plane in the field)
-            zoom.attach(dev, recs, dxs, dys)
-        for i, rec in enumerate(recs):
-            stacks[i][k] = rec
-
-    order = sorted(range(len(focus.planes)), key=lambda k: focus.planes[k] != 0.0)  # (stable: the nominal plane first)
+    stacks = [[None] * len(planes) for _ in range(nb)]
     opened = False
     try:
-        for k in order:
-            dz = focus.planes[k]
+        for k in sorted(range(len(planes)), key=lambda k: planes[k] != 0.0):  # (stable: the nominal plane first)
+            dz = planes[k]
             if dz != 0.0:
                 if not opened:
                     dev.focus_begin()
@@ -1437,7 +1500,21 @@ def _focus_stack(dev, focus, outputs, what, metrics_radii_px, power, detector, p
                 blocks = [[1.0, 1.0 / (beams.n * dxs[i]), 1.0 / (beams.n * dys[i]), (np.pi * wls[i] * dz), -1.0]
                           for i in range(nb)]  # (PilotBeam.ptp's block: wfo.py:462-472)
                 dev.focus_plane(blocks)
-            read(k, dz)
+            state[:, beams.Z] = z0 + dz
+            try:
+                wz, dtf = beams.readout()
+                zs = state[:, beams.Z].tolist()
+            finally:
+                state[:, beams.Z] = z0
+            recs = [{"dz": dz, "z": zs[i], "distancetofocus": float(dtf[i]), "wz": float(wz[i])} for i in range(nb)]
+            for i, rec in enumerate(recs):
+                for name in outputs:
+                    rec[name] = dev.download(i, _WHAT[name])
+                stacks[i][k] = rec
+            if metrics_radii_px is not None:
+                for rec, met in zip(recs, dev.psf_metrics(metrics_radii_px)):
+                    rec["metrics"] = met
+            _attach_products(dev, products, recs, dxs, dys, plane_power=bool(power))
     finally:
         if opened:
             dev.focus_end()
@@ -1532,7 +1609,7 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
         raise ValueError("one wavelength per chain is required")
     if nb == 0:
         return []
-    unknown = set(outputs) - {"psf", "wfo", "amplitude", "phase", "mtf", "otf"}
+    unknown = set(outputs) - set(_WHAT) - {"mtf", "otf"}
     if unknown:
         raise ValueError(f"unknown outputs {sorted(unknown)}")
     last_key = list(opt_chains[0].keys())[-1] if len(opt_chains[0]) else None
@@ -1542,9 +1619,7 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     if otf:
         if not sync:
             raise ValueError("'mtf' / 'otf' outputs and mtf_cuts synchronise: they cannot be combined with sync=False")
-        if last_key is None or not all(chain[last_key]["save"] for chain in opt_chains):
-            raise ValueError("'mtf' / 'otf' outputs and mtf_cuts need the last surface of the chain to be saved")
-        keep_psf = True
+        _need_saved_last(opt_chains, last_key, "'mtf' / 'otf' outputs and mtf_cuts need")
     if psf_zoom is not None:
         from .zoom import PsfWindow
 
@@ -1552,24 +1627,19 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
             raise ValueError(f"psf_zoom must be a paos_amd.PsfWindow, got {psf_zoom!r}")
         if not sync:
             raise ValueError("psf_zoom synchronises: it cannot be combined with sync=False")
-        if last_key is None or not all(chain[last_key]["save"] for chain in opt_chains):
-            raise ValueError("psf_zoom needs the last surface of the chain to be saved")
+        _need_saved_last(opt_chains, last_key, "psf_zoom needs")
         psf_zoom.check(nb, int(gridsize))
-    det_pitch = None
     if detector is not None:
-        if last_key is None or not all(chain[last_key]["save"] for chain in opt_chains):
-            raise ValueError("a detector needs the last surface of the chain to be saved")
+        _need_saved_last(opt_chains, last_key, "a detector needs")
         if detector_weights is not None:
             detector_weights = np.asarray(detector_weights, dtype=np.float64).reshape(-1)
             if detector_weights.size != nb:
                 raise ValueError("one detector weight per chain is required")
             if dev is None:
                 raise ValueError("detector_weights accumulate into `dev`: pass a DeviceFields that outlives the call")
-        keep_psf = True
-        det_pitch = [None] * nb
     elif detector_weights is not None:
         raise ValueError("detector_weights without a detector")
-    det_origin, want_chief = None, isinstance(detector_origin, str)
+    origins = None
     if detector_origin is not None:
         if detector is None:
             raise ValueError("detector_origin without a detector")
@@ -1577,11 +1647,14 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
             if detector_origin != "chief_ray":
                 raise ValueError(f"detector_origin must be None, 'chief_ray' or a (B, 2) array, got {detector_origin!r}")
         else:
-            det_origin = np.array(detector_origin, dtype=np.float64)
-            if det_origin.shape != (nb, 2):
-                raise ValueError(f"detector_origin must have shape ({nb}, 2), got {det_origin.shape}")
-            if not np.all(np.isfinite(det_origin)):
+            origins = np.array(detector_origin, dtype=np.float64)
+            if origins.shape != (nb, 2):
+                raise ValueError(f"detector_origin must have shape ({nb}, 2), got {origins.shape}")
+            if not np.all(np.isfinite(origins)):
                 raise ValueError("detector_origin must be finite")
+    det = None if detector is None else _DetectorRequest(detector, detector_weights, origins, isinstance(detector_origin, str))
+    products = [p for p in (det, otf, psf_zoom) if p]  # (in the order in which they are attached)
+    keep_psf = keep_psf or any(p.reads_psf for p in products)
     fields = _fields_of(field, nb)
     states = [_Item(pupil_diameter, wl, gridsize, zoom, f) for wl, f in zip(wavelengths, fields)]
     focus = None
@@ -1595,51 +1668,12 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     elif dev.batch != nb or dev.n != int(gridsize):
         raise ValueError("supplied DeviceFields does not match the batch")
     results = [dict() for _ in range(nb)]
-    chief = [None]  # detector_origin="chief_ray": the chief rays at the last surface
-    what = {"psf": _lib.WHAT_INTENSITY, "wfo": _lib.WHAT_FIELD, "amplitude": _lib.WHAT_AMPLITUDE,
-            "phase": _lib.WHAT_PHASE}
 
     # nobody reads an array at a saved surface: the walk may skip writing dead rows at the start and store the PSF
     # straight from the last pass (csrc/frugal_pass.h: STORE)
     # (a focus stack and a zoomed window need the field of the last surface: the ordinary walk)
     lean = _WalkState() if (not outputs and metrics_radii_px is None and focus is None and psf_zoom is None) else None
-    tickets = []  # (_Reduction, [(item index, record)], post): powers are fetched after the walk, so the
-    # host keeps planning while the GPU works (no mid-chain synchronisation) -- except when a chain
-    # saves more surfaces than the library has ticket slots: then the oldest are fetched early
-    drained = [0]
-    # The reduction a pass program left behind when it stored the PSF for good answers for every saved surface from
-    # there on (lean.final_ticket): those entries share ONE _Reduction, fetched once -- also when a mid-walk drain has
-    # already read it.  Every other ticket is a reduction of its own (a slot number alone does not say which: the
-    # library hands a slot out again as soon as it was fetched or released).
-    final_reduction = {}
-
-    def reduction_of(ticket, final=False):
-        if not final:
-            return _Reduction(dev, ticket)
-        if ticket not in final_reduction:
-            final_reduction[ticket] = _Reduction(dev, ticket)
-        return final_reduction[ticket]
-
-    def outstanding():
-        return sum(1 for e in tickets[drained[0]:] if e[0].raw is None and not e[0].released)
-
-    def drain():
-        for red, pending, post in tickets[drained[0]:]:
-            values = red.values()
-            if post is not None:
-                values = post(values)
-            for i, rec in pending:
-                rec["power"] = float(values[i])
-        drained[0] = len(tickets)
-
-    def room_in_the_ring():
-        if outstanding() >= _lib.NORM_SLOTS - 2:
-            drain()
-
-    # the power of a saved surface summed by the pass that stores its field (csrc/frugal_pass.h: pow_partial): _walk
-    # leaves the ticket here when the surface's field is exactly what its pass program stored
-    power_state = ({"ticket": None, "post": None, "used": False, "before": room_in_the_ring}
-                   if (power and POWER_ON_STORE) else None)
+    ledger = _PowerLedger(dev)
 
     def on_saved(key, items, plans, wfe):
         pending = []
@@ -1649,7 +1683,7 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
             rec = dict(plan["scalars"])
             rec["aperture"] = plan["aperture"][0] if plan["aperture"] else None
             for name in outputs:
-                rec[name] = dev.download(i, what[name])
+                rec[name] = dev.download(i, _WHAT[name])
             rec["_plan"] = plan
             results[i][item["num"]] = rec
             pending.append((i, rec))
@@ -1658,46 +1692,32 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
             for i, rec in pending:
                 rec["metrics"] = met[i]
         keep = keep_psf and key == last_key
-        if det_pitch is not None and key == last_key:
-            for i, plan in enumerate(plans):
-                det_pitch[i] = (plan["scalars"]["dx"], plan["scalars"]["dy"])
-            if want_chief:
-                chief[0] = plans.chief_ray
+        if det is not None and det.chief and key == last_key:
+            det.origins = plans.chief_ray
         # the last pass has stored |u|^2 and enqueued its sum -- for this surface, or for good (inert surfaces behind it)
         fused = (lean.psf_ticket if lean.psf_ticket is not None else lean.final_ticket) if lean is not None else None
-        rows = lean.rows if lean is not None else None
-        if power:
-            if outstanding() >= _lib.NORM_SLOTS - 1 and fused is None:
-                drain()  # the ticket ring of the library is about to fill: fetch what is pending
-            # the saved last surface of a run that keeps its PSFs: |u|^2 written and summed in one sweep
+        if not power:
             if fused is not None:
-                tickets.append((reduction_of(fused, final=True), pending, None))
-            elif power_state is not None and power_state["ticket"] is not None and not keep:
-                tickets.append((reduction_of(power_state["ticket"]), pending, power_state.get("post")))
-                power_state["used"] = True
+                ledger.final(fused).release()  # (once, however many surfaces it stands for)
             elif keep:
-                if power_state is not None and power_state["ticket"] is not None:  # (the kept PSF brings its own sum)
-                    dev.norm2_release(power_state["ticket"])
-                    power_state["used"] = True
-                tickets.append((reduction_of(dev.psf_keep_power()), pending, None))
-            elif lean is not None and lean.deferred_start is not None:
-                # the start field is launched at the next surface (_walk: launch_start), which enqueues this sum and names its slot
-                red = lean.deferred_start["power"] = _Reduction(dev, -1)
-                tickets.append((red, pending, None))
-            else:
-                like = lean.same_as if lean is not None else None
-                cols = lean.cols if lean is not None else None
-                if rows is not None and cols is not None:
-                    tickets.append((reduction_of(dev.norm2_enqueue(rows, same_as=like, live_cols=cols)), pending, None))
-                elif rows is not None and like is not None:
-                    tickets.append((reduction_of(dev.norm2_enqueue(rows, same_as=like)), pending, None))
-                else:
-                    tickets.append((reduction_of(dev.norm2_enqueue(rows) if rows is not None else dev.norm2_enqueue()),
-                                    pending, None))
+                dev.psf_keep()
         elif fused is not None:
-            reduction_of(fused, final=True).release()  # (once, however many surfaces it stands for)
-        elif keep:
-            dev.psf_keep()
+            ledger.record(fused, pending, final=True)
+        else:
+            ledger.make_room(spare=1)
+            if ledger.offered is not None and not keep:
+                ledger.claim(pending)  # the pass that stored this surface's field has summed it
+            elif keep:
+                # the saved last surface of a run that keeps its PSFs: |u|^2 written and summed in one sweep
+                ledger.decline()  # (the kept PSF brings its own sum)
+                ledger.record(dev.psf_keep_power(), pending)
+            elif lean is not None and lean.deferred_start is not None:
+                # the start field is launched at the next surface (_walk: _launch_start), which enqueues this sum and names its slot
+                lean.deferred_start["power"] = ledger.record(-1, pending)
+            elif lean is not None:
+                ledger.record(_enqueue_power(dev, lean.rows, lean.same_as, lean.cols), pending)
+            else:
+                ledger.record(dev.norm2_enqueue(), pending)
 
     # The walk allocates a few thousand small containers per surface of a large batch (plans, blocks, handles); a
     # generation-2 pass of the cycle collector in the middle of it costs as much as planning several surfaces (round 5:
@@ -1707,40 +1727,19 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     gc.disable()
     try:
         _walk(dev, states, list(opt_chains), on_saved, stats=stats, fresh=1.0 + 0.0j, lean=lean,
-              psf_at=last_key if (keep_psf and lean is not None) else None, power_state=power_state)
-        if detector is not None:  # the kept PSFs of the last surface onto the detector (include/paos_hip.h)
-            dxs = [p[0] for p in det_pitch]
-            dys = [p[1] for p in det_pitch]
-            if getattr(dev, "detector", None) != detector:
-                dev.detector_begin(detector)
-            origins = chief[0] if want_chief else det_origin
-            placed = {} if origins is None else {"origins": origins}  # (paos_detector_*_placed)
-            if detector_weights is not None:
-                dev.detector_add(dxs, dys, detector_weights, **placed)
-            else:
-                images = dev.detector_images(dxs, dys, **placed)
-                for i in range(nb):
-                    results[i][opt_chains[i][last_key]["num"]]["detector"] = images[i]
-        if otf:  # (before a focus stack, whose planes store their own PSFs)
+              psf_at=last_key if (keep_psf and lean is not None) else None,
+              ledger=ledger if (power and POWER_ON_STORE) else None)
+        if products or focus is not None:
             recs = [results[i][opt_chains[i][last_key]["num"]] for i in range(nb)]
-            otf.attach(dev, recs, [rec["dx"] for rec in recs], [rec["dy"] for rec in recs])
-        if psf_zoom is not None:  # (before a focus stack, which overwrites the field)
-            recs = [results[i][opt_chains[i][last_key]["num"]] for i in range(nb)]
-            psf_zoom.attach(dev, recs, [rec["dx"] for rec in recs], [rec["dy"] for rec in recs])
-        if focus is not None:
-            placed = {}
-            if detector is not None and (chief[0] if want_chief else det_origin) is not None:
-                placed = {"origins": chief[0] if want_chief else det_origin}
-            stacks = _focus_stack(dev, focus, outputs, what, metrics_radii_px, power, detector, placed, otf, psf_zoom)
-            for i in range(nb):
-                results[i][opt_chains[i][last_key]["num"]]["focus"] = stacks[i]
+            # (before a focus stack, whose planes store their own PSFs and overwrite the field)
+            _attach_products(dev, products, recs, [rec["dx"] for rec in recs], [rec["dy"] for rec in recs])
+            if focus is not None:
+                for rec, stack in zip(recs, _focus_stack(dev, focus, outputs, metrics_radii_px, power, products)):
+                    rec["focus"] = stack
         if sync or own:
-            drain()
-        else:  # caller synchronises later: hand out handles to the reductions still outstanding (nothing waits here)
-            for red, pending, post in tickets[drained[0]:]:
-                handle = PowerTicket(red, post)
-                for i, rec in pending:
-                    rec["power_ticket"] = handle
+            ledger.drain()
+        else:  # the caller synchronises later
+            ledger.hand_out()
     finally:
         if gc_was_on:
             gc.enable()
@@ -1749,6 +1748,5 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     for res in results:
         for rec in res.values():
             plan = rec.pop("_plan")
-            rec["ABCDt"] = plan["ABCDt"]
-            rec["ABCDs"] = plan["ABCDs"]
+            rec["ABCDt"], rec["ABCDs"] = plan["ABCDt"], plan["ABCDs"]
     return results

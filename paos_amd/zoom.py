@@ -16,6 +16,8 @@ class PsfWindow:
     centroid, the grid centre when the power is zero.  ``field``: also hand out the complex window (``'wfo_zoom'``).
     """
 
+    reads_psf = False  # (``attach`` reads the field, not the kept PSFs: run._attach_products)
+
     def __init__(self, size, oversample, centre=None, field=False):
         _lib.zoom_check(size, oversample, 1 << 30)  # (the rule that needs the grid is checked by run_batch)
         if isinstance(centre, str):
