@@ -136,7 +136,7 @@ struct FrugalArgs {
   // launch runs as well (same axis, same lines; their item records follow this pass's in `items`: [2 or 3][batch])
   int fuse = 0;
   // host only (round 5): a single table pass that moves few bytes -- every item loads and stores at most half of its positions --
-  // runs on the one-line workgroups of the fused launches (paos_hip.hip: frugal_launch, ONE)
+  // runs on the one-line workgroups of the fused launches (frugal_launch.h: frugal_launch, ONE)
   int one_line = 0;
 };
 #if PAOS_STAMPS
@@ -581,7 +581,7 @@ __device__ __forceinline__ void frugal_slot(cx<T>* v, const FrugalSlot& sl, cons
 // items[item_base], with `k` phases, along `axis`.
 struct PhaseSlotDesc { int item_base, mid, k, axis; };
 struct PhaseTableArgs {
-  const FrugalItem* items;     // the staged records of every launch the tables are for (paos_hip.hip: stage_groups)
+  const FrugalItem* items;     // the staged records of every launch the tables are for (passes.hip: stage_groups)
   const cx<double>* tw;        // the context's twiddle table for n
   const PhaseSlotDesc* desc;   // [gridDim.z]
   int n;

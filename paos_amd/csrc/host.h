@@ -1,0 +1,364 @@
+// host.h -- what the translation units of libpaoship share (internal; the C ABI is include/paos_hip.h).
+//
+// The host side of the library is split by what it launches: context.hip (contexts, the parameter arena, errors,
+// the launch timer), pass_plan.hip and passes.hip (pass programs), generic_pass.hip and frugal_<family>.hip (the pass
+// kernels), paos_hip.hip (the pointwise entry points: every kernel of pointwise.h) and the products: focus_otf.hip, zoom.hip,
+// detector.hip.  Here: the build-time layout, the context, the error and launch helpers, and the declarations of the
+// functions that cross unit boundaries.  Whatever is not declared here lives in an anonymous namespace of its unit.
+#pragma once
+#include "../../include/paos_hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "frugal_pass.h"
+
+using namespace paos;
+
+// ---- build-time layout choice -------------------------------------------------------
+// A field is stored as blocks of 4 rows x 2 columns (128 B of complex128, 64 B of complex64),
+// blocks row-major, so whole or half cache lines are the unit of work for the row pass (2 or 4
+// rows per workgroup) and for the column pass (2 columns per workgroup) alike (DESIGN.md
+// section 2).  PAD_BLOCKS extra blocks per block row de-tune the power-of-two stride of
+// the column pass (measured: 3.5 -> 4.8 TB/s at 4096^2, profiles/r01_fftbench_v2_pitchpad.txt).
+#ifndef PAOS_BR
+#define PAOS_BR 4
+#endif
+#ifndef PAOS_PAD_BLOCKS
+#define PAOS_PAD_BLOCKS 3
+#endif
+inline constexpr int BR = PAOS_BR;  // complex128 and the base case of complex64
+// complex64 at N >= 2048 (where the frugal kernels serve it): blocks of 8 rows x 2 columns = 128 B like a complex128
+// block, so that column tiles own whole lines (round 3; profiles/r02_fftbench_c64_8row_blocks_experiment.txt).  Below
+// 2048 the generic kernels keep 4 x 2 (a column tile needs N / 16 >= block height threads per line).
+#ifndef PAOS_F32_BR
+#define PAOS_F32_BR 8
+#endif
+template <typename T, int N>
+constexpr int block_rows() { return (sizeof(T) == 4 && N >= 2048) ? PAOS_F32_BR : PAOS_BR; }
+// one float launch for either block height: FBR is the compile-time block height inside the statement
+#define F32_BR_SWITCH(c, ...)                                                            \
+  do {                                                                                   \
+    if ((c)->br == PAOS_F32_BR) { constexpr int FBR = PAOS_F32_BR; __VA_ARGS__; }        \
+    else { constexpr int FBR = PAOS_BR; __VA_ARGS__; }                                   \
+  } while (0)
+inline constexpr int kNormSlots = PAOS_NORM_SLOTS;  // outstanding paos_norm2_enqueue results
+template <typename T>
+struct Lay {
+  // 2 columns for both types: a block is 128 B of complex128 or 64 B of complex64.  (4 columns
+  // of complex64 would fill the line but make the column tile 4 lines = 1024 threads, which
+  // spills; measured 126 wavefronts/s vs the 2-column shape below.)
+  static constexpr int BC = 2;
+};
+
+// Parameter arena: kArenaSlabs slabs of `cap` doubles each (pinned host mirror + device), filled one after the other.
+// Round 5: a slab is reused only after the work that read it has run -- told by an EVENT recorded one slab switch after it
+// was left (by then every launch that reads it has been enqueued: a call's pushes and its launches never span more than
+// two slabs) -- instead of by a hipStreamSynchronize at every wrap of one ring: at 512 wavefronts per step the ring
+// wrapped every second step, and each wrap made the host wait for the GPU to drain (1024^2: 33 ms per step where the GPU
+// needs 25 and the host 18).  With four slabs the host may run two to three steps ahead and no further.
+constexpr int kArenaSlabs = 4;
+struct Arena {
+  double* host = nullptr;  // pinned, kArenaSlabs * cap doubles
+  double* dev = nullptr;
+  size_t cap = 0, head = 0;  // doubles per slab / fill of the current slab
+  int cur = 0;               // slab being filled
+  int left = -1;             // the slab left at the last switch: its fence is recorded at the NEXT switch
+  hipEvent_t fence[kArenaSlabs] = {};
+  bool fenced[kArenaSlabs] = {};  // fence[k] has been recorded since slab k was last filled
+  bool used[kArenaSlabs] = {};
+};
+
+struct paos_ctx {
+  int device = 0, n = 0, batch = 0, precision = 0;
+  int br = PAOS_BR;  // block height of this context's layout (block_rows<T, N>())
+  unsigned pitch = 0, item_stride = 0;
+  hipStream_t stream = nullptr;
+  double* psf = nullptr;  // batch x item_stride intensities kept on the device, blocked like the field (paos_psf_keep)
+  // a through-focus stack (paos_focus_begin .. paos_focus_end): the forward 2-D spectrum of every item's field, complex<T>
+  // of the context's precision in the field's own layout; allocated by the first paos_focus_begin
+  void* focus_spec = nullptr;
+  bool focus_open = false;
+  // transfer functions (paos_otf_compute): the spectra of the kept PSFs, complex<T> of the context's precision in the
+  // field's own layout (columns 0 .. N/2 hold the spectrum, otf_pass.h); allocated by the first paos_otf_compute.
+  // otf_valid: the buffer was computed from what the PSF buffer holds NOW -- cleared by everything that stores a PSF
+  void* otf_spec = nullptr;
+  bool otf_computed = false, otf_valid = false;
+  double* otf_cuts = nullptr;  // [batch][2][N/2 + 1], allocated by the first paos_otf_cuts
+  // zoomed windows (paos_zoom_compute): the column-contracted field T [batch][N][M] complex128, the windows [batch][M][M]
+  // (intensities; the complex field when asked for) and the phase tables of the fractional centres seen so far -- slot k
+  // of zoom_tabs holds the [s][N] table of zoom_fracs[k], zoom_carry[k] its carries (all for oversampling zoom_s)
+  cx<double>* zoom_t = nullptr;
+  double* zoom_psf = nullptr;
+  cx<double>* zoom_field = nullptr;
+  int zoom_m = 0;  // the window size the three buffers were allocated for
+  bool zoom_done = false, zoom_has_field = false;
+  double* zoom_tabs = nullptr;
+  int zoom_s = 0, zoom_cap = 0;
+  std::vector<double> zoom_fracs;
+  std::vector<std::vector<int>> zoom_carry;
+  double* map_dev = nullptr;      // one n x n phase map kept on the device (paos_phase_map_items) and the key it was uploaded under
+  unsigned long long map_key = 0;
+  // (round 5) the power sums of the last start, kept with everything they depend on (shape, constant, aperture records,
+  // stop flags): the entrance pupil of a wavelength sweep or a Monte-Carlo study is the same step after step, and the sums
+  // are a pure function of those -- the next start with the same key copies them instead of evaluating the exact pixel
+  // overlaps again (start_power_kernel + norm2_final_kernel: 0.08 ms of a 14.6 ms SYN20 step).  PAOS_START_POWER_MEMO=0: never.
+  std::vector<double> start_key;
+  double* start_norm2 = nullptr;  // [batch]
+  cx<double>* psd_scratch = nullptr;  // one item in the field's layout: the spectrum of a PSD screen (paos_psd_screen)
+  int* psd_bad = nullptr;
+  double* psf_partial = nullptr;  // per-workgroup sums of a pass that stores the PSF (paos_run_program: final_intensity)
+  int psf_nparts = 0;
+  double* pow_partial = nullptr;  // per-workgroup sums of |u|^2 of a pass that stores the FIELD (final_intensity = 2)
+  int pow_nparts = 0;
+  // [batch] factors every frugal pass multiplies into the scale of its middle slot (FrugalArgs::dyn_scale): ones, except
+  // between paos_stop_defer_last_power and the pass (or settle_scale) that applies the stop's 1 / sqrt(power)
+  cx<double>* ptab = nullptr;  // [ptab_slots][batch][n] phase factors by position: a table per operator slot of the launches of the
+  int ptab_slots = 0;          // program about to run (FrugalSlot::table; stage_groups)
+  double* dyn_scale = nullptr;
+  bool dyn_pending = false;
+  // c->norm2 holds sum |u|^2 of the field exactly as it is stored: set by a pass program whose last pass summed it on the
+  // way out (paos_run_program, final_intensity = 2), cleared by every entry point that reads or rewrites the field or
+  // reduces into c->norm2 (SETTLE_SCALE / DROP_SCALE sit at the top of all of them).  paos_stop_scale_last_power and
+  // paos_stop_defer_last_power trust c->norm2 only while it is set and run paos_make_stop otherwise.
+  bool norm2_of_field = false;
+  // What the PSF buffer (and psf_partial) is known to hold after a pass stored it: for item i the lines along
+  // psf_zero_axis outside [psf_zero_lo[i], psf_zero_hi[i]) are zero (their per-workgroup sums too).  The next
+  // PSF-storing pass with the same live lines need not write those zeros again; -1 = nothing known.
+  int psf_zero_axis = -1;
+  std::vector<double> psf_zero_lo, psf_zero_hi;
+  // detector pixel grid of paos_detector_begin (plain types: the struct is the same in every translation unit)
+  bool det_set = false;
+  int det_nx = 0, det_ny = 0;
+  double det_geom[4] = {};         // pitch_x, pitch_y, xc, yc
+  double* det_img = nullptr;       // [ny][nx] fp64 accumulator
+  double* det_rows = nullptr;      // row-contraction scratch of one chunk of items (allocated on first use, grown)
+  size_t det_rows_bytes = 0;
+  double* det_out = nullptr;       // per-item images of one chunk (paos_detector_images)
+  size_t det_out_bytes = 0;
+  void* bounce[2] = {nullptr, nullptr};  // pinned host buffers for device -> pageable host copies
+  hipEvent_t bounce_ev[2] = {nullptr, nullptr};
+  void* field = nullptr;
+  void* tw = nullptr;
+  void* staging = nullptr;  // n*n*16 bytes, row-major
+  cx<double>* tables = nullptr;  // kMaxTables x batch x 2n separable phase factors
+  double* mask = nullptr;        // batch x item_stride aperture weights (allocated on first use)
+  double* metric_partial = nullptr;  // psf metrics scratch
+  double* metric_out = nullptr;
+  double* metric_host = nullptr;     // pinned
+  // Line records of apertures riding on frugal passes: a few rendered sets are kept, keyed by everything the
+  // renderer reads (the aperture's two parameter block sets, the pass axis, which items share records), so that a
+  // chain whose relays repeat one aperture -- and the next wavefront batch through the same optics (a Monte-Carlo
+  // study, a benchmark step) -- find their records instead of rendering them again (round 3: 6 renderings of
+  // 0.3 ms per SYN20 step -> 0 in steady state).
+  struct MaskSet {
+    MaskLine* lines = nullptr;  // batch x n
+    double* vals = nullptr;     // batch x n x 2 kMaskW partial weights
+    std::vector<double> key;    // empty: holds nothing valid
+    unsigned long long used = 0;
+    int line_lo = 0, line_hi = 0;  // the lines whose records were rendered (the others hold whatever was there before)
+  };
+  static constexpr int kMaskSets = 8;  // (SYN20: five relay apertures whose pixel radii differ in the last digits + the field stop)
+  MaskSet mask_sets[kMaskSets];
+  unsigned long long mask_clock = 0;
+  unsigned long long mask_hits = 0, mask_rendered = 0;  // paos_record_set_stats
+  // experiment (tools/two_streams.py): extra dynamic LDS per pass workgroup of THIS context (PAOS_LDS_PAD when the
+  // context is created): 6 KiB make two of its workgroups too big for one CU but leave room for one of another
+  // context's -- two contexts then share every CU one workgroup each (measured: -14 %, profiles/r04_membench6_mixed_kinds.txt)
+  size_t lds_pad = 0;
+  int* mask_overflow = nullptr;    // device counter: partial runs that did not fit (must stay 0)
+  double* partial = nullptr;
+  double* norm2 = nullptr;
+  double* norm2_host = nullptr;  // pinned, kNormSlots x batch
+  bool prune = true;  // skip tiles / loads of lines an aperture has zeroed (paos_ctx_set_pruning)
+  int norm_slot = 0;
+  bool norm_busy[64] = {};       // ticket handed out and not fetched yet (kNormSlots entries)
+  int nparts = 0;
+  Arena arena;
+  std::string err;
+  // optional per-kernel-class timing with HIP events on the context's stream
+  int prof_kind = -1;
+  std::vector<hipEvent_t> prof_events;  // start/stop pairs
+  std::vector<int> prof_tags;           // per pair: 1 = the launch skipped dead tiles / loads (pruned)
+  int prof_next_tag = 0;
+  double prof_next_bytes = 0.0;         // bytes the planner has the next timed launch load + store (its algorithmic bytes)
+  std::vector<double> prof_bytes;       // per pair, like prof_tags
+  double prof_next_lines = 0.0;         // 1-D line transforms the next timed launch runs (live lines x transforms that are on, over the batch)
+  std::vector<double> prof_lines;       // per pair, like prof_tags
+  size_t prof_used = 0;
+};
+
+// Everything declared from here on is internal to the library: none of it is exported.
+#pragma GCC visibility push(hidden)
+
+// ---- errors (context.hip): the text goes to the context and, for a call without one, to the calling thread -------
+int fail(paos_ctx* c, int code, const std::string& msg);
+
+#define HIPCHK(c, call)                                                                     \
+  do {                                                                                      \
+    hipError_t e_ = (call);                                                                 \
+    if (e_ != hipSuccess)                                                                   \
+      return fail((c), PAOS_EHIP,                                                           \
+                  std::string(#call) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" +   \
+                      std::to_string(__LINE__) + ")");                                      \
+  } while (0)
+
+inline size_t elem_bytes(const paos_ctx* c) { return c->precision == PAOS_F64 ? 16 : 8; }
+
+// A switch of the environment: is the first character of `name` `ch`?  Flags that are read once keep the answer in a
+// static of the one function that asks; the flags that tests switch (mask_render_mode, mask_rect_blocks,
+// PAOS_FUSE_PAIRS, PAOS_STAGE_PROGRAM) ask at every call.
+inline bool env_is(const char* name, char ch) {
+  const char* e = getenv(name);
+  return e && e[0] == ch;
+}
+
+// ---- FFT launch geometry per grid size ----------------------------------------------
+// Row pass: LINES = BR rows per tile; column pass: LINES = BC columns per tile.
+// E elements per thread; TILES tiles per workgroup keep small grids at >= 128 threads.
+template <typename T, int N>
+struct FftCfg {
+  static constexpr int BC = Lay<T>::BC;
+  static constexpr int BR = block_rows<T, N>();
+  // 16 points per thread.  (32 points of complex64 fill the same 64 data VGPRs, but the
+  // radix-32 butterflies spill: 256 VGPRs + 60-70 AGPRs measured, so E stays 16 for both types.)
+  static constexpr int E = 16;
+  // rows of a block row handled by one row tile: all four, except at N = 4096 where four
+  // lines of 4096 points do not fit the register file of a spill-free workgroup
+  static constexpr int ROW_LINES = (N >= 2048) ? PAOS_BR / 2 : PAOS_BR;  // 256-thread tiles at 2048 measured +29 %
+  // the frugal kernels' row tile: half a block row -- 2 rows of complex128, 4 rows of complex64 at N >= 2048 (1024
+  // threads at <= 64 VGPRs at 4096: two workgroups per CU either way)
+  static constexpr int FR_ROW_LINES = (N >= 2048) ? BR / 2 : BR;
+  static constexpr int COL_LINES = BC;
+  static constexpr int ROW_THREADS = ROW_LINES * N / E, COL_THREADS = COL_LINES * N / E;
+  static constexpr int ROW_TILES = (ROW_THREADS >= 128) ? 1 : 128 / ROW_THREADS;
+  static constexpr int COL_TILES = (COL_THREADS >= 128) ? 1 : 128 / COL_THREADS;
+  // Exchange whole complex numbers through LDS (two barriers per exchange) whenever the
+  // tile fits; otherwise real and imaginary parts take turns in half the space.  Register
+  // pressure (~230 VGPRs) already limits these kernels to 8 waves per CU, so using up to
+  // 144 KiB of the 160 KiB LDS costs no occupancy (measured +3..7 %, profiles/r01_fftbench_v4).
+  static constexpr bool ROW_SPLIT = (size_t)ROW_LINES * ROW_TILES * line_lds_bytes<T, N, false>() > 144 * 1024;
+  static constexpr bool COL_SPLIT = (size_t)COL_LINES * COL_TILES * line_lds_bytes<T, N, false>() > 144 * 1024;
+  static constexpr int MINW = 1;
+};
+
+// ---- context.hip ---------------------------------------------------------------------------------------------
+// the parameter arena: make room for `total` doubles that must all stay live / copy `count` doubles, *dev: where they are
+int arena_reserve(paos_ctx* c, size_t total);
+int arena_push(paos_ctx* c, const double* src, size_t count, const double** dev);
+int copy_to_host(paos_ctx* c, void* host, const void* dev, size_t bytes);  // device -> pageable host; synchronises
+int next_norm_slot(paos_ctx* c);                                           // the next free slot of the power-ticket ring
+int check_mask_overflow(paos_ctx* c);  // after a synchronisation: did an aperture's partial run overflow its line records?
+int check_rows(paos_ctx* c, const double* rows);                           // [batch][2] windows: 0 <= lo <= hi <= n
+std::vector<double> rounded_cols(const paos_ctx* c, const double* cols);   // column windows in whole block heights
+int opt_in_lds(paos_ctx* c, const void* kern, size_t lds);  // more than 64 KiB of dynamic LDS: once per device and kernel
+bool timed_launch_begin(paos_ctx* c, int kind);             // the launch timer (paos_profile_begin)
+hipError_t timed_launch_end(paos_ctx* c, int tag);
+
+// Opt in to `lds_opt_in` bytes of dynamic LDS (0: the kernel needs no opt-in), arm the launch timer, launch, check, stop
+// the timer under `tag`.  The caller has set c->prof_next_bytes / prof_next_lines.  TIMED_LAUNCH(c, kern, ...): a failed
+// launch is reported with the launcher's file and line, like every HIPCHK.
+int launch_failed(paos_ctx* c, const char* call, hipError_t e, const char* file, int line);
+#define TIMED_LAUNCH(c, ...) timed_launch(__FILE__, __LINE__, (c), __VA_ARGS__)
+template <typename Kern, typename... Args>
+int timed_launch(const char* file, int line, paos_ctx* c, Kern kern, dim3 grid, dim3 block, size_t lds, size_t lds_opt_in, int kind,
+                 int tag, Args... args) {
+  if (lds_opt_in) {
+    int rc = opt_in_lds(c, (const void*)kern, lds_opt_in);
+    if (rc) return rc;
+  }
+  const bool timed = timed_launch_begin(c, kind);
+  hipLaunchKernelGGL(kern, grid, block, lds, c->stream, args...);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return launch_failed(c, "hipGetLastError()", e, file, line);
+  if (timed && (e = timed_launch_end(c, tag)) != hipSuccess) return launch_failed(c, "timed_launch_end(c, tag)", e, file, line);
+  return PAOS_OK;
+}
+// the pass kernels on the generic tile shapes (FftCfg) opt in above the 48 KiB every kernel may use
+inline size_t generic_lds_opt_in(size_t lds) { return lds > 48 * 1024 ? lds : 0; }
+
+// f(std::integral_constant<int, N>) for the context's grid size N: the one place that knows the sizes of FftCfg
+template <typename F>
+int dispatch_n(paos_ctx* c, F&& f) {
+  switch (c->n) {
+#define PAOS_N_CASE(N) case N: return f(std::integral_constant<int, N>{})
+    PAOS_N_CASE(64);
+    PAOS_N_CASE(128);
+    PAOS_N_CASE(256);
+    PAOS_N_CASE(512);
+    PAOS_N_CASE(1024);
+    PAOS_N_CASE(2048);
+    PAOS_N_CASE(4096);
+#undef PAOS_N_CASE
+  }
+  return fail(c, PAOS_EUNSUPPORTED, "grid size must be a power of two in 64..4096");
+}
+
+// ---- pass_plan.hip: a pass of a program lowered for the frugal kernels, and the pruning of dead lines across a program ----
+// One pass of a program, lowered for the frugal kernels before anything is launched, so that the
+// planner can look ahead.
+struct LoweredPass {
+  bool ok = false;
+  std::vector<FrugalItem> items;
+  int kpre = 0, kmid = 0, nfft = 1, mask_block = -1, mask_slot = -1;
+  std::vector<double> mask_shared;  // [batch] 1: the item reads the line records of an earlier, identical item
+  std::vector<int> mask_rep;        // [batch] item whose records this item reads (-1: none)
+  int mask_set = -1;                // which of the context's record sets this pass reads
+  int mask_shapes = 3;              // bit s: some item's aperture has shape s (0 ellipse, 1 rectangle) and renders its own records
+  int mask_lo = 0, mask_hi = 0;     // lines whose records this pass reads (run_passes_impl, behind the pruning plan)
+  bool mask_render = false;         // ... and whether it has to be rendered first
+};
+
+bool lower_frugal(const paos_ctx* c, const paos_pass& p, const double* blocks /*host*/, LoweredPass& lp);
+void plan_pruning(const paos_ctx* c, const paos_pass* passes, int n_passes, const double* blocks, std::vector<LoweredPass>& low,
+                  const double* entry_rows, bool entry_stale, const double* entry_cols);
+
+// ---- passes.hip ----------------------------------------------------------------------------------------------------
+// final_mode (with final_ticket): 1 = the PSF instead of the field, 2 = the field as usual plus the ticket of its power
+int run_passes(paos_ctx* c, const paos_pass* passes, int n_passes, const double* blocks, int n_blocks,
+               const double* entry_rows = nullptr, bool entry_stale = false, int* final_ticket = nullptr, int final_mode = 1,
+               const double* entry_cols = nullptr);
+int mask_render_mode();    // how ellipse / rectangle line records are rendered (read per call: tests switch them)
+bool mask_rect_blocks();
+
+// ---- generic_pass.hip: one pass on the generic kernel (fft_kernels.h), any grid size; feat != 0: the build with the
+// optional operators (phase tables, aperture weight maps) ----
+int generic_pass(paos_ctx* c, int axis, const PassArgs& a, int feat);
+
+// ---- frugal_<family>.hip: the pass-kernel shapes of one (type, N) family behind one ordinary function each ----
+int paos_frugal_d1024(paos_ctx* c, const FrugalArgs& a, int axis, int kpre, int kmid, int nfft);
+int paos_frugal_d2048(paos_ctx* c, const FrugalArgs& a, int axis, int kpre, int kmid, int nfft);
+int paos_frugal_d4096(paos_ctx* c, const FrugalArgs& a, int axis, int kpre, int kmid, int nfft);
+int paos_frugal_f2048(paos_ctx* c, const FrugalArgs& a, int axis, int kpre, int kmid, int nfft);
+int paos_frugal_f4096(paos_ctx* c, const FrugalArgs& a, int axis, int kpre, int kmid, int nfft);
+
+// ---- paos_hip.hip: the one unit that includes pointwise.h (its non-template kernels can be compiled once only), so
+// whatever another unit needs of that header's kernels is launched through these ----
+// the deferred stop scale (paos_stop_defer_last_power): apply it to the field now (unless that is about to be
+// overwritten) / the first pass of a program has taken it along: ones again
+int settle_scale(paos_ctx* c, bool field_is_overwritten = false);
+int dyn_scale_reset(paos_ctx* c);
+int zero_outside_rows(paos_ctx* c, const double* live_rows);
+int zero_outside_box(paos_ctx* c, const double* live_rows, const double* live_cols);
+int psf_power_ticket(paos_ctx* c, const double* partial, int nparts, int* ticket, const double* source = nullptr);
+int psf_keep_power_impl(paos_ctx* c, int* ticket);
+// aperture line records (pointwise.h: MaskJob): render the lines [line0, line_end) along `axis` of the aperture whose two
+// parameter block sets start at `params` into record set `set`; at most kMaskRenders of them, in one launch per shape
+struct MaskRender {
+  const double *params, *shared;
+  int set, axis, line0, line_end, shapes;
+};
+constexpr int kMaskRenders = 8;
+int render_mask_records(paos_ctx* c, const MaskRender* jobs, int count);
+// the operators of a pass on the generic kernels: the weight map of its aperture into c->mask / a transform-free pass
+int render_mask_weights(paos_ctx* c, const double* ap);
+int pointwise_pass(paos_ctx* c, const PassArgs& a);
+
+#define SETTLE_SCALE(c) do { if (c) { (c)->norm2_of_field = false; if ((c)->dyn_pending) { int rc_ = settle_scale(c); if (rc_) return rc_; } } } while (0)
+#define DROP_SCALE(c) do { if (c) { (c)->norm2_of_field = false; if ((c)->dyn_pending) { int rc_ = settle_scale(c, true); if (rc_) return rc_; } } } while (0)
+
+#pragma GCC visibility pop

@@ -896,7 +896,7 @@ _FILLED_MAPS = {}  # id(map) -> (map, its zero-filled contiguous copy: what cros
 
 def _queue_apertures(comp, plans):
     """Apertures as pass operators (their weight maps are rendered right before the pass
-    they ride on, csrc/paos_hip.hip: launch_one_pass)."""
+    they ride on, csrc/passes.hip: launch_one_pass)."""
     if getattr(plans, "ap", None) is not None:
         comp.aperture(plans.ap.blocks())
         return

@@ -75,7 +75,7 @@ class ModelDevice:
         # rows outside [lo, hi) are not read (they may hold stale data: NaN in this model)
         return self._new_ticket(np.array([np.sum(np.abs(u[int(lo):int(hi)]) ** 2) for u, (lo, hi) in zip(self.u, live_rows)]))
 
-    # The library's ticket ring (paos_hip.hip: next_norm_slot): NORM_SLOTS slots, the next FREE one is handed out, a slot
+    # The library's ticket ring (context.hip: next_norm_slot): NORM_SLOTS slots, the next FREE one is handed out, a slot
     # is free again as soon as it was fetched or released -- so a slot NUMBER does not identify a reduction, and
     # fetching one twice is an error (or, worse, somebody else's value).  The model is as strict.
     def _new_ticket(self, values):
@@ -353,7 +353,7 @@ class ModelDevice:
             return ticket
         return None
 
-    # one-operator programs, as csrc/paos_hip.hip builds them
+    # one-operator programs, as csrc/passes.hip builds them
     def _single(self, blocks, inverse, kind):
         from paos_amd.passes import PassCompiler
 

@@ -63,6 +63,59 @@ def test_context_creation_fails_loudly_without_gpu():
         WFO(1.0, 1e-6, 64, 4)
 
 
+def test_context_less_error_text_is_one_per_thread_whichever_unit_fails():
+    """The library is several translation units, and a failure without a context leaves its text where
+    paos_last_error(NULL) reads it -- one text per thread, whichever unit raised it.  One entry point of every unit that
+    has one is called with a NULL context (nothing touches a device); between two of them a call with a message of its
+    own changes the text, so a unit that kept a text of its own would be caught reading the stale one.  Expected texts:
+    what the library has always said -- `null context`, except for a pass program, whose one check of all its arguments
+    says `bad pass program`."""
+    import threading
+
+    from paos_amd import _lib
+
+    lib = _lib.load()
+    EINVAL = 1  # include/paos_hip.h
+    calls = [  # (unit, call, text)
+        ("context.hip", lambda: lib.paos_sync(None), "null context"),
+        ("passes.hip", lambda: lib.paos_run_passes(None, None, 0, None, 0), "bad pass program"),
+        ("paos_hip.hip", lambda: lib.paos_psf_keep(None), "null context"),
+        ("focus_otf.hip", lambda: lib.paos_focus_begin(None), "null context"),
+        ("focus_otf.hip", lambda: lib.paos_otf_compute(None), "null context"),
+        ("zoom.hip", lambda: lib.paos_zoom_compute(None, 16, 1, None, 0), "null context"),
+        ("detector.hip", lambda: lib.paos_detector_add(None, None), "null context"),
+    ]
+
+    def last():
+        return lib.paos_last_error(None).decode()
+
+    def walk():
+        for unit, call, text in calls:
+            assert lib.paos_zoom_weights(3, 1, 0.0, None, None) == EINVAL  # (n must be even)
+            assert last().startswith("paos_zoom_weights: n must be even"), (unit, last())
+            assert call() == EINVAL, unit
+            assert last() == text, (unit, last())
+
+    walk()
+    # ... and per thread: another thread's failures leave this thread's text alone
+    assert lib.paos_zoom_weights(3, 1, 0.0, None, None) == EINVAL
+    mine = last()
+    errors = []
+
+    def other():
+        try:
+            assert last() == ""  # nothing has failed on this thread yet
+            walk()
+        except AssertionError as e:  # (an assertion on another thread would otherwise only be printed)
+            errors.append(e)
+
+    t = threading.Thread(target=other)
+    t.start()
+    t.join()
+    assert not errors, errors
+    assert last() == mine
+
+
 def test_shard_bounds_cover_exactly():
     from paos_amd.dist import shard_bounds
 

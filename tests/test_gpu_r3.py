@@ -240,7 +240,7 @@ def test_lean_walk_equals_the_ordinary_walk(n, precision):
 
 def test_psf_zeros_are_reused_only_while_they_are_there():
     """The pass that stores the PSF does not write the zeros of its dead tiles again when the buffer is known to hold
-    them (the previous storing pass had the same live lines: paos_hip.hip, psf_zero_*).  A sequence that keeps and
+    them (the previous storing pass had the same live lines: passes.hip, psf_zero_*).  A sequence that keeps and
     breaks that knowledge -- the same chain twice, a chain with a wider field stop (other live columns), back, an
     intensity sweep over junk in between -- must give the ordinary walk's PSFs bit for bit every time."""
     from paos_amd import _lib
@@ -479,7 +479,7 @@ def test_two_ranks_asking_for_rccl_on_one_gpu_agree():
 
 
 def test_record_sets_are_reused_and_evicted_correctly():
-    """The context keeps a few rendered sets of aperture line records (csrc/paos_hip.hip: MaskSet): a chain whose
+    """The context keeps a few rendered sets of aperture line records (csrc/host.h: MaskSet): a chain whose
     relays repeat one aperture renders it once, a second batch through the same optics renders nothing, and a
     chain with more distinct apertures than there are sets evicts.  Whatever the cache does, the fields equal those
     of a fresh context bit for bit, and those of the stand-alone aperture kernel to rounding."""

@@ -11,6 +11,6 @@ SAN="-O1 -g -fPIC -std=c++17 -Wall -fsanitize=address,undefined -fno-omit-frame-
 g++ $SAN -ffp-contract=off -c paos_amd/csrc/paos_plan.cpp -o build/asan/plan.o
 g++ $SAN -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -c paos_amd/csrc/paos_comm.cpp -o build/asan/comm.o
 GCCLIB=$(dirname "$(gcc -print-file-name=libasan.so)")
-/opt/rocm/bin/hipcc -shared -fPIC build/obj/part[0-5].o build/asan/comm.o build/asan/plan.o build/obj/srchash.o -ldl -L"$GCCLIB" -lasan -lubsan -o build/asan/libpaoship_asan.so
+/opt/rocm/bin/hipcc -shared -fPIC build/obj/hip/*.o build/asan/comm.o build/asan/plan.o build/obj/srchash.o -ldl -L"$GCCLIB" -lasan -lubsan -o build/asan/libpaoship_asan.so
 ASAN_OPTIONS=detect_leaks=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 LD_PRELOAD="$GCCLIB/libasan.so" \
   PAOS_LIB="$PWD/build/asan/libpaoship_asan.so" python -m pytest tests -x -q -m "not gpu" "$@"
