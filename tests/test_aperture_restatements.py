@@ -1,5 +1,8 @@
-"""Two independent restatements of the aperture-mask rules must agree (photutils itself is absent, so mask
-values stay "parity unpinned"; this is the strongest check the environment allows).  oracle/aperture_np.py
+"""Two independent restatements of the aperture-mask rules must agree (photutils itself is absent, so its own
+bits stay unpinned).  This arbitrates SMALL apertures only: aperture_alt's fp64 strip integrals cancel like
+eps a b, so the 2e-14 asked for below holds at the semi-axes <= 12 px used here, and is 1.2e-12 at 40.7 x 25.2 and
+2.9e-9 at a 512-pixel pupil (measured against exact areas: tests/test_aperture_xprec_reference.py, which is
+the check that holds at the sizes the project runs).  oracle/aperture_np.py
 (edge-wise Green's theorem on the bounding box; the algorithm the HIP kernel mirrors) against
 oracle/aperture_alt.py (closed-form strip integrals / quadrature, literal Python sub-sample loops, no
 bounding box) on the cases most likely to expose a slip: centres on exact half-integers, apertures that
