@@ -28,7 +28,7 @@ import numpy as np
 from . import _lib
 from . import abcd as _abcd
 from .abcd import ABCD
-from .aperture import EllipticalAperture, RectangularAperture, bbox_misses_grid, make_aperture
+from .aperture import EllipticalAperture, RectangularAperture, make_aperture
 from .coordinate_break import coordinate_break
 from . import passes as _passes
 from .passes import PassCompiler, SeparableCompiler
@@ -72,19 +72,6 @@ FUSE_START = _os.environ.get("PAOS_FUSE_START", "1") != "0"
 _MASK_RUN = 192  # kMaskW of csrc/frugal_pass.h
 
 
-def _aperture_fits_line_records(handle, obscuration, n, precision):
-    if n < (1024 if precision == "fp64" else 2048) or handle.theta != 0.0:
-        return False
-    if isinstance(handle, EllipticalAperture):
-        a, b = handle.a, handle.b
-        if not (a >= 2.0 and b >= 2.0):
-            return False
-        return (2.0 * a * math.sqrt(3.0 / b) + 8.0 <= _MASK_RUN and
-                2.0 * b * math.sqrt(3.0 / a) + 8.0 <= _MASK_RUN)
-    return not obscuration and handle.w > 0.0 and handle.h > 0.0
-
-_OFF_PHASE = [0.0] * _lib.PHASE_STRIDE
-_OFF_APERTURE = [0.0] * _lib.APERTURE_STRIDE
 
 
 class _Reduction:
@@ -199,105 +186,100 @@ class _PowerLedger:
                 rec["power_ticket"] = handle
 
 
-class _BatchApertures:
-    """The apertures of one surface for every wavefront of a batch as arrays (round 5: ``_plan_batch``): pixel-unit centres
-    and sizes, shape, obscuration flag -- what the library's parameter blocks, the line-record test and the live-row
-    bookkeeping need, without a Python object per wavefront.  ``handle(i)`` makes the photutils-like object of item i
-    when somebody wants to see it (a saved surface's record, an orthonormal Zernike pupil)."""
+class _SurfaceApertures:
+    """The apertures of one surface for every wavefront of a batch, as arrays over the batch: pixel-unit centres ``ixc, iyc``
+    and sizes ``ea, eb`` (semi-axes of an ellipse, FULL widths of a rectangle: wfo.py:224,261-264), ``theta``, the flags
+    ``rect`` and ``obsc``, and ``on`` -- true where the item carries an aperture here (the other entries of an item that is
+    off mean nothing).  Everything the walk wants to know about a surface's apertures is asked here, once: the library's
+    parameter blocks, the line-record test, the live rows and columns, the start's shape -- without a Python object per
+    wavefront (at 1024^2 x 256 wavefronts the per-item Python was 40 % of a step that the GPU finishes in half the time
+    the host needed to describe it).  ``handle(i)`` makes the photutils-like object of item i when somebody wants to see it
+    (a saved surface's record, an orthonormal Zernike pupil)."""
 
-    def __init__(self, ixc, iyc, ea, eb, rect, obsc):
-        self.ixc, self.iyc, self.ea, self.eb, self.rect, self.obsc = ixc, iyc, ea, eb, rect, obsc
+    def __init__(self, ixc, iyc, ea, eb, theta, rect, obsc, on):
+        self.ixc, self.iyc, self.ea, self.eb, self.theta = ixc, iyc, ea, eb, theta
+        self.rect, self.obsc, self.on = rect, obsc, on
         self.batch = len(ixc)
         self._handles = {}
 
+    @classmethod
+    def from_blocks(cls, shape_code, blocks):
+        """From [batch][8] parameter blocks of one shape (aperture.py: block), tilt included."""
+        b = np.asarray(blocks, dtype=np.float64).reshape(-1, _lib.APERTURE_STRIDE)
+        return cls(b[:, 1], b[:, 2], b[:, 3], b[:, 4], b[:, 5], np.full(len(b), shape_code == _lib.SHAPE_RECT),
+                   b[:, 6] != 0.0, b[:, 0] != 0.0)
+
     def handle(self, i):
+        """The aperture object of item i (None where it has none), made when it is first looked at."""
+        if not self.on[i]:
+            return None
         h = self._handles.get(i)
         if h is None:
             cls = RectangularAperture if self.rect[i] else EllipticalAperture
-            h = self._handles[i] = cls((float(self.ixc[i]), float(self.iyc[i])), float(self.ea[i]), float(self.eb[i]), 0.0)
+            h = self._handles[i] = cls((float(self.ixc[i]), float(self.iyc[i])), float(self.ea[i]), float(self.eb[i]),
+                                       float(self.theta[i]))
         return h
 
     def blocks(self):
-        """[batch][8] parameter blocks of paos_aperture / paos_start (aperture.py: block) and the shape code per item."""
+        """[batch][8] parameter blocks of paos_aperture / paos_start (aperture.py: block; all zero for an item that is off)
+        and the shape code per item."""
         b = np.zeros((self.batch, _lib.APERTURE_STRIDE), dtype=np.float64)
         b[:, 0] = 1.0
-        b[:, 1], b[:, 2], b[:, 3], b[:, 4] = self.ixc, self.iyc, self.ea, self.eb
+        b[:, 1], b[:, 2], b[:, 3], b[:, 4], b[:, 5] = self.ixc, self.iyc, self.ea, self.eb, self.theta
         b[:, 6] = self.obsc
         b[:, 7] = np.where(self.rect, 32.0, 0.0)
+        b[~self.on] = 0.0
         return b, np.where(self.rect, float(_lib.SHAPE_RECT), float(_lib.SHAPE_ELLIPSE))
 
     def fits_line_records(self, n, precision):
-        """``_aperture_fits_line_records`` for every item."""
-        if n < (1024 if precision == "fp64" else 2048):
+        """May the apertures ride on a pass as per-line records (csrc/frugal_pass.h: MaskLine)?  Every item that is on must
+        fit: an untilted ellipse whose partial runs fit, or an untilted clear rectangle."""
+        if n < (1024 if precision == "fp64" else 2048) or not self.on.any():
             return False
         a, b = self.ea, self.eb
         with np.errstate(all="ignore"):
             ell = (a >= 2.0) & (b >= 2.0) & (2.0 * a * np.sqrt(3.0 / b) + 8.0 <= _MASK_RUN) & (2.0 * b * np.sqrt(3.0 / a) + 8.0 <= _MASK_RUN)
         rec = ~self.obsc & (a > 0.0) & (b > 0.0)
-        return bool(np.all(np.where(self.rect, rec, ell)))
+        return bool(np.all(~self.on | ((self.theta == 0.0) & np.where(self.rect, rec, ell))))
+
+    def _clear_extent(self, centre, size, n):
+        """Per item [lo, hi) along one axis outside which a clear, untilted aperture leaves exact zeros (photutils' bounding
+        box, widened by a pixel), and where that holds: not for items that are off, obscuring, tilted or degenerate."""
+        ext = np.where(self.rect, size / 2.0, size)
+        ok = self.on & ~self.obsc & (self.theta == 0.0) & np.isfinite(centre) & np.isfinite(ext) & (ext > 0.0)
+        with np.errstate(all="ignore"):
+            lo = np.maximum(0, np.floor(centre - ext + 0.5) - 1)
+            hi = np.minimum(n, np.ceil(centre + ext + 0.5) + 1)
+        return lo, hi, ok & (lo < hi)
 
     def narrow_rows(self, live, n):
-        """``_live_rows_after`` for every item: rows outside a clear aperture's bounding box (widened by a pixel) are zero."""
-        ext = np.where(self.rect, self.eb / 2.0, self.eb)
-        ok = ~self.obsc & np.isfinite(self.iyc) & np.isfinite(ext) & (ext > 0.0)
-        with np.errstate(all="ignore"):
-            lo = np.maximum(0, np.floor(self.iyc - ext + 0.5) - 1)
-            hi = np.minimum(n, np.ceil(self.iyc + ext + 0.5) + 1)
-        for i in np.nonzero(ok & (lo < hi))[0].tolist():
+        """Rows that may be non-zero after the stand-alone apertures were applied; ``live`` is updated in place, one
+        [lo, hi) per item."""
+        lo, hi, ok = self._clear_extent(self.iyc, self.eb, n)
+        for i in np.nonzero(ok)[0].tolist():
             r = live[i]
             r[0], r[1] = max(r[0], int(lo[i])), min(r[1], int(hi[i]))
-            if r[0] >= r[1]:
+            if r[0] >= r[1]:  # disjoint boxes: everything is zero; keep a token range
                 r[0], r[1] = 0, 0
 
-
-def _live_cols_of(plans, n):
-    """Per item the columns [lo, hi) outside which a clear aperture leaves exact zeros (photutils' bounding box widened by
-    a pixel, like ``_live_rows_after`` for the rows), or None when some item has no such aperture."""
-    out = []
-    for i, p in enumerate(plans):
-        ap = p["aperture"]
-        if ap is None or ap[1] or ap[0].theta != 0.0:
+    def live_cols(self, n):
+        """Per item the columns [lo, hi) outside which the aperture leaves exact zeros, or None when some item has no
+        such aperture."""
+        lo, hi, ok = self._clear_extent(self.ixc, self.ea, n)
+        if not ok.all():
             return None
-        h = ap[0]
-        ext = h.a if isinstance(h, EllipticalAperture) else h.w / 2.0
-        xc = h._xy[0]
-        if not (math.isfinite(xc) and math.isfinite(ext) and ext > 0.0):
+        return [[int(a), int(b)] for a, b in zip(lo.tolist(), hi.tolist())]
+
+    def start_shape(self):
+        """The shape code when every item carries an aperture and all are of one shape (paos_start takes one), else None."""
+        if not self.on.all() or (self.rect.any() and not self.rect.all()):
             return None
-        lo = max(0, int(math.floor(xc - ext + 0.5)) - 1)
-        hi = min(n, int(math.ceil(xc + ext + 0.5)) + 1)
-        if lo >= hi:
-            return None
-        out.append([lo, hi])
-    return out
-
-
-class _LazyAperture:
-    """``plan["aperture"]`` of an item of a ``_BatchApertures`` surface: behaves like the (handle, obscuration) pair
-    ``_plan_host`` makes; the handle is built when it is looked at."""
-
-    __slots__ = ("src", "i")
-
-    def __init__(self, src, i):
-        self.src, self.i = src, i
-
-    def __getitem__(self, k):
-        if k == 0:
-            return self.src.handle(self.i)
-        if k == 1:
-            return bool(self.src.obsc[self.i])
-        raise IndexError(k)
-
-    def __iter__(self):
-        yield self.src.handle(self.i)
-        yield bool(self.src.obsc[self.i])
-
-    def __len__(self):
-        return 2
+        return _lib.SHAPE_RECT if self.rect[0] else _lib.SHAPE_ELLIPSE
 
 
 class _Plans(list):
-    """The per-item plans of one surface; ``ap`` is the surface's ``_BatchApertures`` when ``_plan_batch`` planned the
-    apertures of ALL items with array arithmetic (None otherwise: the consumers then read the per-item entries).
+    """The per-item plans of one surface (``_plan_surface``): dicts with ``stop``, ``zernike``, ``phase_map``; ``ap`` is the
+    surface's ``_SurfaceApertures``, or None when no item carries an aperture here.
     ``summary()``: (any stop, any Zernike, any phase map, any aperture) over the items -- looked at a dozen times per
     surface by the walk, scanned once."""
 
@@ -308,14 +290,17 @@ class _Plans(list):
     def summary(self):
         if self._summary is None:
             self._summary = (any(p["stop"] for p in self), any(p["zernike"] is not None for p in self),
-                             any(p["phase_map"] is not None for p in self), any(p["aperture"] is not None for p in self))
+                             any(p["phase_map"] is not None for p in self), self.ap is not None)
         return self._summary
+
+    def aperture(self, i):
+        """The aperture object of item i at this surface, or None."""
+        return self.ap.handle(i) if self.ap is not None else None
 
 
 class _Item:
-    """Host state of one wavefront while it walks the chain: the two paraxial rays of the field
-    point and the ray-transfer factors met so far.  (The pilot beams of all wavefronts live together
-    in a ``planner.BeamBatch``.)"""
+    """One wavefront of a walk: the beam's scalars and its field point.  (The pilot beams of all wavefronts live together
+    in a ``planner.BeamBatch``, their paraxial rays in a ``_Rays``.)"""
 
     def __init__(self, pupil_diameter, wavelength, gridsize, zoom, field):
         # the argument checks of WFO.__init__ (wfo.py:100-103)
@@ -324,12 +309,7 @@ class _Item:
         assert pupil_diameter > 0, "beam diameter should be positive"
         assert wavelength > 0, "a wavelength should be positive"
         self.pupil_diameter, self.wavelength, self.gridsize, self.zoom = pupil_diameter, wavelength, gridsize, zoom
-        self.vt = np.array([0.0, field["ut"]])
-        self.vs = np.array([0.0, field["us"]])
-        # an on-axis field point: both rays are [0, 0] and stay so under every ABCD matrix (A @ 0 = 0)
-        # until a coordinate break moves them -- no need to multiply
-        self.still = field["ut"] == 0.0 and field["us"] == 0.0
-        self.factors_t, self.factors_s = [], []
+        self.field = field
 
 
 def _fields_of(field, nb):
@@ -354,41 +334,37 @@ def _fields_of(field, nb):
 
 
 class _Rays:
-    """The two paraxial rays of every wavefront of a batch as arrays: ``vt`` / ``vs`` (batch, 2) and ``still`` (both rays
-    exactly zero).  The walk keeps them here so that items at different field points are planned with array arithmetic
-    (``_plan_batch(..., rays=)``) and advanced through a surface with one stacked ``A @ v`` (``advance``) -- the very
-    operations ``_plan_host`` and the per-item update form, so the numbers are the same.  ``_Item.vt`` / ``vs`` are
-    brought up to date around the per-item planner only (``to_states`` / ``from_states``)."""
+    """The two paraxial rays of every wavefront of a batch as arrays: ``vt`` / ``vs`` (batch, 2), started from the field
+    points (run.py:64-65), and ``still`` (both rays exactly zero: an on-axis field point, whose rays stay [0, 0] under
+    every ABCD matrix -- A @ 0 = 0 -- until a coordinate break moves them).  The one ray state of a walk: ``_plan_surface``
+    plans the apertures from it, ``coordinate_break`` and ``advance`` move it."""
 
-    def __init__(self, states):
-        self.vt = np.array([st.vt for st in states], dtype=np.float64).reshape(len(states), 2)
-        self.vs = np.array([st.vs for st in states], dtype=np.float64).reshape(len(states), 2)
-        self.still = np.array([bool(st.still) for st in states])
+    def __init__(self, fields):
+        self.vt = np.array([[0.0, f["ut"]] for f in fields], dtype=np.float64).reshape(len(fields), 2)
+        self.vs = np.array([[0.0, f["us"]] for f in fields], dtype=np.float64).reshape(len(fields), 2)
+        self._settle()
+
+    def _settle(self):
+        self.still = ~(self.vt.any(axis=1) | self.vs.any(axis=1))
         self._all_still = bool(self.still.all())
 
     def all_still(self):
         return self._all_still
 
-    def to_states(self, states):
-        for i, st in enumerate(states):
-            st.vt, st.vs, st.still = self.vt[i].copy(), self.vs[i].copy(), bool(self.still[i])
-
-    def from_states(self, states):
-        for i, st in enumerate(states):
-            self.vt[i], self.vs[i], self.still[i] = st.vt, st.vs, st.still
-        self._all_still = bool(self.still.all())
-
     def coordinate_break(self, items):
-        """``coordinate_break`` of every item (run.py:81-91), once per distinct (rays, break) of the batch."""
+        """``coordinate_break`` of the items that are one (run.py:81-91), once per distinct (rays, break) of the batch; the
+        rays of the others stay as they are."""
         memo = {}
         for i, it in enumerate(items):
+            if it["type"] != "Coordinate Break":
+                continue
             key = (self.vt[i].tobytes(), self.vs[i].tobytes(), it["xdec"], it["ydec"], it["xrot"], it["yrot"])
             hit = memo.get(key)
             if hit is None:
                 hit = memo[key] = coordinate_break(self.vt[i], self.vs[i], it["xdec"], it["ydec"], it["xrot"], it["yrot"], 0.0)
             self.vt[i], self.vs[i] = hit
-        self.still = ~(self.vt.any(axis=1) | self.vs.any(axis=1))
-        self._all_still = bool(self.still.all())
+        if memo:
+            self._settle()
 
     def advance(self, col_t, col_s):
         """``v <- A @ v`` for the items whose rays are not zero (an on-axis item's stay [0, 0] under every matrix)."""
@@ -490,181 +466,108 @@ def _sag_map_once(sag, nx, ny, delx, dely, xdec, ydec, n, dx, dy):
     return m
 
 
-def _plan_host(st, item, n, dx, dy, wl, wz_of, aperture_plan=False):
-    """Host half of one loop iteration of run.py:77-178 for one wavefront -- everything but the
-    pilot-beam scalars (those are advanced for the whole batch in one C call, planner.BeamBatch).
-    ``dx, dy, wl`` are the wavefront's current sampling and wavelength, ``wz_of()`` its beam radius."""
-    plan = {"aperture": None, "stop": bool(item["is_stop"]), "zernike": None, "phase_map": None}
-    kind = item["type"]
-
-    if kind == "Coordinate Break":
-        st.vt, st.vs = coordinate_break(st.vt, st.vs, item["xdec"], item["ydec"], item["xrot"],
-                                        item["yrot"], 0.0)
-        st.still = not (np.any(st.vt) or np.any(st.vs))
-
-    ap = item.get("aperture")
-    if aperture_plan is not False:  # (_plan_batch has done the aperture)
-        plan["aperture"] = aperture_plan
-    elif ap is not None:
-        xdec = ap["xc"] if math.isfinite(ap["xc"]) else st.vs[0]
-        ydec = ap["yc"] if math.isfinite(ap["yc"]) else st.vt[0]
-        xrad = ap["xrad"]
-        yrad = ap["yrad"]
-        xrad *= math.sqrt(1 / (st.vs[1] ** 2 + 1))  # sqrt is correctly rounded either way
-        yrad *= math.sqrt(1 / (st.vt[1] ** 2 + 1))
-        xaper = xdec - st.vs[0]
-        yaper = ydec - st.vt[0]
-        if math.isfinite(xrad) and math.isfinite(yrad):
-            handle = make_aperture(n, dx, dy, xaper, yaper, hx=xrad, hy=yrad, shape=ap["shape"])
-            if bbox_misses_grid(handle, n):
-                raise TypeError("aperture does not overlap the grid (mask is None in the reference)")
-            plan["aperture"] = (handle, ap["type"] != "aperture")
-
-    if kind == "Zernike":
-        radius = item["Zradius"] if math.isfinite(item["Zradius"]) else wz_of()
-        pupil = None
-        if item["Zorthonorm"]:  # run.py:133-141: orthonormal over THIS surface's aperture object
-            assert "aperture" in item, "Zorthonorm requires aperture"
-            if plan["aperture"] is None:
-                raise KeyError("aperture")  # the reference finds no _retval_["aperture"]
-            # to_mask("exact") of a RectangularAperture: photutils has no exact rectangle overlap and
-            # maps that request to the 32 x 32 sub-pixel rule (its _translate_mask_mode), i.e. the very
-            # mask WFO.aperture applies -- so both shapes are served by the aperture kernel
-            pupil = plan["aperture"][0]
-        index = np.asarray(item["Zindex"])
-        assert not np.any(np.diff(index) - 1), "Zernike sequence should be continuous"
-        ordering = item["Zordering"]
-        if ordering not in ("ansi", "noll", "fringe", "standard"):
-            raise AssertionError("Unrecognised ordering scheme.")
-        m, nn, norm = zernike_tables(len(index), ordering, bool(item["Znormalize"]))
-        plan["zernike"] = dict(m=m, n=nn, norm=norm, Z=np.asarray(item["Z"], dtype=np.float64), dx=dx, dy=dy,
-                               radius=radius, wl=wl, origin=item["Zorigin"], pupil=pupil)
-    elif kind == "Grid Sag":  # run.py:154-164
-        plan["phase_map"] = (_sag_map_once(item["grid_sag"], item["nx"], item["ny"], item["delx"], item["dely"],
-                                           item["xdec"], item["ydec"], n, dx, dy), wl)
-    elif kind == "PSD":  # run.py:166-177
-        # (the draws are taken here, in the reference's order; the screen itself is built when the surface is launched: on the
-        # device where the context can -- _launch_phase_maps)
-        plan["phase_map"] = (PsdScreen((n, n), dx, dy, item["A"], item["B"], item["C"], item["fknee"], item["fmin"],
-                                       item["fmax"], item["SR"], item["units"]), wl)
-    return plan
+_NO_GEOMETRY = (float("nan"),) * 4
+_RENDERED_SHAPES = {"elliptical", "rectangular", None}  # (None: an item without an aperture entry)
 
 
-def _plan_batch(states, items, n, dxs, dys, wls, wz_of, all_still=None, rays=None):
-    """``_plan_host`` for every wavefront of a batch.  The common case -- every item on axis (both paraxial rays zero:
-    no coordinate break has moved them), the same kind of surface for all, no Grid Sag / PSD map to build -- is planned
-    with array arithmetic (round 5: at 1024^2 x 256 wavefronts the per-item Python of this function was 40 % of a
-    step that the GPU finishes in half the time the host needed to describe it).  The numbers are the ones
-    ``_plan_host`` forms: with the rays at zero its ``xrad *= sqrt(1 / (0**2 + 1))`` and ``xdec - 0.0`` are exact
-    identities, the pixel quantities are the same IEEE divisions and sums.  Anything else takes the per-item path.
-
-    ``rays`` (a ``_Rays``: the walk's) lifts the on-axis condition: the rays are read from (and a coordinate break is
-    applied to) its arrays, and the radii and centres are formed as ``_plan_host`` forms them, operation for operation
-    -- ``vs[1] ** 2`` of a NumPy scalar is C ``pow``, which rounds differently from ``vs[1] * vs[1]`` (what an array's
-    ``** 2`` forms) at ties, so the squares are taken of the scalars here too.  Only Grid Sag / PSD surfaces and mixed kinds then go item by item."""
-    kind = items[0]["type"]
-    same_kind = all(it["type"] == kind for it in items)
-    if rays is not None:
-        fast = kind not in ("Grid Sag", "PSD") and same_kind
-        if fast and kind == "Coordinate Break":
-            rays.coordinate_break(items)
-    else:
-        if all_still is None:
-            all_still = all(st.still for st in states)
-        fast = kind not in ("Coordinate Break", "Grid Sag", "PSD") and all_still and same_kind
-    if not fast:
-        if rays is not None:
-            rays.to_states(states)
-        plans = _Plans(_plan_host(st, it, n, dxs[i], dys[i], wls[i], lambda i=i: wz_of(i))
-                       for i, (st, it) in enumerate(zip(states, items)))
-        if rays is not None:
-            rays.from_states(states)
-        return plans
-    moving = rays is not None and not rays.all_still()
-    plans = _Plans({"aperture": None, "stop": bool(it["is_stop"]), "zernike": None, "phase_map": None} for it in items)
-    aps = [it.get("aperture") for it in items]
-    have = [i for i, a in enumerate(aps) if a is not None]
-    if have:
-        sel = aps if len(have) == len(aps) else [aps[i] for i in have]
-        geo = np.array([(a["xc"], a["yc"], a["xrad"], a["yrad"]) for a in sel], dtype=np.float64)
-        xc, yc, xrad, yrad = geo[:, 0], geo[:, 1], geo[:, 2], geo[:, 3]
-        if len(have) == len(aps):
-            dx, dy = np.asarray(dxs, dtype=np.float64), np.asarray(dys, dtype=np.float64)
-        else:
-            dx, dy = np.array([dxs[i] for i in have], dtype=np.float64), np.array([dys[i] for i in have], dtype=np.float64)
-        shapes = [a["shape"] for a in sel]
-        rect = np.array([sh == "rectangular" for sh in shapes])
-        known = all(sh in ("elliptical", "rectangular") for sh in shapes)
-        if moving:  # run.py:97-108 with the rays of every item (_plan_host, operation for operation)
-            sel_rows = slice(None) if len(have) == len(aps) else np.asarray(have)
-            vs0, vs1 = rays.vs[sel_rows, 0], rays.vs[sel_rows, 1]
-            vt0, vt1 = rays.vt[sel_rows, 0], rays.vt[sel_rows, 1]
-            with np.errstate(all="ignore"):
-                xrad = xrad * np.sqrt(1 / (np.array([v ** 2 for v in vs1]) + 1))
-                yrad = yrad * np.sqrt(1 / (np.array([v ** 2 for v in vt1]) + 1))
-                xaper = np.where(np.isfinite(xc), xc, vs0) - vs0  # (a missing centre falls back on the chief ray)
-                yaper = np.where(np.isfinite(yc), yc, vt0) - vt0
-        else:
-            xaper = np.where(np.isfinite(xc), xc, 0.0)  # (a missing centre falls back on the chief ray: zero here)
-            yaper = np.where(np.isfinite(yc), yc, 0.0)
+def _plan_apertures(aps, n, dxs, dys, rays):
+    """The apertures of one surface (run.py:96-122) for all items with array arithmetic, from their ``aperture`` entries
+    ``aps`` (None where an item has none): a ``_SurfaceApertures``, or None when no item carries one.  The numbers are the ones the reference forms item by item, operation for operation:
+    ``vs[1] ** 2`` of a NumPy scalar is C ``pow``, which rounds differently from ``vs[1] * vs[1]`` (what an array's
+    ``** 2`` forms) at ties, so the squares are taken of the scalars; the pixel quantities are the same IEEE divisions and
+    sums.  While every ray is zero (no off-axis item, no coordinate break has moved them) ``xrad * sqrt(1 / (0**2 + 1))``
+    and ``xdec - 0.0`` are exact identities and are not formed.  An item whose radii are not both finite has no aperture
+    (run.py:112); one whose bounding box misses the grid raises the reference's ``TypeError``."""
+    geo = np.array([(a["xc"], a["yc"], a["xrad"], a["yrad"]) if a is not None else _NO_GEOMETRY for a in aps], dtype=np.float64)
+    xc, yc, xrad, yrad = geo[:, 0], geo[:, 1], geo[:, 2], geo[:, 3]
+    dx, dy = np.asarray(dxs, dtype=np.float64), np.asarray(dys, dtype=np.float64)
+    if not rays.all_still():  # run.py:97-108 with the rays of every item
+        vs0, vs1, vt0, vt1 = rays.vs[:, 0], rays.vs[:, 1], rays.vt[:, 0], rays.vt[:, 1]
         with np.errstate(all="ignore"):
-            ixc, iyc = xaper / dx + n / 2, yaper / dy + n / 2
-            ea, eb = xrad / dx, yrad / dy   # semi-axes of an ellipse, FULL widths of a rectangle (wfo.py:224,261-264)
-            xe, ye = np.where(rect, np.abs(ea / 2.0), np.abs(ea)), np.where(rect, np.abs(eb / 2.0), np.abs(eb))
-            x0, x1 = np.floor(ixc - xe + 0.5), np.ceil(ixc + xe + 0.5)
-            y0, y1 = np.floor(iyc - ye + 0.5), np.ceil(iyc + ye + 0.5)
-            miss = ~(np.isfinite(ixc) & np.isfinite(iyc) & np.isfinite(xe) & np.isfinite(ye))
-            miss |= (np.maximum(x0, 0) >= np.minimum(x1, n)) | (np.maximum(y0, 0) >= np.minimum(y1, n))
-        finite = np.isfinite(xrad) & np.isfinite(yrad)
-        obsc = np.array([a["type"] != "aperture" for a in sel])
-        if known and len(have) == len(aps) and bool(finite.all()):
-            # every item carries an aperture of a shape the kernels render: no per-item objects at all
-            if bool(miss.any()):
-                raise TypeError("aperture does not overlap the grid (mask is None in the reference)")
-            plans.ap = _BatchApertures(ixc, iyc, ea, eb, rect, obsc)
-            for i, p in enumerate(plans):
-                p["aperture"] = _LazyAperture(plans.ap, i)
-        else:
-            ixc, iyc, ea, eb = ixc.tolist(), iyc.tolist(), ea.tolist(), eb.tolist()
-            for k, i in enumerate(have):
-                if not finite[k]:
-                    continue  # run.py:112: skipped unless both radii are finite
-                shape = shapes[k]
-                if shape == "elliptical":
-                    handle = EllipticalAperture((ixc[k], iyc[k]), ea[k], eb[k], 0.0)
-                elif shape == "rectangular":
-                    handle = RectangularAperture((ixc[k], iyc[k]), ea[k], eb[k], 0.0)
-                else:  # ("circular" needs r, which run() never passes: make_aperture raises as the reference does)
-                    handle = make_aperture(n, dxs[i], dys[i], float(xaper[k]), float(yaper[k]), hx=float(xrad[k]),
-                                           hy=float(yrad[k]), shape=shape)
-                if miss[k]:
-                    raise TypeError("aperture does not overlap the grid (mask is None in the reference)")
-                plans[i]["aperture"] = (handle, bool(obsc[k]))
-    plans._summary = (any(it["is_stop"] for it in items), kind == "Zernike", False,
-                      plans.ap is not None or any(p["aperture"] is not None for p in plans) if have else False)
-    if kind == "Zernike":
-        # (run.py:124-152 per item; what depends only on the index array / ordering / normalisation -- the continuity
-        # check, the (m, n, norm) tables -- is looked up once per distinct index array of the batch)
+            xrad = xrad * np.sqrt(1 / (np.array([v ** 2 for v in vs1]) + 1))
+            yrad = yrad * np.sqrt(1 / (np.array([v ** 2 for v in vt1]) + 1))
+            xaper = np.where(np.isfinite(xc), xc, vs0) - vs0  # (a missing centre falls back on the chief ray)
+            yaper = np.where(np.isfinite(yc), yc, vt0) - vt0
+    else:
+        xaper = np.where(np.isfinite(xc), xc, 0.0)  # (a missing centre falls back on the chief ray: zero here)
+        yaper = np.where(np.isfinite(yc), yc, 0.0)
+    on = np.isfinite(xrad) & np.isfinite(yrad)  # (never for an item without an aperture entry)
+    if not on.any():
+        return None
+    shapes = [a["shape"] if a is not None else None for a in aps]
+    rect = np.array([sh == "rectangular" for sh in shapes])
+    with np.errstate(all="ignore"):
+        ixc, iyc = xaper / dx + n / 2, yaper / dy + n / 2
+        ea, eb = xrad / dx, yrad / dy
+        xe, ye = np.where(rect, np.abs(ea / 2.0), np.abs(ea)), np.where(rect, np.abs(eb / 2.0), np.abs(eb))
+        x0, x1 = np.floor(ixc - xe + 0.5), np.ceil(ixc + xe + 0.5)
+        y0, y1 = np.floor(iyc - ye + 0.5), np.ceil(iyc + ye + 0.5)
+        miss = ~(np.isfinite(ixc) & np.isfinite(iyc) & np.isfinite(xe) & np.isfinite(ye))
+        miss |= (np.maximum(x0, 0) >= np.minimum(x1, n)) | (np.maximum(y0, 0) >= np.minimum(y1, n))
+    bad = on & miss
+    if not _RENDERED_SHAPES.issuperset(shapes):
+        bad |= on & np.array([sh not in _RENDERED_SHAPES for sh in shapes])
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        if shapes[i] not in _RENDERED_SHAPES:
+            # ("circular" needs r, which run() never passes: make_aperture raises as the reference does)
+            make_aperture(n, dxs[i], dys[i], float(xaper[i]), float(yaper[i]), hx=float(xrad[i]), hy=float(yrad[i]),
+                          shape=shapes[i])
+        raise TypeError("aperture does not overlap the grid (mask is None in the reference)")
+    obsc = np.array([a is not None and a["type"] != "aperture" for a in aps])
+    return _SurfaceApertures(ixc, iyc, ea, eb, np.zeros(len(aps)), rect, obsc, on)
+
+
+def _plan_surface(items, n, dxs, dys, wls, wz_of, rays):
+    """Host half of one loop iteration of run.py:77-178 for every wavefront of a batch -- everything but the pilot-beam
+    scalars (those are advanced for the whole batch in one C call, planner.BeamBatch).  ``dxs, dys, wls`` are the
+    wavefronts' current samplings and wavelengths, ``wz_of(i)`` item i's beam radius, ``rays`` the walk's ``_Rays``.  In
+    the reference's order: the coordinate break, the apertures (``_plan_apertures``: arrays over the batch), then, item
+    by item in item order, what is per item by nature -- a Zernike surface's tables, a Grid Sag map, the draws of a PSD
+    screen."""
+    kinds = [it["type"] for it in items]  # (looked through at C speed: a step of 256 wavefronts plans 20 surfaces)
+    if "Coordinate Break" in kinds:
+        rays.coordinate_break(items)
+    plans = _Plans({"stop": bool(it["is_stop"]), "zernike": None, "phase_map": None} for it in items)
+    aps = [it.get("aperture") for it in items]
+    if aps.count(None) < len(aps):
+        plans.ap = _plan_apertures(aps, n, dxs, dys, rays)
+    if "Zernike" in kinds or "Grid Sag" in kinds or "PSD" in kinds:
         tables = {}
-        for i, it in enumerate(items):
-            radius = it["Zradius"] if math.isfinite(it["Zradius"]) else wz_of(i)
-            pupil = None
-            if it["Zorthonorm"]:
-                assert "aperture" in it, "Zorthonorm requires aperture"
-                if plans[i]["aperture"] is None:
-                    raise KeyError("aperture")  # the reference finds no _retval_["aperture"]
-                pupil = plans[i]["aperture"][0]
-            index = np.asarray(it["Zindex"])
-            key = (index.tobytes(), index.dtype.str, it["Zordering"], bool(it["Znormalize"]))
-            hit = tables.get(key)
-            if hit is None:
-                assert not np.any(np.diff(index) - 1), "Zernike sequence should be continuous"
-                if it["Zordering"] not in ("ansi", "noll", "fringe", "standard"):
-                    raise AssertionError("Unrecognised ordering scheme.")
-                hit = tables[key] = zernike_tables(len(index), it["Zordering"], bool(it["Znormalize"]))
-            m, nn, norm = hit
-            plans[i]["zernike"] = dict(m=m, n=nn, norm=norm, Z=np.asarray(it["Z"], dtype=np.float64), dx=dxs[i], dy=dys[i],
+        for i, (it, plan, kind) in enumerate(zip(items, plans, kinds)):
+            if kind == "Zernike":
+                # (run.py:124-152; what depends only on the index array / ordering / normalisation -- the continuity check,
+                # the (m, n, norm) tables -- is looked up once per distinct index array of the batch)
+                radius = it["Zradius"] if math.isfinite(it["Zradius"]) else wz_of(i)
+                pupil = None
+                if it["Zorthonorm"]:  # run.py:133-141: orthonormal over THIS surface's aperture object
+                    assert "aperture" in it, "Zorthonorm requires aperture"
+                    # to_mask("exact") of a RectangularAperture: photutils has no exact rectangle overlap and maps that
+                    # request to the 32 x 32 sub-pixel rule (its _translate_mask_mode), i.e. the very mask WFO.aperture
+                    # applies -- so both shapes are served by the aperture kernel
+                    pupil = plans.aperture(i)
+                    if pupil is None:
+                        raise KeyError("aperture")  # the reference finds no _retval_["aperture"]
+                index = np.asarray(it["Zindex"])
+                key = (index.tobytes(), index.dtype.str, it["Zordering"], bool(it["Znormalize"]))
+                hit = tables.get(key)
+                if hit is None:
+                    assert not np.any(np.diff(index) - 1), "Zernike sequence should be continuous"
+                    if it["Zordering"] not in ("ansi", "noll", "fringe", "standard"):
+                        raise AssertionError("Unrecognised ordering scheme.")
+                    hit = tables[key] = zernike_tables(len(index), it["Zordering"], bool(it["Znormalize"]))
+                m, nn, norm = hit
+                plan["zernike"] = dict(m=m, n=nn, norm=norm, Z=np.asarray(it["Z"], dtype=np.float64), dx=dxs[i], dy=dys[i],
                                        radius=radius, wl=wls[i], origin=it["Zorigin"], pupil=pupil)
+            elif kind == "Grid Sag":  # run.py:154-164
+                plan["phase_map"] = (_sag_map_once(it["grid_sag"], it["nx"], it["ny"], it["delx"], it["dely"],
+                                                   it["xdec"], it["ydec"], n, dxs[i], dys[i]), wls[i])
+            elif kind == "PSD":  # run.py:166-177
+                # (the draws are taken here, in the reference's order; the screen itself is built when the surface is
+                # launched: on the device where the context can -- _launch_phase_maps)
+                plan["phase_map"] = (PsdScreen((n, n), dxs[i], dys[i], it["A"], it["B"], it["C"], it["fknee"], it["fmin"],
+                                               it["fmax"], it["SR"], it["units"]), wls[i])
+    plans.summary()
     return plans
 
 
@@ -732,49 +635,28 @@ def _live_rows_after(plans, live, n):
     """Rows that may be non-zero after the stand-alone apertures of ``plans`` were applied: a clear
     aperture (not an obscuration) leaves exact zeros outside its bounding box (photutils' box,
     widened by a pixel here).  ``live`` is updated in place, one [lo, hi) per item."""
-    if getattr(plans, "ap", None) is not None:
+    if plans.ap is not None:
         plans.ap.narrow_rows(live, n)
-        return
-    for i, p in enumerate(plans):
-        ap = p["aperture"]
-        if ap is None or ap[1] or ap[0].theta != 0.0:
-            continue
-        h = ap[0]
-        ext = h.b if isinstance(h, EllipticalAperture) else h.h / 2.0
-        yc = h._xy[1]
-        if not (math.isfinite(yc) and math.isfinite(ext) and ext > 0.0):
-            continue
-        lo = max(0, int(math.floor(yc - ext + 0.5)) - 1)
-        hi = min(n, int(math.ceil(yc + ext + 0.5)) + 1)
-        if lo >= hi:
-            continue
-        live[i][0] = max(live[i][0], lo)
-        live[i][1] = min(live[i][1], hi)
-        if live[i][0] >= live[i][1]:  # disjoint boxes: everything is zero; keep a token range
-            live[i][0], live[i][1] = 0, 0
+
+
+def _live_cols_of(plans, n):
+    """Per item the columns [lo, hi) outside which a clear aperture leaves exact zeros (like ``_live_rows_after`` for the
+    rows), or None when some item has no such aperture."""
+    return plans.ap.live_cols(n) if plans.ap is not None else None
 
 
 def _launch_apertures(dev, plans):
-    if getattr(plans, "ap", None) is not None:
-        blocks, codes = plans.ap.blocks()
-        for code in (_lib.SHAPE_ELLIPSE, _lib.SHAPE_RECT):
-            mine = codes == float(code)
-            if mine.any():
-                b = blocks.copy()
-                b[~mine] = 0.0
-                dev.aperture(code, b)
+    """The surface's apertures as stand-alone kernels: one call per shape, enable = 0 for the items of the other."""
+    if plans.ap is None:
         return
-    for code, cls_is_ellipse in ((_lib.SHAPE_ELLIPSE, True), (_lib.SHAPE_RECT, False)):
-        blocks, any_on = [], False
-        for p in plans:
-            ap = p["aperture"]
-            if ap is not None and isinstance(ap[0], EllipticalAperture) == cls_is_ellipse:
-                blocks.append(ap[0].block(obscuration=ap[1]))
-                any_on = True
-            else:
-                blocks.append(_OFF_APERTURE)
-        if any_on:
-            dev.aperture(code, blocks)
+    blocks, codes = plans.ap.blocks()
+    for code in (_lib.SHAPE_ELLIPSE, _lib.SHAPE_RECT):
+        mine = plans.ap.on & (codes == float(code))
+        if mine.any():
+            b = blocks.copy()
+            b[~mine] = 0.0
+            dev.aperture(code, b)
+
 
 
 def _zernike_tables(plans):
@@ -897,18 +779,8 @@ _FILLED_MAPS = {}  # id(map) -> (map, its zero-filled contiguous copy: what cros
 def _queue_apertures(comp, plans):
     """Apertures as pass operators (their weight maps are rendered right before the pass
     they ride on, csrc/passes.hip: launch_one_pass)."""
-    if getattr(plans, "ap", None) is not None:
+    if plans.ap is not None:
         comp.aperture(plans.ap.blocks())
-        return
-    recs = []
-    for p in plans:
-        ap = p["aperture"]
-        if ap is None:
-            recs.append(None)
-        else:
-            code = _lib.SHAPE_ELLIPSE if isinstance(ap[0], EllipticalAperture) else _lib.SHAPE_RECT
-            recs.append((ap[0].block(obscuration=ap[1]), code))
-    comp.aperture(recs)
 
 
 def _queue_steps(comp, lens, stw, ptp, wts, inv_stw, inv_wts):
@@ -944,29 +816,20 @@ def _start_field(dev, fs, plans, value, lean, may_defer):
     and with ``START_BOX`` inside its columns as well.  Returns (True, copies): the surface's aperture and stop are done,
     ``copies`` names per item the first item with the same field (None: all differ).  Otherwise fill, and (False, None):
     the surface runs as usual.  ``may_defer``: a box start is not launched but left as ``lean.deferred_start``."""
+    code = plans.ap.start_shape() if plans.ap is not None else None
+    if code is None:
+        dev.fill(value)
+        return False, None
     rows = cols = None
     if lean is not None and hasattr(dev, "zero_outside_rows"):
         trial = [[0, dev.n] for _ in plans]
-        _live_rows_after(plans, trial, dev.n)
+        plans.ap.narrow_rows(trial, dev.n)
         # worth it only when every item's aperture leaves whole rows dark
         if all(r[0] > 0 or r[1] < dev.n for r in trial) and all(r[0] < r[1] for r in trial):
             rows = trial
             if START_BOX:  # ... and whole columns: the field is written inside the aperture's box only
-                cols = _live_cols_of(plans, dev.n)
-    batch_ap = getattr(plans, "ap", None)
-    if batch_ap is not None:
-        if bool(batch_ap.rect.any()) and not bool(batch_ap.rect.all()):
-            dev.fill(value)
-            return False, None
-        code = _lib.SHAPE_RECT if bool(batch_ap.rect.all()) else _lib.SHAPE_ELLIPSE
-        blocks = batch_ap.blocks()[0].tolist()
-    else:
-        aps = [p["aperture"] for p in plans]
-        if any(a is None for a in aps) or len({isinstance(a[0], EllipticalAperture) for a in aps}) != 1:
-            dev.fill(value)
-            return False, None
-        code = _lib.SHAPE_ELLIPSE if isinstance(aps[0][0], EllipticalAperture) else _lib.SHAPE_RECT
-        blocks = [a[0].block(obscuration=a[1]) for a in aps]
+                cols = plans.ap.live_cols(dev.n)
+    blocks = plans.ap.blocks()[0].tolist()
     stops = [1.0 if p["stop"] else 0.0 for p in plans]
     # which items now hold the same field: same aperture record, stop flag and window
     seen, same_as = {}, []
@@ -1118,7 +981,7 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
     fs = _FieldState(dev.n, len(states))
     npass = fused_start = 0  # fused_start: the first field was written with the Zernike phase of the next surface on it
     factor_cols_t, factor_cols_s = [], []  # [surface][item] ABCD factors met so far (run.py:215-219)
-    rays = _Rays(states)  # the paraxial rays of every item (_plan_batch plans from them, `advance` moves them)
+    rays = _Rays([st.field for st in states])  # the paraxial rays of every item
 
     # from which surface on nothing touches the field any more (index into keys[0]; len = never)
     order = keys[0]
@@ -1137,7 +1000,7 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
                 readout.extend(beams.readout())
             return readout
 
-        plans = _plan_batch(states, items, n, dxs, dys, wls, lambda i: wz_dtf()[0][i], rays=rays)
+        plans = _plan_surface(items, n, dxs, dys, wls, lambda i: wz_dtf()[0][i], rays)
         # (the ray-transfer factors met so far, one column per surface; a saved surface gets its product -- lazily)
         col_t, col_s = [it["ABCDt"] for it in items], [it["ABCDs"] for it in items]
         factor_cols_t.append(col_t)
@@ -1190,12 +1053,8 @@ def _walk(dev, states, chains, on_saved, stats=None, fresh=None, lean=None, psf_
                 # on a transform-free pass: the stand-alone aperture kernel is cheaper there
                 # -- unless the previous propagation left a pass open: then the aperture becomes the
                 # last operator of that pass (applied while the tile is stored) at no extra traffic
-                if plans.ap is not None:
-                    fuse_ap = (not own_breaker or comp.open_takes_mask()) and plans.ap.fits_line_records(dev.n, dev.precision)
-                else:
-                    aps = [p["aperture"] for p in plans if p["aperture"] is not None]
-                    fuse_ap = (bool(aps) and (not own_breaker or comp.open_takes_mask()) and
-                               all(_aperture_fits_line_records(h, o, dev.n, dev.precision) for h, o in aps))
+                fuse_ap = (plans.ap is not None and (not own_breaker or comp.open_takes_mask()) and
+                           plans.ap.fits_line_records(dev.n, dev.precision))
             if fuse_ap:
                 _queue_apertures(comp, plans)
             breaker = own_breaker or (any_ap and not fuse_ap)
@@ -1326,7 +1185,7 @@ def run(pupil_diameter, wavelength, gridsize, zoom, field, opt_chain, precision=
 
     def on_saved(key, items, plans, wfe):
         item, plan = items[0], plans[0]
-        rec = {"aperture": plan["aperture"][0] if plan["aperture"] else None}
+        rec = {"aperture": plans.aperture(0)}
         if isinstance(wfe, np.ma.MaskedArray):  # Grid Sag / PSD: the host-built map itself
             rec["wfe"] = wfe
         elif wfe is not None:
@@ -1681,7 +1540,7 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
             if not item["save"]:
                 continue
             rec = dict(plan["scalars"])
-            rec["aperture"] = plan["aperture"][0] if plan["aperture"] else None
+            rec["aperture"] = plans.aperture(i)
             for name in outputs:
                 rec[name] = dev.download(i, _WHAT[name])
             rec["_plan"] = plan

@@ -1,6 +1,6 @@
 """Several field points per batch (run_batch / run_broadband / run_sharded with one field per chain) and detector
-images placed at each item's chief ray, on the CPU: the batch planner's array path against the per-item planner for
-off-axis items, per-item fields on the NumPy model of the device against the oracle, the chief-ray origins against
+images placed at each item's chief ray, on the CPU: the batch planner's array arithmetic against the scalar planner of
+tests/plan_np.py for off-axis items, per-item fields on the NumPy model of the device against the oracle, the chief-ray origins against
 paos_amd.raytrace, the placed restatement against brute-force supersampling, and the argument checks."""
 import copy
 import os
@@ -28,28 +28,31 @@ def _lens(name):
 
 
 def _compare_plans(fast, slow, nb):
+    import plan_np
     from paos_amd import run as prun
 
-    assert fast.ap is not None
+    assert fast.ap is not None and fast.ap.on.all()
     blocks, _ = fast.ap.blocks()
     for i in range(nb):
-        h, o = slow[i]["aperture"]
+        h, o = slow[i]
         assert list(blocks[i]) == h.block(obscuration=o), i
-        fh, fo = fast[i]["aperture"]
+        fh, fo = fast.aperture(i), bool(fast.ap.obsc[i])
         assert type(fh) is type(h) and fo == o
     n = 1024
     la, lb = [[0, n] for _ in range(nb)], [[0, n] for _ in range(nb)]
     prun._live_rows_after(fast, la, n)
-    prun._live_rows_after(slow, lb, n)
+    plan_np.live_rows_after(slow, lb, n)
     assert la == lb
-    assert prun._live_cols_of(fast, n) == prun._live_cols_of(slow, n)
+    assert prun._live_cols_of(fast, n) == plan_np.live_cols_of(slow, n)
 
 
 @pytest.mark.parametrize("with_break", [False, True])
 def test_batch_planner_array_path_equals_the_per_item_planner_off_axis(with_break):
-    """_plan_batch with the walk's ray arrays: mixed on- and off-axis items (missing centres fall back on the chief ray,
-    radii shrink with the slopes) are planned with array arithmetic, and every number equals _plan_host's; a
-    coordinate break in front moves the rays of every item exactly as _plan_host moves them."""
+    """_plan_surface with the walk's ray arrays: mixed on- and off-axis items (missing centres fall back on the chief ray,
+    radii shrink with the slopes) are planned with array arithmetic, and every number equals the scalar planner's
+    (tests/plan_np.py); a coordinate break in front moves the rays of every item exactly as the scalar planner moves
+    them."""
+    import plan_np
     from paos_amd import run as prun
     from paos_amd.abcd import ABCD
 
@@ -57,9 +60,8 @@ def test_batch_planner_array_path_equals_the_per_item_planner_off_axis(with_brea
     rng = np.random.default_rng(5)
     fields = [{"us": 0.0, "ut": 0.0}, {"us": 0.0, "ut": 1.2e-5}, SYNTH, {"us": TIE, "ut": -TIE}, {"us": -2e-3, "ut": 0.0}]
     fields = [fields[i % len(fields)] for i in range(nb)]
-    fast_states = [prun._Item(1.0, 1e-6, n, 4, f) for f in fields]
-    slow_states = [prun._Item(1.0, 1e-6, n, 4, f) for f in fields]
-    rays = prun._Rays(fast_states)
+    slow_rays = [plan_np.Ray(f) for f in fields]
+    rays = prun._Rays(fields)
     dxs = [4.0 / n * (1 + 0.01 * i) for i in range(nb)]
     dys = [4.0 / n * (1 + 0.02 * i) for i in range(nb)]
     wls = [1e-6] * nb
@@ -79,22 +81,21 @@ def test_batch_planner_array_path_equals_the_per_item_planner_off_axis(with_brea
                           "ABCDt": abcd, "ABCDs": abcd})
         surfaces.append(items)
     for items in surfaces:
-        fast = prun._plan_batch(fast_states, items, n, dxs, dys, wls, lambda i: 0.5, rays=rays)
-        slow = [prun._plan_host(st, it, n, dxs[i], dys[i], wls[i], lambda: 0.5)
-                for i, (st, it) in enumerate(zip(slow_states, items))]
-        for i, st in enumerate(slow_states):
-            assert rays.vt[i].tolist() == st.vt.tolist() and rays.vs[i].tolist() == st.vs.tolist(), i
-            assert bool(rays.still[i]) == st.still
+        fast = prun._plan_surface(items, n, dxs, dys, wls, lambda i: 0.5, rays)
+        slow = [plan_np.plan_aperture(r, it, n, dxs[i], dys[i]) for i, (r, it) in enumerate(zip(slow_rays, items))]
+        for i, r in enumerate(slow_rays):
+            assert rays.vt[i].tolist() == r.vt.tolist() and rays.vs[i].tolist() == r.vs.tolist(), i
+            assert bool(rays.still[i]) == r.still
         if items[0]["type"] != "Coordinate Break":
             _compare_plans(fast, slow, nb)
         # the ray update of the walk: one stacked A @ v == the per-item products
         col = [it["ABCDt"] for it in items]
         rays.advance(col, col)
-        for st in slow_states:
-            if not st.still:
-                st.vt, st.vs = col[0]() @ st.vt, col[0]() @ st.vs
-        for i, st in enumerate(slow_states):
-            assert rays.vt[i].tolist() == st.vt.tolist() and rays.vs[i].tolist() == st.vs.tolist(), i
+        for r in slow_rays:
+            if not r.still:
+                r.advance(col[0], col[0])
+        for i, r in enumerate(slow_rays):
+            assert rays.vt[i].tolist() == r.vt.tolist() and rays.vs[i].tolist() == r.vs.tolist(), i
     assert not rays.all_still()
 
 

@@ -226,10 +226,9 @@ def _planned_box(shape, blocks, n):
     """The rows and columns the host would have the start write (run.py: _start_field): rows, cols per item, or None
     where the walk would write whole fields."""
     from paos_amd import run as prun
-    from paos_amd.aperture import EllipticalAperture, RectangularAperture
 
-    cls = EllipticalAperture if shape == _lib().SHAPE_ELLIPSE else RectangularAperture
-    plans = [{"aperture": (cls((b[1], b[2]), b[3], b[4], b[5]), bool(b[6]))} for b in blocks]
+    plans = prun._Plans({"stop": False, "zernike": None, "phase_map": None} for _ in blocks)
+    plans.ap = prun._SurfaceApertures.from_blocks(shape, blocks)
     rows = [[0, n] for _ in plans]
     prun._live_rows_after(plans, rows, n)
     if not (all(r[0] > 0 or r[1] < n for r in rows) and all(r[0] < r[1] for r in rows)):

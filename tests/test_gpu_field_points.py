@@ -180,3 +180,63 @@ def test_airs_ch0_broadband_at_the_chief_rays_against_the_oracle():
     assert want.max() > 0.0
     e, e2 = rel_err(got["image"], want), l2_rel_err(got["image"], want)
     assert e < PSF_TOL and e2 < PSF_TOL, (e, e2)
+
+
+def _partly_on_chains():
+    """Stop, lens, a slit at its focus, lens, image plane, for three items whose slits differ: an ellipse, an aperture with
+    a NaN radius (the reference applies none), a rectangle.  The slit is saved and a propagation follows it; the pass that
+    brings the field to the focus is still open there, so the slits ride on it as its last operator."""
+    from paos_amd.abcd import ABCD
+
+    def surface(num, kind, name, thickness=0.0, curvature=0.0, **extra):
+        item = {"num": num, "type": kind, "name": name, "is_stop": False, "save": False,
+                "ABCDt": ABCD(thickness=thickness, curvature=curvature), "ABCDs": ABCD(thickness=thickness, curvature=curvature)}
+        item.update(extra)
+        return item
+
+    def aperture(**geo):
+        return dict({"shape": "elliptical", "type": "aperture", "xc": 0.0, "yc": 0.0}, **geo)
+
+    slits = [aperture(xrad=3.0e-4, yrad=2.0e-4), aperture(xrad=float("nan"), yrad=2.0e-4),
+             aperture(shape="rectangular", xrad=5.0e-4, yrad=3.0e-4)]
+    return [{1: surface(1, "Standard", "STOP", is_stop=True, save=True, aperture=aperture(xrad=0.5, yrad=0.5)),
+             2: surface(2, "Paraxial Lens", "L1", thickness=10.0, curvature=0.1),
+             3: surface(3, "Standard", "SLIT", thickness=10.0, save=True, aperture=slit),
+             4: surface(4, "Paraxial Lens", "L2", thickness=10.0, curvature=0.1),
+             5: surface(5, "Standard", "IMAGE_PLANE", save=True)} for slit in slits]
+
+
+def test_one_surface_with_an_ellipse_no_aperture_and_a_rectangle():
+    """1024^2 fp64 is the smallest grid at which apertures ride on a pass as line records.  Three items whose apertures at
+    one surface are an ellipse, none (a NaN radius) and a rectangle share every launch: each item's fields equal those of
+    the same item run alone, bit for bit, and the lean walk reports the ordinary walk's powers -- both are fp64 sums of
+    the same 2^20 non-negative terms, associated differently by the two reductions (trees of depth ~20: a few 1e-15
+    relative each), so 1e-13 relative, the bound the lean walk has been held to since it exists (test_gpu_r3.py)."""
+    from paos_amd import _lib
+    from paos_amd.run import run_batch
+
+    n, on_axis = 1024, {"us": 0.0, "ut": 0.0}
+    chains = _partly_on_chains()
+    wls = [1.0e-6, 1.1e-6, 1.2e-6]
+    stats = {}
+    whole = run_batch(1.0, wls, n, 4, on_axis, chains, outputs=("wfo",), stats=stats)
+    for i in range(3):
+        own = {}
+        alone = run_batch(1.0, [wls[i]], n, 4, on_axis, [chains[i]], outputs=("wfo",), stats=own)[0]
+        assert sorted(alone) == sorted(whole[i]) == [1, 3, 5] and own == stats
+        for k in alone:
+            assert np.array_equal(alone[k]["wfo"], whole[i][k]["wfo"]), (i, k)
+            assert alone[k]["power"] == whole[i][k]["power"], (i, k)
+        assert np.abs(whole[i][5]["wfo"]).max() > 0.0
+    # the three slits did three different things: the one that is off passes everything
+    passed = [whole[i][3]["power"] / whole[i][1]["power"] for i in range(3)]
+    assert passed[0] < 0.999 and passed[2] < 0.999 and passed[0] != passed[2] and abs(passed[1] - 1.0) < 1e-12
+    dev = _lib.DeviceFields(n, 3)
+    try:
+        lean = run_batch(1.0, wls, n, 4, on_axis, chains, outputs=(), dev=dev, keep_psf=True)
+        for i in range(3):
+            for k in (1, 3, 5):
+                print(f"item {i} surface {k}: lean power {lean[i][k]['power']!r}, ordinary {whole[i][k]['power']!r}")
+                assert abs(lean[i][k]["power"] - whole[i][k]["power"]) <= 1e-13 * whole[i][k]["power"], (i, k)
+    finally:
+        dev.close()

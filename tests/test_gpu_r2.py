@@ -314,7 +314,7 @@ def test_line_records_never_overflow_when_the_host_accepts_an_aperture():
     from paos_amd.aperture import EllipticalAperture
     from paos_amd.passes import PassCompiler
     from paos_amd.planner import PilotBeam
-    from paos_amd.run import _aperture_fits_line_records
+    from paos_amd.run import _SurfaceApertures
 
     n, nb = 4096, 8
     rng = np.random.default_rng(11)
@@ -332,7 +332,7 @@ def test_line_records_never_overflow_when_the_host_accepts_an_aperture():
             if rng.random() < 0.5:
                 xc, yc = n / 2 + rng.uniform(-3, 3), n / 2 + rng.uniform(-3, 3)
             h = EllipticalAperture((xc, yc), a, b)
-            if _aperture_fits_line_records(h, False, n, "fp64"):
+            if _SurfaceApertures.from_blocks(_lib.SHAPE_ELLIPSE, [h.block(obscuration=False)]).fits_line_records(n, "fp64"):
                 handles.append(h)
         tried += nb
         dev.fill(1.0 + 0.5j)

@@ -1140,12 +1140,14 @@ def test_zernike_right_behind_the_start_reads_one_field_per_group_of_copies():
 
 
 def test_batch_planner_equals_the_per_item_planner():
-    """Round 5: ``run._plan_batch`` plans the apertures of a whole batch with array arithmetic.  Against ``_plan_host`` item by
-    item, on random batches -- ellipses and rectangles, apertures and obscurations, missing centres, different sampling per
-    item: the parameter blocks, the line-record test, the live rows and the handles' numbers are identical (==, not close);
-    a non-finite radius skips the aperture for that item only; an aperture that misses the grid raises the reference's
-    TypeError; a batch with a coordinate break or an off-axis item takes the per-item path and still agrees."""
+    """``run._plan_surface`` plans the apertures of a whole batch with array arithmetic.  Against the scalar planner of one
+    wavefront (tests/plan_np.py: the reference's formulas) item by item, on random batches -- ellipses and rectangles,
+    apertures and obscurations, missing centres, different sampling per item: the parameter blocks, the line-record test,
+    the live rows and the handles' numbers are identical (==, not close); a non-finite radius skips the aperture for that
+    item only; an aperture that misses the grid raises the reference's TypeError; a batch with an off-axis item still
+    agrees."""
     import paos_amd.run as prun
+    import plan_np
     from paos_amd.abcd import ABCD
 
     rng = np.random.default_rng(11)
@@ -1162,49 +1164,187 @@ def test_batch_planner_equals_the_per_item_planner():
                         "ABCDt": ABCD(thickness=0.1), "ABCDs": ABCD(thickness=0.1)})
         return out
 
-    def both(items, states):
+    def both(items, fields):
         dxs = [4.0 / n * (1 + 0.01 * i) for i in range(nb)]
         dys = [4.0 / n * (1 + 0.02 * i) for i in range(nb)]
         wls = [1e-6] * nb
-        fast = prun._plan_batch(states, items, n, dxs, dys, wls, lambda i: 0.5)
-        slow = [prun._plan_host(st, it, n, dxs[i], dys[i], wls[i], lambda: 0.5) for i, (st, it) in enumerate(zip(states, items))]
+        fast = prun._plan_surface(items, n, dxs, dys, wls, lambda i: 0.5, prun._Rays(fields))
+        slow = [plan_np.plan_aperture(plan_np.Ray(f), it, n, dxs[i], dys[i]) for i, (f, it) in enumerate(zip(fields, items))]
         return fast, slow
 
-    on_axis = [prun._Item(1.0, 1e-6, n, 4, {"us": 0.0, "ut": 0.0}) for _ in range(nb)]
+    on_axis = [{"us": 0.0, "ut": 0.0} for _ in range(nb)]
     for shape in ("elliptical", "rectangular"):
         for kind_type in ("aperture", "obscuration"):
             for nan_centre in (False, True):
-                fast, slow = both(items_of(shape, kind_type, nan_centre), on_axis)
-                assert fast.ap is not None
+                items = items_of(shape, kind_type, nan_centre)
+                fast, slow = both(items, on_axis)
+                assert fast.ap is not None and fast.ap.on.all()
                 blocks, codes = fast.ap.blocks()
                 for i in range(nb):
-                    h, o = slow[i]["aperture"]
+                    h, o = slow[i]
                     assert list(blocks[i]) == h.block(obscuration=o), (shape, kind_type, i)
                     assert codes[i] == (_lib.SHAPE_ELLIPSE if shape == "elliptical" else _lib.SHAPE_RECT)
-                    fh, fo = fast[i]["aperture"]
+                    fh, fo = fast.aperture(i), bool(fast.ap.obsc[i])
                     assert fo == o and type(fh) is type(h) and fh.block(obscuration=fo) == h.block(obscuration=o)
-                    assert fast[i]["stop"] == slow[i]["stop"]
+                    assert fast[i]["stop"] == bool(items[i]["is_stop"])
                 assert fast.ap.fits_line_records(n, "fp64") == all(
-                    prun._aperture_fits_line_records(*slow[i]["aperture"], n, "fp64") for i in range(nb))
+                    plan_np.fits_line_records(*slow[i], n, "fp64") for i in range(nb))
                 la, lb = [[0, n] for _ in range(nb)], [[0, n] for _ in range(nb)]
                 prun._live_rows_after(fast, la, n)
-                prun._live_rows_after(slow, lb, n)
+                plan_np.live_rows_after(slow, lb, n)
                 assert la == lb
                 assert fast.summary() == (True, False, False, True)
     # one item without a finite radius: no aperture for that item, handles for the others, same as item by item
     fast, slow = both(items_of("elliptical", "aperture", bad_radius=5), on_axis)
-    assert fast.ap is None and fast[5]["aperture"] is None and slow[5]["aperture"] is None
-    assert all(fast[i]["aperture"][0].block() == slow[i]["aperture"][0].block() for i in range(nb) if i != 5)
+    assert fast.ap.on.tolist() == [i != 5 for i in range(nb)]
+    assert fast.aperture(5) is None and slow[5] is None
+    assert fast.ap.blocks()[0].tolist() == [plan_np.block_of(ap) for ap in slow]
+    assert all(fast.aperture(i).block() == slow[i][0].block() for i in range(nb) if i != 5)
     # an aperture whose box misses the grid: the reference fails on `u *= None`
     far = items_of("elliptical", "aperture")
     far[3]["aperture"]["xc"] = 50.0
     with pytest.raises(TypeError):
         both(far, on_axis)
-    # an off-axis item: the per-item path, which scales the radii by the ray slopes (run.py:97-108)
-    off = [prun._Item(1.0, 1e-6, n, 4, {"us": 0.01 if i == 2 else 0.0, "ut": 0.0}) for i in range(nb)]
+    # an off-axis item: the radii are scaled by the ray slopes (run.py:97-108)
+    off = [{"us": 0.01 if i == 2 else 0.0, "ut": 0.0} for i in range(nb)]
     fast, slow = both(items_of("elliptical", "aperture"), off)
-    assert fast.ap is None
-    assert all(fast[i]["aperture"][0].block() == slow[i]["aperture"][0].block() for i in range(nb))
+    assert fast.ap.on.all()
+    assert fast.ap.blocks()[0].tolist() == [plan_np.block_of(ap) for ap in slow]
+    assert all(fast.aperture(i).block() == slow[i][0].block() for i in range(nb))
+
+
+def _zernike_item(i, abcd, orthonorm=False):
+    return {"type": "Zernike", "is_stop": False, "save": False, "ABCDt": abcd, "ABCDs": abcd, "Zindex": np.arange(0, 10 + i % 2),
+            "Z": np.linspace(0.0, 1e-8, 10 + i % 2), "Zordering": "noll" if i % 2 else "standard", "Znormalize": True,
+            "Zradius": float("nan") if i % 3 else 0.4, "Zorigin": "x", "Zorthonorm": orthonorm}
+
+
+def test_one_planner_call_serves_items_of_different_kinds():
+    """A batch whose items differ in kind at one surface -- Standard, Zernike, Coordinate Break, every one with an aperture,
+    on and off axis: the break moves the rays of its items only, every aperture is the scalar planner's (==), and the
+    Zernike items get their own tables, radius (the given one, else the beam's), sampling and wavelength."""
+    import paos_amd.run as prun
+    import plan_np
+    from paos_amd.abcd import ABCD
+    from paos_amd.zernike import zernike_tables
+
+    n, nb = 1024, 9
+    rng = np.random.default_rng(23)
+    tie = 94906267.0 * 2.0 ** -40
+    fields = [{"us": 0.0, "ut": 0.0}, {"us": 3.0e-4, "ut": -5.0e-4}, {"us": tie, "ut": -tie}] * 3
+    dxs = [4.0 / n * (1 + 0.01 * i) for i in range(nb)]
+    dys = [4.0 / n * (1 + 0.02 * i) for i in range(nb)]
+    wls = [1e-6 * (1 + 0.1 * i) for i in range(nb)]
+    abcd = ABCD(thickness=0.3, curvature=0.7)
+    kinds = ["Standard", "Zernike", "Coordinate Break", "Zernike", "Coordinate Break", "Standard", "Zernike", "Standard",
+             "Coordinate Break"]
+    items = []
+    for i, kind in enumerate(kinds):
+        it = _zernike_item(i, abcd) if kind == "Zernike" else {"type": kind, "is_stop": bool(i % 2), "save": False,
+                                                               "ABCDt": abcd, "ABCDs": abcd}
+        if kind == "Coordinate Break":
+            it.update(xdec=1e-3 * i, ydec=float("nan"), xrot=0.2 * i, yrot=-0.15)
+        it["aperture"] = {"shape": "rectangular" if i % 4 == 0 else "elliptical", "type": "aperture" if i % 3 else "obscuration",
+                          "xc": float("nan") if i % 2 else float(rng.normal(0, 0.01)), "yc": float(rng.normal(0, 0.01)),
+                          "xrad": float(rng.uniform(0.2, 0.6)), "yrad": float(rng.uniform(0.2, 0.6))}
+        items.append(it)
+    rays = prun._Rays(fields)
+    plans = prun._plan_surface(items, n, dxs, dys, wls, lambda i: 0.5 + i, rays)
+    slow_rays = [plan_np.Ray(f) for f in fields]
+    slow = [plan_np.plan_aperture(r, it, n, dxs[i], dys[i]) for i, (r, it) in enumerate(zip(slow_rays, items))]
+    for i, r in enumerate(slow_rays):
+        assert rays.vt[i].tolist() == r.vt.tolist() and rays.vs[i].tolist() == r.vs.tolist(), i
+        assert bool(rays.still[i]) == r.still
+        if kinds[i] != "Coordinate Break":  # untouched: still what the field point started them as
+            assert rays.vt[i].tolist() == [0.0, fields[i]["ut"]] and rays.vs[i].tolist() == [0.0, fields[i]["us"]]
+    assert plans.ap.on.all()
+    assert plans.ap.blocks()[0].tolist() == [plan_np.block_of(ap) for ap in slow]
+    for i in range(nb):
+        assert type(plans.aperture(i)) is type(slow[i][0])
+    la, lb = [[0, n] for _ in range(nb)], [[0, n] for _ in range(nb)]
+    prun._live_rows_after(plans, la, n)
+    plan_np.live_rows_after(slow, lb, n)
+    assert la == lb
+    assert plans.summary() == (True, True, False, True)
+    for i, (it, p) in enumerate(zip(items, plans)):
+        assert p["stop"] == bool(it["is_stop"]) and p["phase_map"] is None
+        if kinds[i] != "Zernike":
+            assert p["zernike"] is None
+            continue
+        z = p["zernike"]
+        m, nn, norm = zernike_tables(len(it["Zindex"]), it["Zordering"], True)
+        assert np.array_equal(z["m"], m) and np.array_equal(z["n"], nn) and np.array_equal(z["norm"], norm)
+        assert z["radius"] == (0.4 if i % 3 == 0 else 0.5 + i)
+        assert (z["dx"], z["dy"], z["wl"], z["origin"], z["pupil"]) == (dxs[i], dys[i], wls[i], "x", None)
+        assert np.array_equal(z["Z"], it["Z"])
+
+
+def test_a_partly_on_batch_of_mixed_shapes_follows_the_scalar_rules():
+    """Some items with an aperture and some without (no entry, or a radius that is not finite), ellipses and rectangles,
+    clear and obscuring, on and off axis: the one record's blocks are the per-item blocks with zero rows for the items
+    without, and ``fits_line_records`` / ``narrow_rows`` / ``live_cols`` / ``start_shape`` give the scalar rules' answers
+    -- on the whole batch and on the sub-batches where those answers differ (all on, all clear, one shape)."""
+    import paos_amd.run as prun
+    import plan_np
+    from paos_amd.abcd import ABCD
+
+    n, nb = 1024, 12
+    rng = np.random.default_rng(31)
+    abcd = ABCD(thickness=0.1)
+    fields = [{"us": 0.0, "ut": 0.0}, {"us": 2.0e-3, "ut": -1.0e-3}] * 6
+    dxs = [4.0 / n * (1 + 0.01 * i) for i in range(nb)]
+    dys = [4.0 / n * (1 + 0.02 * i) for i in range(nb)]
+
+    def item(i, shape, kind_type="aperture", rad=None, **geo):
+        ap = {"shape": shape, "type": kind_type, "xc": float(rng.normal(0, 0.01)), "yc": float("nan") if i % 2 else 0.01,
+              "xrad": float(rng.uniform(0.02, 0.3)) if rad is None else rad, "yrad": float(rng.uniform(0.02, 0.3))}
+        ap.update(geo)
+        return {"type": "Standard", "is_stop": False, "save": False, "aperture": ap, "ABCDt": abcd, "ABCDs": abcd}
+
+    none = {"type": "Standard", "is_stop": False, "save": False, "ABCDt": abcd, "ABCDs": abcd}
+    whole = [item(0, "elliptical"), dict(none), item(2, "rectangular"), item(3, "elliptical", rad=float("nan")),
+             item(4, "elliptical", "obscuration"), item(5, "rectangular"), dict(none, aperture=None), item(7, "elliptical", rad=0.9),
+             item(8, "rectangular", "obscuration"), item(9, "elliptical"), item(10, "rectangular", yrad=float("inf")),
+             item(11, "elliptical")]
+    on = [i not in (1, 3, 6, 10) for i in range(nb)]
+    picks = {"whole": list(range(nb)), "all on": [0, 2, 4, 5, 7, 8, 9, 11], "clear": [0, 2, 5, 9, 11], "ellipses": [0, 9, 11],
+             "rectangles": [2, 5], "small clear ellipses and rectangles": [0, 2, 5, 9, 11, 1]}
+    answers = set()
+    for name, pick in picks.items():
+        items, fl = [whole[i] for i in pick], [fields[i] for i in pick]
+        dx, dy = [dxs[i] for i in pick], [dys[i] for i in pick]
+        plans = prun._plan_surface(items, n, dx, dy, [1e-6] * len(pick), lambda i: 0.5, prun._Rays(fl))
+        slow = [plan_np.plan_aperture(plan_np.Ray(f), it, n, dx[k], dy[k]) for k, (f, it) in enumerate(zip(fl, items))]
+        assert plans.ap.on.tolist() == [on[i] for i in pick] == [ap is not None for ap in slow], name
+        blocks, codes = plans.ap.blocks()
+        assert blocks.tolist() == [plan_np.block_of(ap) for ap in slow], name
+        for k, ap in enumerate(slow):
+            if ap is None:
+                assert plans.aperture(k) is None and not blocks[k].any()
+            else:
+                assert type(plans.aperture(k)) is type(ap[0]) and plans.aperture(k).block(obscuration=ap[1]) == blocks[k].tolist()
+                assert codes[k] == plan_np.start_shape([ap])
+        fits = plans.ap.fits_line_records(n, "fp64")
+        assert fits == plan_np.all_fit_line_records(slow, n, "fp64"), name
+        assert not plans.ap.fits_line_records(512, "fp64") and not plans.ap.fits_line_records(n, "fp32")
+        la, lb = [[0, n] for _ in pick], [[0, n] for _ in pick]
+        plans.ap.narrow_rows(la, n)
+        plan_np.live_rows_after(slow, lb, n)
+        assert la == lb, name
+        cols = plans.ap.live_cols(n)
+        assert cols == plan_np.live_cols_of(slow, n) == prun._live_cols_of(plans, n), name
+        shape = plans.ap.start_shape()
+        assert shape == plan_np.start_shape(slow), name
+        assert plans.summary() == (False, False, False, True)
+        answers.add((name, fits, cols is not None, shape))
+    # (the cases do tell the rules apart: each answer is taken both ways)
+    assert {a[1] for a in answers} == {True, False} and {a[2] for a in answers} == {True, False}
+    assert {a[3] for a in answers} == {None, _lib.SHAPE_ELLIPSE, _lib.SHAPE_RECT}
+    assert any(r != [0, n] for r in la)
+    # nobody carries an aperture: no record at all
+    plans = prun._plan_surface([whole[1], whole[3], whole[6]], n, dxs[:3], dys[:3], [1e-6] * 3, lambda i: 0.5,
+                               prun._Rays(fields[:3]))
+    assert plans.ap is None and plans.summary() == (False, False, False, False) and plans.aperture(1) is None
 
 
 def test_gate_arrays_are_remembered_per_column_and_forgotten_when_a_matrix_is_edited():
