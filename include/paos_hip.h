@@ -397,6 +397,12 @@ int paos_copy_yardstick(paos_ctx* ctx, int reps, double* ms_per_launch, double* 
  * wfo.py:246-276, riding on a pass as line records) found its records in one of the context's kept sets
  * (*found) and how often it had to render them (*rendered).  bench.py reports both per step of its walked sweep. */
 int paos_record_set_stats(paos_ctx* ctx, unsigned long long* found, unsigned long long* rendered);
+/* Measurement / test aid: how many frugal pass launches of the context, since it was created, ran on the central-half
+ * build of their shape (*central: every item of the launch's first pass loads positions inside [n / 4, 3 n / 4), so
+ * the slot and the first butterfly layer in front skip the outer positions, which are exact zeros) and how many on
+ * the ordinary build (*plain).  PAOS_CENTRAL_HALF=0 / 1 in the environment when the context is created switches the
+ * central-half builds off / on; results are equal as numbers either way. */
+int paos_central_half_stats(paos_ctx* ctx, unsigned long long* central, unsigned long long* plain);
 /* Measurement / test aid: on = 0 makes every pass process every tile (no dead-line pruning). */
 int paos_ctx_set_pruning(paos_ctx* ctx, int on);
 int paos_run_passes_live(paos_ctx* ctx, const paos_pass* passes, int n_passes, const double* blocks,

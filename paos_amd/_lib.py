@@ -100,6 +100,7 @@ SYMBOLS = {
     "paos_run_passes": (ctypes.c_int, [_c_ctx, ctypes.POINTER(Pass), ctypes.c_int, _dbl_p, ctypes.c_int]),
     "paos_copy_yardstick": (ctypes.c_int, [_c_ctx, ctypes.c_int, _dbl_p, _dbl_p]),
     "paos_record_set_stats": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
+    "paos_central_half_stats": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
     "paos_ctx_set_pruning": (ctypes.c_int, [_c_ctx, ctypes.c_int]),
     "paos_run_passes_live": (ctypes.c_int, [_c_ctx, ctypes.POINTER(Pass), ctypes.c_int, _dbl_p, ctypes.c_int, _dbl_p]),
     "paos_zernike": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, _dbl_p, _dbl_p, ctypes.c_int, _dbl_p]),
@@ -700,6 +701,13 @@ class DeviceFields:
         self._check(self._lib.paos_record_set_stats(self._ctx, ctypes.byref(found), ctypes.byref(rendered)),
                     "paos_record_set_stats")
         return int(found.value), int(rendered.value)
+
+    def central_half_stats(self):
+        """(central, plain): frugal pass launches on the central-half build of their shape / on the ordinary build, since creation."""
+        central, plain = ctypes.c_ulonglong(0), ctypes.c_ulonglong(0)
+        self._check(self._lib.paos_central_half_stats(self._ctx, ctypes.byref(central), ctypes.byref(plain)),
+                    "paos_central_half_stats")
+        return int(central.value), int(plain.value)
 
     def set_pruning(self, on):
         """Dead-line pruning of the pass programs on (default) / off -- results are identical."""

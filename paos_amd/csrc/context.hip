@@ -282,6 +282,8 @@ int paos_ctx_create(int device, int n, int batch, int precision, paos_ctx** out)
   if ((e = hipSetDevice(device)) != hipSuccess) return bail(e, "hipSetDevice");
   if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
   if (const char* pad = getenv("PAOS_LDS_PAD")) c->lds_pad = (size_t)std::max(0, std::atoi(pad));
+  if (env_is("PAOS_CENTRAL_HALF", '0')) c->central_half = false;
+  if (env_is("PAOS_CENTRAL_HALF", '1')) c->central_half = true;
   if ((e = hipMalloc(&c->dyn_scale, (size_t)batch * sizeof(double))) != hipSuccess) return bail(e, "hipMalloc(dyn_scale)");
   {
     std::vector<double> ones((size_t)batch, 1.0);
@@ -476,6 +478,13 @@ int paos_record_set_stats(paos_ctx* c, unsigned long long* found, unsigned long 
   if (!c || !found || !rendered) return fail(c, PAOS_EINVAL, "bad record-set request");
   *found = c->mask_hits;
   *rendered = c->mask_rendered;
+  return PAOS_OK;
+}
+
+int paos_central_half_stats(paos_ctx* c, unsigned long long* central, unsigned long long* plain) {
+  if (!c || !central || !plain) return fail(c, PAOS_EINVAL, "bad central-half request");
+  *central = c->central_launches;
+  *plain = c->plain_launches;
   return PAOS_OK;
 }
 

@@ -277,6 +277,42 @@ __device__ __forceinline__ void dft16_lf(cx<T>* v) {
   for (int k2 = 0; k2 < 4; ++k2) v[3 + 4 * k2] = o[k2];
 }
 
+// dft16_lf of a line whose outer quarters are exact zeros: v[0..3] = v[12..15] = {0, 0} (the first stage of a pass that loads
+// the central half of its positions at most -- frugal_pass.h: CH).  Each first-layer radix-4 then has the inputs (0, a, b, 0),
+// and what dft<4> makes of them -- t0 = 0 + b, t1 = 0 - b, t2 = a + 0, t3 = a - 0 -- is b, -b, a, a: four complex additions,
+// in the order and with the operands of the full butterfly, so the live sums keep their bits (an exact zero may change its
+// sign).  The second layer is dft16_lf's.  Forward transforms only (the pass kernel conjugates around an inverse one).
+template <int DIR, typename T>
+__device__ __forceinline__ void dft16_lf_central(cx<T>* v) {
+  static_assert(DIR > 0, "the pass kernel runs forward transforms only");
+  cx<T> y[16];
+#pragma unroll
+  for (int n2 = 0; n2 < 4; ++n2) {
+    const cx<T> a = v[4 + n2], b = v[8 + n2];
+    const cx<T> nb = {-b.x, -b.y};
+    y[0 * 4 + n2] = cadd(b, a);     // t0 + t2
+    y[1 * 4 + n2] = sub_ib(nb, a);  // t1 - i t3
+    y[2 * 4 + n2] = csub(b, a);     // t0 - t2
+    y[3 * 4 + n2] = add_ib(nb, a);  // t1 + i t3
+  }
+  cx<T> o[4];
+  {
+    cx<T> b[4] = {y[0], y[1], y[2], y[3]};
+    dft<4, DIR>(b);
+#pragma unroll
+    for (int k2 = 0; k2 < 4; ++k2) v[4 * k2] = b[k2];
+  }
+  lf_twiddled_dft4<1, DIR>(y + 4, o);
+#pragma unroll
+  for (int k2 = 0; k2 < 4; ++k2) v[1 + 4 * k2] = o[k2];
+  lf_twiddled_dft4<2, DIR>(y + 8, o);
+#pragma unroll
+  for (int k2 = 0; k2 < 4; ++k2) v[2 + 4 * k2] = o[k2];
+  lf_twiddled_dft4<3, DIR>(y + 12, o);
+#pragma unroll
+  for (int k2 = 0; k2 < 4; ++k2) v[3 + 4 * k2] = o[k2];
+}
+
 // In-place DFT of R points held in registers, natural order in and out.
 template <int R, int DIR, typename T>
 __device__ __forceinline__ void dft(cx<T>* v) {
@@ -428,7 +464,9 @@ __device__ __forceinline__ void apply_twiddle_chain(cx<T>* v, cx<T> w1) {
 // ``w1_last`` (optional): the base twiddles tw[t + s TL] of the butterflies s = 0 .. TPT - 1 a thread runs in the LAST stage
 // (N = 4096: one, k = t; N = 2048: two) -- per-thread constants the caller keeps in registers, so that the stage needs no
 // table in LDS (the four-per-CU shapes of frugal_pass.h only fit without the 4 KiB table).
-template <typename T, int N, int E, int DIR, bool SPLIT, int NS = 1, int FR = 0>
+// CH != 0 (the first stage, NS = 1, of 16-point-per-thread complex128 lines): slots 0..3 and 12..15 hold exact zeros
+// (dft16_lf_central); the later stages are the ordinary ones.
+template <typename T, int N, int E, int DIR, bool SPLIT, int NS = 1, int FR = 0, int CH = 0>
 __device__ __forceinline__ void fft_stages(cx<T>* v, void* lds, int t,
                                            const cx<T>* __restrict__ tw, const cx<double>* circle = nullptr,
                                            const cx<T>* w1_last = nullptr) {
@@ -464,7 +502,10 @@ __device__ __forceinline__ void fft_stages(cx<T>* v, void* lds, int t,
     }
     // (timing diagnostics, results wrong: PAOS_DIAG bit 3 drops the butterflies of every FIRST stage, bit 4 of every
     // LAST stage -- what a zero-aware first / last stage could save at the very most, profiles/r04_zero_aware_stages.txt)
-    if constexpr (!(((PAOS_DIAG & 8) && NS == 1) || ((PAOS_DIAG & 16) && S::LAST))) dft<R, DIR>(v + s * R);
+    if constexpr (CH != 0 && NS == 1 && PAOS_LF16 != 0) {  // (PAOS_LF16 = 0 variant builds: the full butterfly, on the zeros too)
+      static_assert(R == 16 && TPT == 1, "central-half first stage: one 16-point butterfly per thread");
+      dft16_lf_central<DIR>(v);
+    } else if constexpr (!(((PAOS_DIAG & 8) && NS == 1) || ((PAOS_DIAG & 16) && S::LAST))) dft<R, DIR>(v + s * R);
     // (PAOS_TAIL_FENCE = 0, experiment: no fence behind the LAST stage's butterflies, so that the scheduler may start
     // the tile's stores while the remaining outputs are still being computed)
     if constexpr (!(S::LAST && PAOS_TAIL_FENCE == 0)) PAOS_FENCE();
@@ -524,7 +565,7 @@ __device__ __forceinline__ void fft_stages(cx<T>* v, void* lds, int t,
       }
     }
     PAOS_FENCE_IF(1);
-    fft_stages<T, N, E, DIR, SPLIT, NS * R, FR>(v, lds, t, tw, circle, w1_last);
+    fft_stages<T, N, E, DIR, SPLIT, NS * R, FR, 0>(v, lds, t, tw, circle, w1_last);
   }
 }
 

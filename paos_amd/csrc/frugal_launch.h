@@ -11,9 +11,17 @@ namespace {
 #ifndef PAOS_SINGLE_ONE_LINE
 #define PAOS_SINGLE_ONE_LINE 1   // 0 (A/B builds): single table passes keep the two-line workgroups whatever they load and store
 #endif
-template <typename T, int N, int AXIS, int KPRE, int KMID, int NFFT, int STORE = 0, int TAB = 0, int LONG = 0, int ONE = 0>
+// Round 11, CH = 1: the central-half build of the shape (frugal_pass.h: frugal_pass_kernel, CH) -- for the launches whose first
+// pass loads positions of [N / 4, 3 N / 4) only (launch_lowered: FrugalArgs::central).  Built for 4096^2 complex128, table
+// slots, KPRE = 1 and the shapes a chain step launches with such a window: the field-storing LONG builds and the one-line
+// single passes.  The PSF-storing LONG build (two-line workgroups; the last column launch of a step loads a quarter too)
+// was built and measured as well: 0.97 -> 1.10 ms per launch, so it keeps the ordinary build (profiles/r11_central_half.md).
+template <typename T, int N, int KPRE, int TAB>
+constexpr bool frugal_central() { return sizeof(T) == 8 && N == 4096 && KPRE == 1 && TAB != 0; }
+template <typename T, int N, int AXIS, int KPRE, int KMID, int NFFT, int STORE = 0, int TAB = 0, int LONG = 0, int ONE = 0, int CH = 0>
 int frugal_launch(paos_ctx* c, const FrugalArgs& args) {
   using C = FftCfg<T, N>;
+  static_assert(CH == 0 || frugal_central<T, N, KPRE, TAB>(), "no central-half build of this shape");
   // Round 5: the launches that run two or three passes of a chain (LONG builds) and store the field are bound by the latency
   // chain of a workgroup -- exchanges, barriers, table reads -- not by bytes (they move a sixteenth of the grid): at 4096^2
   // complex128 they run on ONE-line workgroups of 256 threads, four per CU with one wave each per SIMD instead of two of
@@ -50,7 +58,8 @@ int frugal_launch(paos_ctx* c, const FrugalArgs& args) {
   const dim3 grid(groups, c->batch), block(TILES * LINES * N / C::E);
   constexpr size_t kMaxPad = 8192;
   const size_t lds = frugal_lds_bytes<T, N, LINES, TILES, SPLIT, KPRE, KMID, C::E, STORE, kOcc>() + (c->lds_pad < kMaxPad ? c->lds_pad : kMaxPad);
-  auto kern = frugal_pass_kernel<T, N, C::E, LINES, TILES, AXIS, C::BR, C::BC, SPLIT, KPRE, KMID, NFFT, STORE, TAB, LONG, kOcc>;
+  auto kern = frugal_pass_kernel<T, N, C::E, LINES, TILES, AXIS, C::BR, C::BC, SPLIT, KPRE, KMID, NFFT, STORE, TAB, LONG, kOcc, CH>;
+  ++(CH != 0 ? c->central_launches : c->plain_launches);  // paos_central_half_stats
   return TIMED_LAUNCH(c, kern, grid, block, lds, frugal_lds_bytes<T, N, LINES, TILES, SPLIT, KPRE, KMID, C::E, STORE, kOcc>() + kMaxPad,
                       AXIS == 0 ? PAOS_KERNEL_PASS_ROWS : PAOS_KERNEL_PASS_COLS, c->prof_next_tag, PAOS_FRUGAL_PASS(a));
 }
@@ -64,6 +73,9 @@ int frugal_nfft(paos_ctx* c, const FrugalArgs& a, int nfft) {
       if (nfft < 2) return fail(c, PAOS_EINVAL, "a fused chain starts with a two-transform pass");
 #define PAOS_LONG_CASE(L)                                                           \
   case L:                                                                           \
+    if constexpr (frugal_central<T, N, 1, 1>() && PAOS_LONG_ONE_LINE != 0) {  /* (the one-line builds only) */ \
+      if (a.central && !a.psf && !a.pow_partial) return frugal_launch<T, N, AXIS, 1, 1, 2, 0, 1, L, 0, 1>(c, a);  \
+    }                                                                               \
     if (a.psf) return frugal_launch<T, N, AXIS, 1, 1, 2, 1, 1, L>(c, a);            \
     if (a.pow_partial) return frugal_launch<T, N, AXIS, 1, 1, 2, 2, 1, L>(c, a);    \
     return frugal_launch<T, N, AXIS, 1, 1, 2, 0, 1, L>(c, a);
@@ -84,6 +96,10 @@ int frugal_nfft(paos_ctx* c, const FrugalArgs& a, int nfft) {
       if (a.psf) return nfft >= 2 ? frugal_launch<T, N, AXIS, KPRE, KMID, 2, 1, 1>(c, a) : frugal_launch<T, N, AXIS, KPRE, KMID, 1, 1, 1>(c, a);
       if (a.pow_partial) return nfft >= 2 ? frugal_launch<T, N, AXIS, KPRE, KMID, 2, 2, 1>(c, a) : frugal_launch<T, N, AXIS, KPRE, KMID, 1, 2, 1>(c, a);
       if constexpr (sizeof(T) == 8 && (N == 4096 || N == 2048) && PAOS_LONG_ONE_LINE != 0) {
+        if constexpr (frugal_central<T, N, KPRE, 1>()) {
+          if (a.one_line && a.central && PAOS_SINGLE_ONE_LINE != 0)
+            return nfft >= 2 ? frugal_launch<T, N, AXIS, KPRE, KMID, 2, 0, 1, 0, 1, 1>(c, a) : frugal_launch<T, N, AXIS, KPRE, KMID, 1, 0, 1, 0, 1, 1>(c, a);
+        }
         if (a.one_line && PAOS_SINGLE_ONE_LINE != 0) return nfft >= 2 ? frugal_launch<T, N, AXIS, KPRE, KMID, 2, 0, 1, 0, 1>(c, a) : frugal_launch<T, N, AXIS, KPRE, KMID, 1, 0, 1, 0, 1>(c, a);
       }
       return nfft >= 2 ? frugal_launch<T, N, AXIS, KPRE, KMID, 2, 0, 1>(c, a) : frugal_launch<T, N, AXIS, KPRE, KMID, 1, 0, 1>(c, a);

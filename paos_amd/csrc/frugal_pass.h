@@ -138,6 +138,9 @@ struct FrugalArgs {
   // host only (round 5): a single table pass that moves few bytes -- every item loads and stores at most half of its positions --
   // runs on the one-line workgroups of the fused launches (frugal_launch.h: frugal_launch, ONE)
   int one_line = 0;
+  // host only (round 11): every active item of the launch's first pass loads positions inside [n / 4, 3 n / 4) -- the launch
+  // takes the central-half build of its shape where there is one (frugal_pass_kernel: CH; frugal_launch.h)
+  int central = 0;
 };
 #if PAOS_STAMPS
 #define PAOS_STAMP(i)                                                                              \
@@ -314,7 +317,10 @@ __device__ __forceinline__ cx<float> slot_factor32(const double* g, const double
 // RECS > 0: the aperture line records of the workgroup's RECS lines (first line ``lbase``) were fetched by the kernel
 // before the tile's loads (wave-uniform: scalar registers); RECS < 0: the kernel staged them in LDS (``recs``);
 // RECS = 0: the slot loads its line's record itself.
-template <typename T, int N, int E, int K, typename Map, int PLAIN = 0, bool SHARE = false, int RECS = 0, int TAB = 0>
+// CH != 0 (the table slot in front of the first transform of a launch whose every item loads positions of the central half
+// [N / 4, 3 N / 4) only -- frugal_pass_kernel: CH): elements 0 .. E/4 - 1 and 3 E/4 .. E - 1 are exact zeros for every thread
+// and stay the {0, 0} they are: the aperture weights and the table factors go to elements E/4 .. 3 E/4 - 1 alone.
+template <typename T, int N, int E, int K, typename Map, int PLAIN = 0, bool SHARE = false, int RECS = 0, int TAB = 0, int CH = 0>
 __device__ __forceinline__ void frugal_slot(cx<T>* v, const FrugalSlot& sl, const FrugalPhase* ph,
                                             const Map& m, const cx<double>* circle, bool conj_in, bool conj_out, int tpos,
                                             void* area = nullptr, bool area_busy = false, const MaskLine* recs = nullptr,
@@ -348,6 +354,8 @@ __device__ __forceinline__ void frugal_slot(cx<T>* v, const FrugalSlot& sl, cons
   // order, swap_nibbles(m.t) between the two transforms of a digit-swapped pass
   constexpr int TL = N / E;
   static_assert(TL % 2 == 0, "the checkerboard sign is constant along a thread's elements");
+  static_assert(CH == 0 || (K > 0 && TAB != 0 && sizeof(T) == 8 && E % 4 == 0), "central-half slots: complex128 table slots");
+  constexpr int kFirst = CH != 0 ? E / 4 : 0, kEnd = CH != 0 ? 3 * E / 4 : E;  // the elements that can be non-zero
   const double sc = __dmul_rn(sl.scale, extra_scale);  // (extra_scale: 1 exactly, except behind a deferred stop)
   const int line = Map::kAxis == 0 ? m.row(0) : m.col(0);  // this thread's row (column): constant
   if (sl.mask_on != 0.0) {  // wave-uniform: an aperture rides on this slot
@@ -390,7 +398,7 @@ __device__ __forceinline__ void frugal_slot(cx<T>* v, const FrugalSlot& sl, cons
 #pragma unroll
     for (int j = 0; j < R; ++j) { wa[j] = __dmul_rn(wa[j], ml.lm); wb[j] = __dmul_rn(wb[j], ml.lm); }
 #pragma unroll
-    for (int k = 0; k < E; ++k) {
+    for (int k = kFirst; k < kEnd; ++k) {
       const int pos = tpos + k * TL;
       double w = (pos >= ml.p1 && pos < ml.p2) ? w_in : w_out;
 #pragma unroll
@@ -535,13 +543,13 @@ __device__ __forceinline__ void frugal_slot(cx<T>* v, const FrugalSlot& sl, cons
     // the two-line workgroups keep; 16: +14 %.  profiles/r05_fftbench_fused_variants.txt)
     constexpr int kFence = Map::kLinesPerWorkgroup == 1 ? 4 : PAOS_TABLE_FENCE;
 #pragma unroll
-    for (int k = 0; k < E; ++k) {
+    for (int k = kFirst; k < kEnd; ++k) {
 #if defined(PAOS_DIAG_NOTABLE)  // (timing diagnostic: what the table loads cost -- results wrong)
       apply(k, cx<double>{0.6, 0.8});
 #else
       apply(k, tb[k * TL]);
 #endif
-      if ((k + 1) % kFence == 0) __builtin_amdgcn_sched_barrier(0);
+      if ((k - kFirst + 1) % kFence == 0) __builtin_amdgcn_sched_barrier(0);  // (groups counted from the first element: the last one ends on a fence)
     }
     return;
   }
@@ -659,10 +667,11 @@ __device__ __forceinline__ void stream_store(cx<T>* p, cx<T> v) {
 // transform is folded into the slot that precedes it (frugal_slot multiplies the imaginary part by
 // -f instead of f), the one BEHIND it is an XOR on the sign bit (half the issue cost of an fp64 multiply).
 // FLIP = false: the conjugation behind the transform is left to the slot that follows (frugal_slot: conj_in)
-template <typename T, int N, int E, bool SPLIT, bool FLIP = true>
+// CH != 0: elements 0 .. E/4 - 1 and 3 E/4 .. E - 1 are exact zeros on entry (fft_core.h: dft16_lf_central)
+template <typename T, int N, int E, bool SPLIT, bool FLIP = true, int CH = 0>
 __device__ __forceinline__ void frugal_fft(cx<T>* v, void* lds, int t, const cx<T>* tw, const cx<double>* circle,
                                            double inv, const cx<T>* w1_last = nullptr) {
-  fft_stages<T, N, E, +1, SPLIT, 1, 1>(v, lds, t, tw, circle, w1_last);
+  fft_stages<T, N, E, +1, SPLIT, 1, 1, CH>(v, lds, t, tw, circle, w1_last);
   unpermute_slots<N, E>(v);
   if constexpr (FLIP) {
     const unsigned mask = inv != 0.0 ? 0x80000000u : 0u;
@@ -771,11 +780,22 @@ __device__ __forceinline__ void tile_power_out(double acc, double* scratch, doub
 // same lines, one / two transforms, phases in both of its slots -- whose item records follow this pass's
 // (items[batch + item], items[2 batch + item]): load | slot F slot F | slot F slot [F] | [slot F slot [F]] | store.  The tile never leaves the registers between the
 // two passes: one load, one store, one prologue and one launch less per pair; results are bit-identical.
+// CH != 0 (round 11; 4096-point complex128 table builds with KPRE = 1): the host launches the build only when every active item
+// of the launch's FIRST pass loads positions inside the central half [N / 4, 3 N / 4) -- the quarter windows behind the start
+// box and the apertures of a chain.  A thread's elements sit at t + k N / E, so k < E / 4 and k >= 3 E / 4 are zero for
+// the whole workgroup: the load loop, the aperture and table loops of the first pass's pre slot and the first butterfly
+// layer of its first transform run over k = E/4 .. 3 E/4 - 1 only.  Everything behind that first stage -- the later
+// passes of a LONG launch included -- sees full lines and is the ordinary code.  Every value the CH = 0 build computes
+// is reproduced by the same operations or was an exact zero (whose sign alone may differ in an intermediate).
+// There is NO device-side guard: the build never looks at an outer element, so an item whose [pos_lo, pos_hi) reaches beyond
+// the central half would silently lose those positions.  Whoever sets FrugalArgs::central must have checked every active
+// item of the first pass (passes.hip: launch_lowered is the only place that does).
 template <typename T, int N, int E, int LINES, int TILES, int AXIS, int BR, int BC, bool SPLIT,
-          int KPRE, int KMID, int NFFT, int STORE = 0, int TAB = 0, int LONG = 0, int OCC = 0>
+          int KPRE, int KMID, int NFFT, int STORE = 0, int TAB = 0, int LONG = 0, int OCC = 0, int CH = 0>
 __global__ void __launch_bounds__(TILES* LINES* N / E, (frugal_min_waves<T, N, TILES * LINES * N / E, OCC>()))
     frugal_pass_kernel(PAOS_FRUGAL_PARAMS) {
   static_assert(LONG == 0 || (TAB != 0 && (NFFT == 2 || NFFT == 3) && KPRE == 1 && KMID == 1), "LONG builds: see above");
+  static_assert(CH == 0 || (sizeof(T) == 8 && N == 4096 && E == 16 && TAB != 0 && KPRE == 1 && NFFT <= 2), "CH builds: see above");
   FrugalArgs a;
   a.items = k_items; a.field = k_field; a.pitch = k_pitch; a.item_stride = k_item_stride; a.wg0 = k_wg0;
   a.tw = k_tw; a.psf = k_psf; a.psf_partial = k_psf_partial; a.pow_partial = k_pow_partial; a.dyn_scale = k_dyn_scale; a.live_lo = a.live_hi = 0;
@@ -938,7 +958,15 @@ __global__ void __launch_bounds__(TILES* LINES* N / E, (frugal_min_waves<T, N, T
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  if (plo <= 0 && phi >= N) {  // wave-uniform: the whole line is live
+  if constexpr (CH != 0) {  // [plo, phi) lies inside [N / 4, 3 N / 4): the outer elements are never loaded
+#pragma unroll
+    for (int k = 0; k < E; ++k) v[k] = cx<T>{(T)0, (T)0};
+#pragma unroll
+    for (int k = E / 4; k < 3 * E / 4; ++k) {
+      const int pos = m.t + k * (N / E);
+      if (pos >= plo && pos < phi) v[k] = stream_load<NTL>(at(k));
+    }
+  } else if (plo <= 0 && phi >= N) {  // wave-uniform: the whole line is live
 #pragma unroll
     for (int k = 0; k < E; ++k) v[k] = stream_load<NTL>(at(k));
   } else {
@@ -1065,9 +1093,9 @@ __global__ void __launch_bounds__(TILES* LINES* N / E, (frugal_min_waves<T, N, T
   constexpr bool kShare = PAOS_SHARE_PHASES != 0 && TAB == 0;
   // (with phases in BOTH slots the second sharing loop costs the shape its spill-free register allocation: there
   // only the slot between the transforms shares)
-  frugal_slot<T, N, E, KPRE, decltype(m), kPlainPre, kShare && KMID == 0, 0, TAB>(v, it.pre, it.pre_ph, m, circle, false, inv1, m.t, lds, false);
+  frugal_slot<T, N, E, KPRE, decltype(m), kPlainPre, kShare && KMID == 0, 0, TAB, CH>(v, it.pre, it.pre_ph, m, circle, false, inv1, m.t, lds, false);
   PAOS_STAMP(2);
-  if (ran1) frugal_fft<T, N, E, SPLIT, false>(v, lds, m.t, tw, circle, it.fft1_inv, w1_last);
+  if (ran1) frugal_fft<T, N, E, SPLIT, false, CH>(v, lds, m.t, tw, circle, it.fft1_inv, w1_last);
   PAOS_STAMP(3);
   constexpr bool kShareMid = kShare && KPRE == 0 && KMID < 3;
   frugal_slot<T, N, E, KMID, decltype(m), 0, kShareMid, (kRecMode == 1 ? -1 : kRecs), TAB>(

@@ -170,6 +170,11 @@ struct paos_ctx {
   // context is created): 6 KiB make two of its workgroups too big for one CU but leave room for one of another
   // context's -- two contexts then share every CU one workgroup each (measured: -14 %, profiles/r04_membench6_mixed_kinds.txt)
   size_t lds_pad = 0;
+  // Round 11: launches whose first pass loads positions of the central half [n / 4, 3 n / 4) only take the central-half build
+  // of their shape (frugal_pass.h: CH).  PAOS_CENTRAL_HALF=0 when the context is created switches it off -- read per
+  // context, so that a test can hold an "on" and an "off" context in one process.  (On by default: profiles/r11_central_half.md.)
+  bool central_half = true;
+  unsigned long long central_launches = 0, plain_launches = 0;  // frugal pass launches on CH / ordinary builds (paos_central_half_stats)
   int* mask_overflow = nullptr;    // device counter: partial runs that did not fit (must stay 0)
   double* partial = nullptr;
   double* norm2 = nullptr;

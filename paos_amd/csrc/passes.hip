@@ -319,6 +319,17 @@ int launch_lowered(paos_ctx* c, const paos_pass& p, LoweredPass& lp, const doubl
     }
     a.one_line = light ? 1 : 0;
   }
+  {  // every active item of the FIRST pass loads positions of the central half only: the central-half build of the shape,
+    // where there is one (frugal_launch.h).  Per launch, not per item: one item outside sends the whole launch to the old build.
+    bool central = c->central_half && tables, any = false;
+    for (int it = 0; it < c->batch && central; ++it) {
+      const FrugalItem& fi = lp.items[it];
+      if (fi.active == 0.0) continue;
+      any = true;
+      central = 4.0 * fi.pos_lo >= (double)c->n && 4.0 * fi.pos_hi <= 3.0 * (double)c->n;
+    }
+    a.central = central && any ? 1 : 0;
+  }
   a.fuse = next2 ? 2 + next2->nfft : (next ? next->nfft : 0);  // LONG: the transforms of the passes that ride along
   // (a fused pair runs on the one build whose four slots all read tables)
   const int kpre = next ? 1 : (tables && lp.kpre > 1 ? 1 : lp.kpre), kmid = next ? 1 : (tables && lp.kmid > 1 ? 1 : lp.kmid);

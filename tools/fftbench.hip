@@ -230,7 +230,9 @@ void bench_frugal(const char* name, int batch, int reps, int pad_blocks) {
 // Round 5: the fused launches of the separable pass programs -- load | slot F slot F | slot F slot F | store on a quarter of the
 // lines, a quarter of the positions loaded and stored, every slot reading a phase table (TAB = 1, LONG = 2) -- with the
 // library's two-line workgroups (512 threads, two per CU) against one-line workgroups (256 threads, four per CU).
-template <int AXIS, int LINES, int LONG = 2, int NFFT = 2, int E = 16>
+// Round 11, CH = 1: the central-half build of the same launch (frugal_pass.h: CH) -- the live quarter [1536, 2560) lies inside
+// [1024, 3072), so both builds run the same program and their checksums must agree (PAOS_BENCH_CENTRAL below).
+template <int AXIS, int LINES, int LONG = 2, int NFFT = 2, int E = 16, int CH = 0>
 void bench_fused(const char* name, int batch, int reps, int pad_blocks) {
   using T = double;
   constexpr int N = 4096, BR = 4, BC = 2, TILES = 1;
@@ -291,7 +293,7 @@ void bench_fused(const char* name, int batch, int reps, int pad_blocks) {
 #endif
   constexpr bool SPLIT = true;
   const size_t lds = frugal_lds_bytes<T, N, LINES, TILES, SPLIT, 1, 1, E>();
-  auto kf = frugal_pass_kernel<T, N, E, LINES, TILES, AXIS, BR, BC, SPLIT, 1, 1, NFFT, 0, 1, LONG>;
+  auto kf = frugal_pass_kernel<T, N, E, LINES, TILES, AXIS, BR, BC, SPLIT, 1, 1, NFFT, 0, 1, LONG, 0, CH>;
   CK(hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   // checksum of one launch on a fresh copy (the variants must agree bit for bit)
   hipLaunchKernelGGL(kf, grid, block, lds, 0, PAOS_FRUGAL_PASS(a));
@@ -365,6 +367,19 @@ int main(int argc, char** argv) {
       bench_fused<0, 1, 2, 2, 8>("fused rows, 1 line, 8 points per thread", 32, reps, pad);
       bench_fused<1, 1, 2, 2, 8>("fused cols, 1 line, 8 points per thread", 32, reps, pad);
 #endif
+    }
+    return 0;
+  }
+  if (getenv("PAOS_BENCH_CENTRAL")) {  // round 11: the one-line fused launches, ordinary against central-half build, interleaved
+    for (int round = 0; round < 3; ++round) {
+      bench_fused<0, 1, 2>("fused rows [2][2], base", 32, reps, pad);
+      bench_fused<0, 1, 2, 2, 16, 1>("fused rows [2][2], central half", 32, reps, pad);
+      bench_fused<1, 1, 2>("fused cols [2][2], base", 32, reps, pad);
+      bench_fused<1, 1, 2, 2, 16, 1>("fused cols [2][2], central half", 32, reps, pad);
+      bench_fused<0, 1, 4>("fused rows [2][2][2], base", 32, reps, pad);
+      bench_fused<0, 1, 4, 2, 16, 1>("fused rows [2][2][2], central half", 32, reps, pad);
+      bench_fused<1, 1, 4>("fused cols [2][2][2], base", 32, reps, pad);
+      bench_fused<1, 1, 4, 2, 16, 1>("fused cols [2][2][2], central half", 32, reps, pad);
     }
     return 0;
   }

@@ -4,7 +4,8 @@
 meant to fit their register budget without scratch.  Known exceptions: the complex64 shapes with three phases in one
 slot (<= 24 B per lane), since round 4 the LONG builds (a launch that runs two or three passes: <= 40 B per lane --
 a few dwords spilled once per wave in a four- to six-transform kernel) and, since round 5, the OCC = 1 builds of 2048^2
-(four workgroups per CU at 128 VGPRs: <= 80 B per lane).  Exit status 1 if any other shape spills: a
+(four workgroups per CU at 128 VGPRs: <= 80 B per lane).  The central-half builds of round 11 (`ch`: 1) are LONG or single-pass
+shapes like the others and fall under the same rules.  Exit status 1 if any other shape spills: a
 change to the kernel header that costs the ordinary shapes their allocation shows here, not only in the bench (round 4:
 a generic lambda inside a discarded `if constexpr` branch did exactly that to every shape).  The row and column kernels
 of the transfer functions (otf_pass.h) are listed too; any scratch in them is unexpected."""
@@ -12,11 +13,11 @@ import re
 import sys
 
 txt = open(sys.argv[1] if len(sys.argv) > 1 else "build/make.log").read()
-KEYS = ("type", "N", "lines", "axis", "BR", "split", "kpre", "kmid", "nfft", "store", "tab", "long", "occ")
+KEYS = ("type", "N", "lines", "axis", "BR", "split", "kpre", "kmid", "nfft", "store", "tab", "long", "occ", "ch")
 rows = []
 for b in txt.split("Function Name: ")[1:]:
     name = b.split("\n")[0].strip()
-    m = re.search(r"frugal_pass_kernelI([df])Li(\d+)ELi\d+ELi(\d)ELi1ELi(\d)ELi(\d)ELi2ELb([01])ELi(\d)ELi(\d)ELi(\d)ELi(\d)E(?:Li(\d)ELi(\d)E)?(?:Li(\d)E)?", name)
+    m = re.search(r"frugal_pass_kernelI([df])Li(\d+)ELi\d+ELi(\d)ELi1ELi(\d)ELi(\d)ELi2ELb([01])ELi(\d)ELi(\d)ELi(\d)ELi(\d)E(?:Li(\d)ELi(\d)E)?(?:Li(\d)E)?(?:Li(\d)E)?", name)
     v, c = re.search(r"VGPRs: (\d+)", b), re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b)
     if m and v and c:
         g = tuple(x if x is not None else "0" for x in m.groups())
