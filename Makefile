@@ -43,7 +43,7 @@ build/obj/paos_plan.o: $(CSRC)/paos_plan.cpp $(HEADERS)
 $(LIB): $(OBJS)
 	$(HIPCC) -shared -fPIC $(OBJS) -ldl -o $(LIB)
 
-build/fftbench: tools/fftbench.hip $(CSRC)/fft_core.h $(CSRC)/fft_kernels.h $(CSRC)/frugal_pass.h
+build/fftbench: tools/fftbench.hip $(HEADERS)
 	mkdir -p build
 	$(HIPCC) -O3 --offload-arch=$(ARCH) -ffp-contract=off -I$(CSRC) tools/fftbench.hip -o build/fftbench
 

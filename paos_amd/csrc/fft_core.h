@@ -199,9 +199,6 @@ __device__ __forceinline__ cx<T> mulw(cx<T> v, int m) {
 // of 160 -- 16 fewer per transform stage, six stages per two-transform pass, in kernels that run at the rate of
 // the fp64 pipe (profiles/r02_valu_mix_fftbench.txt).  All constants are compile-time; cos(2 pi m / 16) is never
 // zero for the m used here (m = 4, the multiplication by -+i, is kept exact and free).
-#ifndef PAOS_LF16
-#define PAOS_LF16 1
-#endif
 template <int M16, int DIR>
 struct W16 {  // W16^M16 for DIR = +1 (exp(-2 pi i M16 / 16)), its conjugate for DIR = -1
   static constexpr int m32 = (M16 * 2) & 31;
@@ -316,7 +313,7 @@ __device__ __forceinline__ void dft16_lf_central(cx<T>* v) {
 // In-place DFT of R points held in registers, natural order in and out.
 template <int R, int DIR, typename T>
 __device__ __forceinline__ void dft(cx<T>* v) {
-  if constexpr (R == 16 && PAOS_LF16 != 0) {
+  if constexpr (R == 16) {
     dft16_lf<DIR>(v);
   } else if constexpr (R == 2) {
     cx<T> a = v[0], b = v[1];
@@ -428,15 +425,6 @@ __device__ __forceinline__ void apply_twiddle_chain(cx<T>* v, cx<T> w1) {
   }
 }
 
-// PAOS_DIAG (microbench timing builds only; results are wrong): bit 0 drops the barriers,
-// bit 1 drops the LDS traffic of the exchanges.
-#ifndef PAOS_DIAG
-#define PAOS_DIAG 0
-#endif
-#define PAOS_SYNC() do { if (!(PAOS_DIAG & 1)) __syncthreads(); } while (0)
-// inside fft_stages; bit 2 (timing only): only the first exchange keeps its barriers
-#define PAOS_SYNC_X() do { if (!((PAOS_DIAG & 4) && NS > 1)) PAOS_SYNC(); } while (0)
-
 // All stages of one line.  ``lds`` is this line's exchange area: cx<T> slots
 // when !SPLIT, T slots (real and imaginary parts exchanged one after the other,
 // halving the LDS footprint) when SPLIT.  ``tw`` = exp(-2 pi i m / N), m < N.
@@ -444,19 +432,6 @@ __device__ __forceinline__ void apply_twiddle_chain(cx<T>* v, cx<T> w1) {
 // which keeps a 4096-point c128 pass at ~118 VGPRs -- four waves per SIMD, i.e. two 512-thread
 // workgroups per CU whose load / compute / store phases overlap (profiles/r01_vgpr_experiments.txt).
 #define PAOS_FENCE() do { if constexpr (FR != 0) __builtin_amdgcn_sched_barrier(0); } while (0)
-// (round-5 scheduling experiments, tools/fftbench.hip builds only: bit 0 drops the fence behind an exchange -- the next stage's
-// twiddle loads and first products may then start while the exchange's last reads are in flight --, bit 1 the fence behind the
-// twiddle loop, bit 2 the fences inside the circle-twiddle loop)
-#ifndef PAOS_NOFENCE
-#define PAOS_NOFENCE 0
-#endif
-#define PAOS_FENCE_IF(bit) do { if constexpr (FR != 0 && !(PAOS_NOFENCE & (bit))) __builtin_amdgcn_sched_barrier(0); } while (0)
-#ifndef PAOS_TAIL_FENCE
-#define PAOS_TAIL_FENCE 1
-#endif
-#ifndef PAOS_TABLE_TWIDDLES
-#define PAOS_TABLE_TWIDDLES 1
-#endif
 // ``circle`` (frugal complex128 kernels, else nullptr): exp(+2 pi i m / 256), m < 256, in LDS.  The
 // stage whose twiddles are 256th roots of unity (NS * R == 256: w^r = exp(-2 pi i k r / 256) with
 // k r < 256) reads its 15 powers from it instead of multiplying them up -- 15 ds_read_b128 for
@@ -480,7 +455,7 @@ __device__ __forceinline__ void fft_stages(cx<T>* v, void* lds, int t,
     if constexpr (NS > 1) {
       const int j = t + s * TL;
       const int k = j & (NS - 1);
-      if constexpr (FR != 0 && PAOS_TABLE_TWIDDLES && sizeof(T) == 8 && NS * R == 256) {
+      if constexpr (FR != 0 && sizeof(T) == 8 && NS * R == 256) {
         // two reads in flight ahead of the product that consumes them; the fences keep the scheduler
         // from hoisting all fifteen (60 VGPRs) above the first product
         cx<double> wa = circle[k], wb = circle[2 * k];
@@ -490,7 +465,7 @@ __device__ __forceinline__ void fft_stages(cx<T>* v, void* lds, int t,
           wa = wb;
           if (r + 2 < R) wb = circle[k * (r + 2)];
           v[s * R + r] = cmul(v[s * R + r], cx<T>{(T)w.x, (T)(DIR > 0 ? -w.y : w.y)});
-          PAOS_FENCE_IF(4);
+          PAOS_FENCE();
         }
       } else {
         cx<T> w1 = (w1_last != nullptr && NS * R == N) ? w1_last[s] : tw[k * (N / (NS * R))];
@@ -498,17 +473,15 @@ __device__ __forceinline__ void fft_stages(cx<T>* v, void* lds, int t,
         if constexpr (FR != 0) apply_twiddle_chain<R>(v + s * R, w1);
         else apply_twiddle_powers<R>(v + s * R, w1);
       }
-      PAOS_FENCE_IF(2);
+      PAOS_FENCE();
     }
-    // (timing diagnostics, results wrong: PAOS_DIAG bit 3 drops the butterflies of every FIRST stage, bit 4 of every
-    // LAST stage -- what a zero-aware first / last stage could save at the very most, profiles/r04_zero_aware_stages.txt)
-    if constexpr (CH != 0 && NS == 1 && PAOS_LF16 != 0) {  // (PAOS_LF16 = 0 variant builds: the full butterfly, on the zeros too)
+    if constexpr (CH != 0 && NS == 1) {
       static_assert(R == 16 && TPT == 1, "central-half first stage: one 16-point butterfly per thread");
       dft16_lf_central<DIR>(v);
-    } else if constexpr (!(((PAOS_DIAG & 8) && NS == 1) || ((PAOS_DIAG & 16) && S::LAST))) dft<R, DIR>(v + s * R);
-    // (PAOS_TAIL_FENCE = 0, experiment: no fence behind the LAST stage's butterflies, so that the scheduler may start
-    // the tile's stores while the remaining outputs are still being computed)
-    if constexpr (!(S::LAST && PAOS_TAIL_FENCE == 0)) PAOS_FENCE();
+    } else {
+      dft<R, DIR>(v + s * R);
+    }
+    PAOS_FENCE();
   }
 
   if constexpr (!S::LAST) {
@@ -535,13 +508,13 @@ __device__ __forceinline__ void fft_stages(cx<T>* v, void* lds, int t,
 #pragma unroll
       for (int s = 0; s < TPT; ++s)
 #pragma unroll
-        for (int r = 0; r < R; ++r) if (!(PAOS_DIAG & 2)) l[wb[s] + lds_pad(r * NS)] = v[s * R + r];
-      PAOS_SYNC_X();
+        for (int r = 0; r < R; ++r) l[wb[s] + lds_pad(r * NS)] = v[s * R + r];
+      __syncthreads();
 #pragma unroll
       for (int s = 0; s < TPT2; ++s)
 #pragma unroll
-        for (int r = 0; r < R2; ++r) if (!(PAOS_DIAG & 2)) v[s * R2 + r] = l[ridx(s, r)];
-      if constexpr (!SN::LAST) PAOS_SYNC_X();
+        for (int r = 0; r < R2; ++r) v[s * R2 + r] = l[ridx(s, r)];
+      if constexpr (!SN::LAST) __syncthreads();
     } else {
       T* l = reinterpret_cast<T*>(lds);
 #pragma unroll
@@ -549,120 +522,21 @@ __device__ __forceinline__ void fft_stages(cx<T>* v, void* lds, int t,
 #pragma unroll
         for (int s = 0; s < TPT; ++s)
 #pragma unroll
-          for (int r = 0; r < R; ++r)
-            if (!(PAOS_DIAG & 2)) l[wb[s] + lds_pad(r * NS)] = part ? v[s * R + r].y : v[s * R + r].x;
-        PAOS_SYNC_X();
+          for (int r = 0; r < R; ++r) l[wb[s] + lds_pad(r * NS)] = part ? v[s * R + r].y : v[s * R + r].x;
+        __syncthreads();
 #pragma unroll
         for (int s = 0; s < TPT2; ++s)
 #pragma unroll
           for (int r = 0; r < R2; ++r) {
-            if (!(PAOS_DIAG & 2)) {
-              const T val = l[ridx(s, r)];
-              if (part) v[s * R2 + r].y = val; else v[s * R2 + r].x = val;
-            }
+            const T val = l[ridx(s, r)];
+            if (part) v[s * R2 + r].y = val; else v[s * R2 + r].x = val;
           }
-        if (part == 0 || !SN::LAST) PAOS_SYNC_X();
+        if (part == 0 || !SN::LAST) __syncthreads();
       }
     }
-    PAOS_FENCE_IF(1);
+    PAOS_FENCE();
     fft_stages<T, N, E, DIR, SPLIT, NS * R, FR, 0>(v, lds, t, tw, circle, w1_last);
   }
-}
-
-// ---- 4096-point transforms with a digit-swapped side (the two transforms of a fused pass) ----------
-// A pass that runs FFT | pointwise | FFT needs natural order only at its two ends (global memory).  In
-// between, the 256 threads of a line may hold the 4096 points in any order as long as each thread knows
-// which positions it owns.  That freedom removes the barriers of one exchange per transform:
-//
-//   index digits  n = t0 + 16 t1 + 256 s  (thread t = t0 + 16 t1 holds slots s = 0..15)
-//   NAT -> SWP (decimation in frequency):
-//     DFT16 over s -> a | * W4096^(t a) | X1: (t0, t1; a) -> (t0, a; t1)   cross-wave: LDS + barriers
-//     DFT16 over slots  -> b | * W256^(t0 b) | X2: (t0, a; b) -> (b, a; t0)    inside the 16 lanes of a group:
-//     DFT16 over slots  -> c                                                 LDS, no barrier
-//     thread (t0 = b, t1 = a), slot c holds X[a + 16 b + 256 c]: position sigma(t) + 256 c, sigma = nibble swap
-//   SWP -> NAT is the transposed flow (the DFT matrix is symmetric): the same three DFT16s, the same two
-//   diagonal twiddles at the same (thread, slot) places, the exchanges inverted and in reverse order.
-//
-// X1 moves slot a of thread t to row a of a 16 x 272 table (272 = 16 * 17: the second digit of a row is
-// padded to 17 so that the in-group transposition X2 reads and writes it without bank conflicts; rows 272
-// apart put the two groups of a 32-lane LDS cycle on the two halves of the banks).  Row a is read -- and
-// later reused for X2 -- only by the 16 threads of group a, which sit in one wave: X2 needs no barrier.
-// Real and imaginary parts take turns (SPLIT) like in fft_stages.  Seven barriers per transform become three.
-constexpr int kSwapRow = 272;
-
-__device__ __forceinline__ int swap_nibbles(int t) { return ((t & 15) << 4) | (t >> 4); }
-
-// scatter ``v[r]`` to ``lds[wbase + r * wstride]``, [barrier], gather ``v[r]`` from ``lds[rbase + r * rstride]``
-template <typename T, bool BARRIER>
-__device__ __forceinline__ void swap_exchange(cx<T>* v, T* lds, int wbase, int wstride, int rbase, int rstride, bool first) {
-#pragma unroll
-  for (int part = 0; part < 2; ++part) {
-    if (BARRIER && (part == 1 || !first)) __syncthreads();  // the area may still be read (previous round / transform)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) lds[wbase + r * wstride] = part ? v[r].y : v[r].x;
-    if (BARRIER) __syncthreads();
-    else __builtin_amdgcn_wave_barrier();  // same wave: LDS operations execute in order; keep the compiler from reordering
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const T val = lds[rbase + r * rstride];
-      if (part) v[r].y = val; else v[r].x = val;
-    }
-    if (!BARRIER) __builtin_amdgcn_wave_barrier();
-  }
-}
-
-// v[b] *= W256^(t0 b) = conj(circle[t0 b]), two table reads in flight
-template <typename T>
-__device__ __forceinline__ void swap_twiddle256(cx<T>* v, const cx<double>* circle, int t0) {
-  cx<double> wa = circle[t0], wb = circle[2 * t0];
-#pragma unroll
-  for (int r = 1; r < 16; ++r) {
-    const cx<double> w = wa;
-    wa = wb;
-    if (r + 2 < 16) wb = circle[t0 * (r + 2)];
-    v[r] = cmul(v[r], cx<T>{(T)w.x, (T)-w.y});
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// natural order in (slot s = x[t + 256 s]) -> digit-swapped out (slot c = X[swap_nibbles(t) + 256 c])
-template <typename T>
-__device__ __forceinline__ void fft4096_nat_to_swapped(cx<T>* v, T* lds, int t, const cx<T>* tw, const cx<double>* circle,
-                                                       bool area_idle) {
-  const int t0 = t & 15, t1 = t >> 4;
-  dft<16, +1>(v);
-  __builtin_amdgcn_sched_barrier(0);
-  apply_twiddle_chain<16>(v, tw[t]);
-  __builtin_amdgcn_sched_barrier(0);
-  swap_exchange<T, true>(v, lds, t, kSwapRow, t1 * kSwapRow + t0, 16, area_idle);
-  __builtin_amdgcn_sched_barrier(0);
-  dft<16, +1>(v);
-  __builtin_amdgcn_sched_barrier(0);
-  swap_twiddle256(v, circle, t0);
-  swap_exchange<T, false>(v, lds, t1 * kSwapRow + t0, 17, t1 * kSwapRow + t0 * 17, 1, false);
-  __builtin_amdgcn_sched_barrier(0);
-  dft<16, +1>(v);
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// digit-swapped in -> natural order out: the transposed flow
-template <typename T>
-__device__ __forceinline__ void fft4096_swapped_to_nat(cx<T>* v, T* lds, int t, const cx<T>* tw, const cx<double>* circle) {
-  const int t0 = t & 15, t1 = t >> 4;
-  dft<16, +1>(v);
-  __builtin_amdgcn_sched_barrier(0);
-  // X2 transposed: (b = t0, a = t1; r) -> (r, a; b); row t1 is private to this group
-  swap_exchange<T, false>(v, lds, t1 * kSwapRow + t0, 17, t1 * kSwapRow + t0 * 17, 1, false);
-  swap_twiddle256(v, circle, t0);
-  dft<16, +1>(v);
-  __builtin_amdgcn_sched_barrier(0);
-  // X1 transposed: (t0, a = t1; s') -> (t0 + 16 s'; a): writes stay in the group's own row
-  swap_exchange<T, true>(v, lds, t1 * kSwapRow + t0, 16, t, kSwapRow, true);
-  __builtin_amdgcn_sched_barrier(0);
-  apply_twiddle_chain<16>(v, tw[t]);
-  __builtin_amdgcn_sched_barrier(0);
-  dft<16, +1>(v);
-  __builtin_amdgcn_sched_barrier(0);
 }
 
 // Undo the output slot permutation in registers (compile-time renaming), so

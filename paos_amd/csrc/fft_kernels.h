@@ -151,7 +151,7 @@ __device__ __forceinline__ cx<T> apply_pw(cx<T> v, const PwOp& op, const double*
 // while line s is transformed).
 // COLSIB > 1 (complex64: a block is 64 B, so two column tiles share every 128-byte line): column tiles
 // are renumbered like the half-block row tiles, siblings 8 workgroups apart = on one XCD.
-template <int N, int E, int LINES, int TILES, int AXIS, int BR, int BC, int SEQ = 1, int COLSIB = 1, int SWZ = 0>
+template <int N, int E, int LINES, int TILES, int AXIS, int BR, int BC, int SEQ = 1, int COLSIB = 1>
 struct TileMap {
   static constexpr int kLinesPerWorkgroup = LINES * TILES;
   static constexpr int kAxis = AXIS;
@@ -184,18 +184,7 @@ struct TileMap {
         }
         row0 = tile * LINES;
         const int bc = tid % BC, br = (tid / BC) % PAR;
-        int q = tid / (BC * PAR);
-        // SWZ (round 5): the lanes of a wave alternate between the PAR lines of the tile, so the 16 lanes of one
-        // ds_write_b64 group hold 16 / PAR consecutive positions of every line -- and the scatter slots 17 t + r of two lines
-        // (whose areas start a multiple of 128 B apart, as the gathers need) fall on the same banks: a 2-way conflict on every
-        // exchange write, all of SQ_LDS_BANK_CONFLICT (profiles/r04_sq_counters.txt: 1.458e8 = 32 writes x 4 array cycles x
-        // 8 exchanges x 139 300 waves).  Odd lines therefore take their positions 8 further on (t ^ 8: the other half of the
-        // 16 slot residues); the set of addresses a wave touches in HBM is the same, only which lane holds which changes.
-        // Measured (profiles/r05_fftbench_fused_variants.txt, r05_ab_variants_bench.txt): stand-alone dense two-transform passes
-        // -1 ... -2.5 %, the fused launches of the separable programs 0 ... +4 % (bound by the latency of their chain, not by
-        // LDS cycles), and in the chain the launches that load / store a quarter of their positions +2 ... +13 % -- the lane
-        // pairs of a quad then come from two 128-byte blocks.  Off in the library (frugal_pass.h: PAOS_LDS_SWIZZLE).
-        if constexpr (SWZ != 0 && PAR == 2 && BC == 2) q ^= (br & 1) ? 4 : 0;
+        const int q = tid / (BC * PAR);
         line = br; t = q * BC + bc;
       }
       base = (unsigned)layout_index<BR, BC>(row0 + line, t, pitch);
@@ -213,8 +202,7 @@ struct TileMap {
         static_assert(BC % LINES == 0, "column tiles span one block column, or one column of it (COLSIB siblings share its lines)");
         static_assert((N / E) % BR == 0, "threads per line must cover whole blocks");
         const int bc = tid % PAR, br = (tid / PAR) % BR;
-        int q = tid / (PAR * BR);
-        if constexpr (SWZ != 0 && PAR == 2 && BR == 4) q ^= (bc & 1) ? 2 : 0;  // (t ^ 8 for the odd column, as above)
+        const int q = tid / (PAR * BR);
         line = bc; t = q * BR + br;
       }
       base = (unsigned)layout_index<BR, BC>(t, col0 + line, pitch);
@@ -324,7 +312,7 @@ __global__ void __launch_bounds__(TILES* LINES* N / E / SEQ, MINW)
     if (do1) line_fft<T, N, E, SPLIT, FR>(v, lds, m.t, tw, c1[FC_INVERSE] != 0.0);
     apply_list<T, E, FR, FEAT>(v, a.mid, a.n_mid, a, item, m, N, sq);
     if (do2) {
-      if (do1) PAOS_SYNC();  // the first transform's last LDS reads precede new writes
+      if (do1) __syncthreads();  // the first transform's last LDS reads precede new writes
       line_fft<T, N, E, SPLIT, FR>(v, lds, m.t, tw, c2[FC_INVERSE] != 0.0);
     }
     apply_list<T, E, FR, FEAT>(v, a.post, a.n_post, a, item, m, N, sq);
@@ -333,7 +321,7 @@ __global__ void __launch_bounds__(TILES* LINES* N / E / SEQ, MINW)
   };
   process(va, 0);
   if constexpr (SEQ == 2) {
-    PAOS_SYNC();  // line 0 is done with the exchange area
+    __syncthreads();  // line 0 is done with the exchange area
     process(vb, 1);
   }
 }

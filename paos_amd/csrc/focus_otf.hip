@@ -1,7 +1,7 @@
 // focus_otf.hip -- the two products that run on the generic pass kernel's tile shapes (FftCfg): through-focus stacks
 // (paos_focus_*, the out-of-place passes of focus_pass.h) and the transfer functions of the kept PSFs (paos_otf_*, the packed
 // real-input passes of otf_pass.h).  One unit for both: compiled on its own, otf_pass.h's complex128 kernels come out with
-// the operands of some additions swapped (same results, other bytes; profiles/r10_unit_split.md).
+// the operands of some additions exchanged (same results, other bytes; profiles/r10_unit_split.md).
 #include "host.h"
 
 #include <algorithm>

@@ -1,9 +1,9 @@
-// frugal_launch.h -- from the run-time shape of a frugal pass (axis, phases per slot, transforms, what it stores) to the
-// launch of its compile-time build.  Each frugal_<family>.hip instantiates this for one (type, N) and nothing else.
+// frugal_launch.h -- from the name of a build of the frugal pass kernel (host.h: FrugalBuild) to its launch: which names have
+// a build (frugal_built), what a build's workgroup looks like (FrugalGeometry), the launch (frugal_launch) and the step from
+// the run-time record to the template arguments (frugal_dispatch).  Each frugal_<family>.hip instantiates frugal_dispatch for
+// one (type, N) and nothing else.
 #pragma once
 #include "host.h"
-
-namespace {
 
 #ifndef PAOS_LONG_ONE_LINE
 #define PAOS_LONG_ONE_LINE 1
@@ -11,17 +11,50 @@ namespace {
 #ifndef PAOS_SINGLE_ONE_LINE
 #define PAOS_SINGLE_ONE_LINE 1   // 0 (A/B builds): single table passes keep the two-line workgroups whatever they load and store
 #endif
-// Round 11, CH = 1: the central-half build of the shape (frugal_pass.h: frugal_pass_kernel, CH) -- for the launches whose first
-// pass loads positions of [N / 4, 3 N / 4) only (launch_lowered: FrugalArgs::central).  Built for 4096^2 complex128, table
-// slots, KPRE = 1 and the shapes a chain step launches with such a window: the field-storing LONG builds and the one-line
-// single passes.  The PSF-storing LONG build (two-line workgroups; the last column launch of a step loads a quarter too)
-// was built and measured as well: 0.97 -> 1.10 ms per launch, so it keeps the ordinary build (profiles/r11_central_half.md).
-template <typename T, int N, int KPRE, int TAB>
-constexpr bool frugal_central() { return sizeof(T) == 8 && N == 4096 && KPRE == 1 && TAB != 0; }
-template <typename T, int N, int AXIS, int KPRE, int KMID, int NFFT, int STORE = 0, int TAB = 0, int LONG = 0, int ONE = 0, int CH = 0>
-int frugal_launch(paos_ctx* c, const FrugalArgs& args) {
+
+// Which builds exist of the family (T, N): THE statement of it -- frugal_dispatch instantiates a kernel exactly where this
+// holds, and pick_build (passes.hip) asks here before it names a one-line or a central-half build.
+//   evaluating slots (tab = 0): any number of phases per slot; the PSF store where both slots have at most one (what a chain
+//     can end on: the last column pass of a separable program usually has the column half of a phase in front of its first
+//     transform), field + power where the first has at most one (what a program that ends on a saved surface ends with);
+//   table slots (tab = 1): one build for any number of phases per slot (kpre, kmid = 1: "has phases"), any store;
+//   fused launches (fuse = 1 .. 4): table slots with phases in both, behind a two-transform pass, any store;
+//   one-line workgroups (one_line = 1, round 5): field-storing single table passes of complex128 at 4096^2 and 2048^2;
+//   central half (central = 1, round 11; frugal_pass.h: frugal_pass_kernel, CH): 4096^2 complex128 table slots with kpre = 1, on
+//     the one-line workgroups -- the field-storing fused launches and the one-line single passes.  The PSF-storing fused build
+//     (two-line workgroups; the last column launch of a step loads a quarter too) was built and measured as well: 0.97 ->
+//     1.10 ms per launch, so it keeps the ordinary build (profiles/r11_central_half.md).
+template <typename T, int N>
+constexpr bool frugal_built(const FrugalBuild& b) {
+  constexpr bool kOneLineSizes = sizeof(T) == 8 && (N == 4096 || N == 2048) && PAOS_LONG_ONE_LINE != 0;
+  if (b.axis < 0 || b.axis > 1 || b.kpre < 0 || b.kpre > kFrugalMaxPre || b.kmid < 0 || b.kmid > kFrugalMaxMid) return false;
+  if (b.nfft < 1 || b.nfft > 2 || b.store < 0 || b.store > 2 || b.fuse < 0 || b.fuse > 4) return false;
+  if ((b.tab | b.one_line | b.central) & ~1) return false;
+  if (b.one_line && !(kOneLineSizes && PAOS_SINGLE_ONE_LINE != 0 && b.tab && !b.fuse && b.store == 0)) return false;
+  if (b.central && !(kOneLineSizes && N == 4096 && b.tab && b.kpre == 1 && b.store == 0 && (b.fuse || b.one_line))) return false;
+  if (b.fuse) return b.tab && b.kpre == 1 && b.kmid == 1 && b.nfft == 2;
+  if (b.tab) return b.kpre <= 1 && b.kmid <= 1 && b.kpre + b.kmid > 0;
+  return b.store == 0 || (b.kpre <= 1 && (b.store == 2 || b.kmid <= 1));
+}
+
+// ... what a launch of a name without a build fails with
+inline int frugal_not_built(paos_ctx* c, const FrugalBuild& b) {
+  if (b.tab && b.fuse) {
+    if (b.kpre != 1 || b.kmid != 1) return fail(c, PAOS_EINVAL, "no fused build of this pass shape");
+    if (b.nfft < 2) return fail(c, PAOS_EINVAL, "a fused chain starts with a two-transform pass");
+    if (b.fuse > 4) return fail(c, PAOS_EINVAL, "a launch runs at most three passes");
+  }
+  if (b.tab && !(b.kpre <= 1 && b.kmid <= 1 && b.kpre + b.kmid > 0)) return fail(c, PAOS_EINVAL, "no table build of this pass shape");
+  if (b.store == 1 && !b.tab) return fail(c, PAOS_EUNSUPPORTED, "no PSF-storing build of this pass shape");
+  if (b.store == 2 && !b.tab) return fail(c, PAOS_EUNSUPPORTED, "no power-summing build of this pass shape");
+  return fail(c, PAOS_EINVAL, "no build of this pass shape");
+}
+
+// The workgroup of a build: what frugal_pass_kernel's remaining template arguments and the launch follow from.
+// LINES_, TILES_ != 0 (tools/fftbench.hip, tools/timeline.hip): another tile than the library's, everything else as derived here.
+template <typename T, int N, int AXIS, int KPRE, int KMID, int STORE = 0, int LONG = 0, int ONE = 0, int LINES_ = 0, int TILES_ = 0>
+struct FrugalGeometry {
   using C = FftCfg<T, N>;
-  static_assert(CH == 0 || frugal_central<T, N, KPRE, TAB>(), "no central-half build of this shape");
   // Round 5: the launches that run two or three passes of a chain (LONG builds) and store the field are bound by the latency
   // chain of a workgroup -- exchanges, barriers, table reads -- not by bytes (they move a sixteenth of the grid): at 4096^2
   // complex128 they run on ONE-line workgroups of 256 threads, four per CU with one wave each per SIMD instead of two of
@@ -29,117 +62,74 @@ int frugal_launch(paos_ctx* c, const FrugalArgs& args) {
   // 32-byte pieces such tiles take out of every 128-byte block, which rule them out for byte-bound passes, cost nothing
   // here.  (The PSF- / power-summing builds keep the two-line tiles: their partial sums are laid out per two-line tile.)
   // ONE = 1: a single table pass that loads AND stores at most half of its positions (the two passes of the first stretch since
-  // the start box) is as latency-bound as the fused launches and takes the same shape (launch_lowered decides per launch).
-  constexpr bool kOneLine = PAOS_LONG_ONE_LINE != 0 && (LONG != 0 || ONE != 0) && STORE == 0 && sizeof(T) == 8 && N == 4096;
+  // the start box) is as latency-bound as the fused launches and takes the same shape (pick_build decides per launch).
+  static constexpr bool kLatencyBound = PAOS_LONG_ONE_LINE != 0 && (LONG != 0 || ONE != 0) && STORE == 0 && sizeof(T) == 8;
+  static constexpr bool kOneLine = kLatencyBound && N == 4096;
   // ... and at 2048^2, where a line is 128 threads and the workgroup already two lines of them: four workgroups per CU instead
   // of three (frugal_pass.h: OCC)
   // (1024^2: measured too -- four rows per workgroup keep four twiddles per thread in registers and the shapes spill 30-100 B:
   // fused two-pass launches 0.866 -> 0.878 ms, three-pass 1.22 -> 1.31: stays on three workgroups per CU.  profiles/r05_ab_variants_bench.txt)
-  constexpr int kOcc = (PAOS_LONG_ONE_LINE != 0 && (LONG != 0 || ONE != 0) && STORE == 0 && sizeof(T) == 8 && N == 2048) ? 1 : 0;
-  constexpr int LINES = kOneLine ? 1 : (AXIS == 0 ? C::FR_ROW_LINES : C::COL_LINES);
-  constexpr int TILES = AXIS == 0 ? C::ROW_TILES : C::COL_TILES;
+  static constexpr int OCC = (kLatencyBound && N == 2048) ? 1 : 0;
+  static constexpr int LINES = LINES_ != 0 ? LINES_ : (kOneLine ? 1 : (AXIS == 0 ? C::FR_ROW_LINES : C::COL_LINES));
+  static constexpr int TILES = TILES_ != 0 ? TILES_ : (AXIS == 0 ? C::ROW_TILES : C::COL_TILES);
   // several workgroups share the 160 KiB of LDS: c128 exchanges re and im in turn; a c64 line
   // fits whole (the same 35 KiB) and so needs half the barriers -- except in the 4-line row tiles
-  constexpr bool SPLIT = sizeof(T) == 8 || LINES > 2;
-  FrugalArgs a = args;
-  unsigned groups = N / LINES / TILES;
-  a.wg0 = 0;
+  static constexpr bool SPLIT = sizeof(T) == 8 || LINES > 2;
+  static constexpr int GROUPS = N / LINES / TILES, THREADS = TILES * LINES * N / C::E;
+  static constexpr size_t LDS = frugal_lds_bytes<T, N, LINES, TILES, SPLIT, KPRE, KMID, C::E, STORE, OCC>();
   // TileMap renumbers the tiles that share 128-byte lines inside aligned groups of workgroups (siblings 8 apart: one XCD):
   // 16 for half-block row tiles and whole-block column tiles, 32 for the quarter-block row tiles of the one-line builds
-  constexpr unsigned kAlign = (kOneLine && AXIS == 0) ? 32 : 16;
-  static_assert((N / LINES / TILES) % kAlign == 0, "TileMap renumbers tiles inside aligned groups of workgroups");
+  static constexpr unsigned ALIGN = (LINES == 1 && AXIS == 0) ? 32 : 16;
+};
+
+namespace {
+
+template <typename T, int N, int AXIS, int KPRE, int KMID, int NFFT, int STORE, int TAB, int LONG, int ONE, int CH>
+int frugal_launch(paos_ctx* c, const FrugalArgs& args) {
+  using C = FftCfg<T, N>;
+  using G = FrugalGeometry<T, N, AXIS, KPRE, KMID, STORE, LONG, ONE>;
+  FrugalArgs a = args;
+  unsigned groups = G::GROUPS;
+  a.wg0 = 0;
+  static_assert(G::GROUPS % G::ALIGN == 0, "TileMap renumbers tiles inside aligned groups of workgroups");
   if (a.live_hi > a.live_lo) {  // launch the workgroups of live lines only, in whole groups
-    const unsigned per = LINES * TILES;
-    a.wg0 = (a.live_lo / per) / kAlign * kAlign;
-    unsigned end = ((a.live_hi + per - 1) / per + kAlign - 1) / kAlign * kAlign;
+    const unsigned per = G::LINES * G::TILES;
+    a.wg0 = (a.live_lo / per) / G::ALIGN * G::ALIGN;
+    unsigned end = ((a.live_hi + per - 1) / per + G::ALIGN - 1) / G::ALIGN * G::ALIGN;
     if (end > groups) end = groups;
     groups = end - a.wg0;
   }
-  const dim3 grid(groups, c->batch), block(TILES * LINES * N / C::E);
+  const dim3 grid(groups, c->batch), block(G::THREADS);
   constexpr size_t kMaxPad = 8192;
-  const size_t lds = frugal_lds_bytes<T, N, LINES, TILES, SPLIT, KPRE, KMID, C::E, STORE, kOcc>() + (c->lds_pad < kMaxPad ? c->lds_pad : kMaxPad);
-  auto kern = frugal_pass_kernel<T, N, C::E, LINES, TILES, AXIS, C::BR, C::BC, SPLIT, KPRE, KMID, NFFT, STORE, TAB, LONG, kOcc, CH>;
+  const size_t lds = G::LDS + (c->lds_pad < kMaxPad ? c->lds_pad : kMaxPad);
+  auto kern = frugal_pass_kernel<T, N, C::E, G::LINES, G::TILES, AXIS, C::BR, C::BC, G::SPLIT, KPRE, KMID, NFFT, STORE, TAB, LONG, G::OCC, CH>;
   ++(CH != 0 ? c->central_launches : c->plain_launches);  // paos_central_half_stats
-  return TIMED_LAUNCH(c, kern, grid, block, lds, frugal_lds_bytes<T, N, LINES, TILES, SPLIT, KPRE, KMID, C::E, STORE, kOcc>() + kMaxPad,
-                      AXIS == 0 ? PAOS_KERNEL_PASS_ROWS : PAOS_KERNEL_PASS_COLS, c->prof_next_tag, PAOS_FRUGAL_PASS(a));
+  return TIMED_LAUNCH(c, kern, grid, block, lds, G::LDS + kMaxPad, AXIS == 0 ? PAOS_KERNEL_PASS_ROWS : PAOS_KERNEL_PASS_COLS,
+                      c->prof_next_tag, PAOS_FRUGAL_PASS(a));
 }
 
-template <typename T, int N, int AXIS, int KPRE, int KMID>
-int frugal_nfft(paos_ctx* c, const FrugalArgs& a, int nfft) {
-  // (the digit-swapped two-transform variant NFFT = 3 of frugal_pass.h is built by tools/fftbench.hip only:
-  // measured in round 2 with parity unchanged and no gain, profiles/r02_fftbench_digit_swapped_experiment.txt)
-  if (a.tab && a.fuse) {  // ... and the launch runs the next pass -- or the next two -- of the program as well (LONG builds)
-    if constexpr (KPRE == 1 && KMID == 1) {
-      if (nfft < 2) return fail(c, PAOS_EINVAL, "a fused chain starts with a two-transform pass");
-#define PAOS_LONG_CASE(L)                                                           \
-  case L:                                                                           \
-    if constexpr (frugal_central<T, N, 1, 1>() && PAOS_LONG_ONE_LINE != 0) {  /* (the one-line builds only) */ \
-      if (a.central && !a.psf && !a.pow_partial) return frugal_launch<T, N, AXIS, 1, 1, 2, 0, 1, L, 0, 1>(c, a);  \
-    }                                                                               \
-    if (a.psf) return frugal_launch<T, N, AXIS, 1, 1, 2, 1, 1, L>(c, a);            \
-    if (a.pow_partial) return frugal_launch<T, N, AXIS, 1, 1, 2, 2, 1, L>(c, a);    \
-    return frugal_launch<T, N, AXIS, 1, 1, 2, 0, 1, L>(c, a);
-      switch (a.fuse) {
-        PAOS_LONG_CASE(1)
-        PAOS_LONG_CASE(2)
-        PAOS_LONG_CASE(3)
-        PAOS_LONG_CASE(4)
-      }
-#undef PAOS_LONG_CASE
-      return fail(c, PAOS_EINVAL, "a launch runs at most three passes");
-    } else {
-      return fail(c, PAOS_EINVAL, "no fused build of this pass shape");
-    }
-  }
-  if (a.tab) {  // the slots read their factors from tables: one build for any number of phases per slot
-    if constexpr (KPRE <= 1 && KMID <= 1 && KPRE + KMID > 0) {
-      if (a.psf) return nfft >= 2 ? frugal_launch<T, N, AXIS, KPRE, KMID, 2, 1, 1>(c, a) : frugal_launch<T, N, AXIS, KPRE, KMID, 1, 1, 1>(c, a);
-      if (a.pow_partial) return nfft >= 2 ? frugal_launch<T, N, AXIS, KPRE, KMID, 2, 2, 1>(c, a) : frugal_launch<T, N, AXIS, KPRE, KMID, 1, 2, 1>(c, a);
-      if constexpr (sizeof(T) == 8 && (N == 4096 || N == 2048) && PAOS_LONG_ONE_LINE != 0) {
-        if constexpr (frugal_central<T, N, KPRE, 1>()) {
-          if (a.one_line && a.central && PAOS_SINGLE_ONE_LINE != 0)
-            return nfft >= 2 ? frugal_launch<T, N, AXIS, KPRE, KMID, 2, 0, 1, 0, 1, 1>(c, a) : frugal_launch<T, N, AXIS, KPRE, KMID, 1, 0, 1, 0, 1, 1>(c, a);
-        }
-        if (a.one_line && PAOS_SINGLE_ONE_LINE != 0) return nfft >= 2 ? frugal_launch<T, N, AXIS, KPRE, KMID, 2, 0, 1, 0, 1>(c, a) : frugal_launch<T, N, AXIS, KPRE, KMID, 1, 0, 1, 0, 1>(c, a);
-      }
-      return nfft >= 2 ? frugal_launch<T, N, AXIS, KPRE, KMID, 2, 0, 1>(c, a) : frugal_launch<T, N, AXIS, KPRE, KMID, 1, 0, 1>(c, a);
-    } else {
-      return fail(c, PAOS_EINVAL, "no table build of this pass shape");
-    }
-  }
-  if constexpr (KPRE <= 1 && KMID <= 1) {  // the shapes a chain can end on: also built with the PSF store (KPRE = 1: round 4,
-    // the last column pass of a separable program usually has the column half of a phase in front of its first transform)
-    if (a.psf) return nfft >= 2 ? frugal_launch<T, N, AXIS, KPRE, KMID, 2, 1>(c, a) : frugal_launch<T, N, AXIS, KPRE, KMID, 1, 1>(c, a);
+// From the run-time record to the template arguments, one field per step: V... are the fields unfolded so far, X the value
+// the next one is compared with.  Behind the last field: the launch, where the name has a build.
+constexpr int kFrugalFieldMax[] = {1, kFrugalMaxPre, kFrugalMaxMid, 2, 2, 1, 4, 1, 1};  // (FrugalBuild's fields, in order)
+template <typename T, int N, int X, int... V>
+int frugal_unfold(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a) {
+  constexpr int I = sizeof...(V), kFields = sizeof(kFrugalFieldMax) / sizeof(int);
+  static_assert(sizeof(FrugalBuild) == kFields * sizeof(int), "one maximum per field");
+  const int field[] = {b.axis, b.kpre, b.kmid, b.nfft, b.store, b.tab, b.fuse, b.one_line, b.central};
+  if (field[I] != X) {
+    if constexpr (X < kFrugalFieldMax[I]) return frugal_unfold<T, N, X + 1, V...>(c, b, a);
+    else return frugal_not_built(c, b);
+  } else if constexpr (I + 1 < kFields) {
+    return frugal_unfold<T, N, 0, V..., X>(c, b, a);
+  } else if constexpr (frugal_built<T, N>(FrugalBuild{V..., X})) {
+    return frugal_launch<T, N, V..., X>(c, a);
   } else {
-    if (a.psf) return fail(c, PAOS_EUNSUPPORTED, "no PSF-storing build of this pass shape");
-  }
-  if constexpr (KPRE <= 1) {  // ... and the shapes a program that ends on a saved surface ends with: field + its power
-    if (a.pow_partial) return nfft >= 2 ? frugal_launch<T, N, AXIS, KPRE, KMID, 2, 2>(c, a) : frugal_launch<T, N, AXIS, KPRE, KMID, 1, 2>(c, a);
-  } else {
-    if (a.pow_partial) return fail(c, PAOS_EUNSUPPORTED, "no power-summing build of this pass shape");
-  }
-  return nfft >= 2 ? frugal_launch<T, N, AXIS, KPRE, KMID, 2>(c, a) : frugal_launch<T, N, AXIS, KPRE, KMID, 1>(c, a);
-}
-template <typename T, int N, int AXIS, int KPRE>
-int frugal_kmid(paos_ctx* c, const FrugalArgs& a, int kmid, int nfft) {
-  switch (kmid) {
-    case 0: return frugal_nfft<T, N, AXIS, KPRE, 0>(c, a, nfft);
-    case 1: return frugal_nfft<T, N, AXIS, KPRE, 1>(c, a, nfft);
-    case 2: return frugal_nfft<T, N, AXIS, KPRE, 2>(c, a, nfft);
-    default: return frugal_nfft<T, N, AXIS, KPRE, 3>(c, a, nfft);
-  }
-}
-template <typename T, int N, int AXIS>
-int frugal_kpre(paos_ctx* c, const FrugalArgs& a, int kpre, int kmid, int nfft) {
-  switch (kpre) {
-    case 0: return frugal_kmid<T, N, AXIS, 0>(c, a, kmid, nfft);
-    case 1: return frugal_kmid<T, N, AXIS, 1>(c, a, kmid, nfft);
-    default: return frugal_kmid<T, N, AXIS, 2>(c, a, kmid, nfft);
+    return frugal_not_built(c, b);
   }
 }
 template <typename T, int N>
-int frugal_axis(paos_ctx* c, const FrugalArgs& a, int axis, int kpre, int kmid, int nfft) {
-  return axis == 0 ? frugal_kpre<T, N, 0>(c, a, kpre, kmid, nfft) : frugal_kpre<T, N, 1>(c, a, kpre, kmid, nfft);
+int frugal_dispatch(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a) {
+  return frugal_unfold<T, N, 0>(c, b, a);
 }
 
 }  // namespace

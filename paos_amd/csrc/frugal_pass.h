@@ -17,24 +17,6 @@
 #ifndef PAOS_FENCE_EVERY
 #define PAOS_FENCE_EVERY 2
 #endif
-// Round-4 scheduling experiments (tools/build_variant.sh; profiles/r04_ab_variants_bench.txt) -- all three measured
-// and left OFF: priority -2.0 / -2.5 % wavefronts/s, prefetch -9 % (full launches 3.43 -> 4.04 ms):
-//   PAOS_PRIO_LOAD  p > 0: the waves of a fresh workgroup run at priority p until their tile loads are issued (they
-//                   compete for the issue ports with the fp64 stream of the OLDER workgroup of the CU, and the
-//                   arbiter prefers the older wave)
-//   PAOS_PRIO_STORE p > 0: ... and again from their last butterflies to the end of their stores
-//   PAOS_PREFETCH   d > 0: a workgroup touches the tile of workgroup wg + d (one dword per 64 bytes), so that the
-//                   tile comes from the Infinity Cache when its own workgroup asks for it about one round later:
-//                   bytes in flight are otherwise bounded by the register files (2 x 128 KiB per CU)
-#ifndef PAOS_PRIO_LOAD
-#define PAOS_PRIO_LOAD 0
-#endif
-#ifndef PAOS_PRIO_STORE
-#define PAOS_PRIO_STORE 0
-#endif
-#ifndef PAOS_PREFETCH
-#define PAOS_PREFETCH 0
-#endif
 
 namespace paos {
 
@@ -93,7 +75,7 @@ struct FrugalItem {
 // k < NS, i.e. an index below N / R <= N / 4; with 16 points per thread every supported N stays below 256,
 // with 32 points per thread (complex64) below 1024
 template <int N, int E>
-constexpr int twiddle_lds_entries() { return E == 8 ? N / 8 : (E <= 16 ? 256 : (N / 4 < 1024 ? N / 4 : 1024)); }  // (E = 8: round-5 experiment)
+constexpr int twiddle_lds_entries() { return E <= 16 ? 256 : (N / 4 < 1024 ? N / 4 : 1024); }
 
 // PAOS_STAMPS (tools/fftbench.hip timeline builds only): wave 0 of every workgroup records
 // s_memtime at the phase boundaries plus where it ran (HW_ID, XCC_ID) into FrugalArgs::stamps.
@@ -126,21 +108,12 @@ struct FrugalArgs {
   unsigned long long* stamps;  // [gridDim.y][gridDim.x][kStampSlots]
 #endif
   // Workgroups of dead lines that have nothing to write need not be launched: when every item's live lines lie in
-  // [live_lo, live_hi) and no item wants its dead tiles written (host: launch_lowered; 0, 0 = all lines), the grid
+  // [live_lo, live_hi) and no item wants its dead tiles written (host only: launch_lowered; 0, 0 = all lines), the grid
   // covers the workgroups of these lines only and workgroup blockIdx.x stands for wg0 + blockIdx.x (frugal_launch
   // sets wg0, a multiple of 16: TileMap renumbers the tiles inside aligned groups of 16 workgroups).
-  unsigned live_lo, live_hi, wg0;
-  // host only: launch the TAB build of the shape (every slot with phases reads FrugalSlot::table)
-  int tab = 0;
-  // host only: the LONG value of the build to launch -- the transforms of the NEXT one or two passes of the program that the
-  // launch runs as well (same axis, same lines; their item records follow this pass's in `items`: [2 or 3][batch])
-  int fuse = 0;
-  // host only (round 5): a single table pass that moves few bytes -- every item loads and stores at most half of its positions --
-  // runs on the one-line workgroups of the fused launches (frugal_launch.h: frugal_launch, ONE)
-  int one_line = 0;
-  // host only (round 11): every active item of the launch's first pass loads positions inside [n / 4, 3 n / 4) -- the launch
-  // takes the central-half build of its shape where there is one (frugal_pass_kernel: CH; frugal_launch.h)
-  int central = 0;
+  // (the initialisers are part of the kernels' bytes: the kernel's own copy of this struct is value-initialised because of
+  // them, and as a struct of plain members every build came out with other registers -- profiles/r12_named_builds.md)
+  unsigned live_lo = 0, live_hi = 0, wg0 = 0;
 };
 #if PAOS_STAMPS
 #define PAOS_STAMP(i)                                                                              \
@@ -212,18 +185,6 @@ __device__ __forceinline__ T flip_sign(T x, unsigned mask_hi) {
 // per phase slot 8 x (argument + sincos) = 184 fp64 instructions less per thread for 8 ds_write_b128 + 8
 // ds_read_b128 and two workgroup barriers (`area_busy`: the area may still be read by the transform in front).
 // The self-mirrored position N / 2 (thread 0, element E / 2) is evaluated by its owner.
-#ifndef PAOS_SHARE_PHASES
-#define PAOS_SHARE_PHASES 1
-#endif
-#ifndef PAOS_MERGE_PHASES
-#define PAOS_MERGE_PHASES 1  // two phases of one slot through one sincos of their exactly summed arguments
-#endif
-#ifndef PAOS_LDS_SWIZZLE
-#define PAOS_LDS_SWIZZLE 0   // 1: the single-pass shapes of the pass kernel take the bank swizzle of fft_kernels.h (TileMap: SWZ).  Measured and
-                             // left OFF (profiles/r05_ab_variants_bench.txt): it removes every LDS bank conflict of the exchanges and buys dense
-                             // launches +0.8 %, but a lane pair of an odd line then sits in another 128-byte block than its even neighbour,
-                             // and the launches that load or store a quarter of their positions take 2-13 % longer
-#endif
 #ifndef PAOS_TABLE_FENCE
 #define PAOS_TABLE_FENCE 8   // table slots (TAB builds): factors fetched and applied in groups of this many elements.  Measured
                              // (profiles/r04_ab_variants_bench.txt, 11c-f): 2 / 4 / 16 are 12 / 5 / 4 % slower; the next group's loads issued
@@ -242,7 +203,7 @@ template <int K>
 __device__ __forceinline__ cx<double> slot_factor(const double* g, const double* step, const double* across2,
                                                   const double* coefq, const double* m2, const cx<double>* circle) {
   cx<double> p = {1.0, 0.0};
-  if constexpr (K == 2 && PAOS_MERGE_PHASES != 0) {
+  if constexpr (K == 2) {
     // Two phases of one slot through ONE sincos: exp(i q0) exp(i q1) = exp(i (q0 + q1)).  The sum of the two rounded
     // arguments is taken exactly (TwoSum: a = fl(q0 + q1), e = q0 + q1 - a, |e| <= ulp(a) / 2 ~ 6e-5 at 1e12 rad)
     // and the tail joins the argument after its reduction, where r + e is exact to 1e-20 (a first-order tail,
@@ -290,7 +251,7 @@ template <int K>
 __device__ __forceinline__ cx<float> slot_factor32(const double* g, const double* step, const double* across2,
                                                    const double* coefq, const double* m2) {
   cx<float> p = {1.0f, 0.0f};
-  if constexpr (K == 2 && PAOS_MERGE_PHASES != 0) {
+  if constexpr (K == 2) {
     // two phases of one slot: their arguments add exactly (TwoSum, as slot_factor<2>), then ONE reduction and ONE
     // hardware sin / cos instead of two of each and a rotation
     const double x0 = __dmul_rn(g[0], step[0]);
@@ -350,8 +311,7 @@ __device__ __forceinline__ void frugal_slot(cx<T>* v, const FrugalSlot& sl, cons
     }
     return;
   }
-  // tpos: position along the line of the thread's element 0 (its elements are TL apart): m.t in natural
-  // order, swap_nibbles(m.t) between the two transforms of a digit-swapped pass
+  // tpos: position along the line of the thread's element 0 (its elements are TL apart): m.t
   constexpr int TL = N / E;
   static_assert(TL % 2 == 0, "the checkerboard sign is constant along a thread's elements");
   static_assert(CH == 0 || (K > 0 && TAB != 0 && sizeof(T) == 8 && E % 4 == 0), "central-half slots: complex128 table slots");
@@ -485,7 +445,7 @@ __device__ __forceinline__ void frugal_slot(cx<T>* v, const FrugalSlot& sl, cons
       for (int k = 0; k < E / 2; ++k) {
         const cx<float> p = factor32(k);
         fac[k * TL + tpos] = p;
-        constexpr bool kFresh = K == 1 || (K == 2 && PAOS_MERGE_PHASES != 0);  // p comes straight from the transcendental unit
+        constexpr bool kFresh = K <= 2;  // p comes straight from the transcendental unit
         const cx<float> zs = scale2(kFresh ? cmul_after_trans(cx<float>{(float)v[k].x, (float)v[k].y}, p)
                                            : cmul(cx<float>{(float)v[k].x, (float)v[k].y}, p), ff, ffy);
         v[k] = {(T)zs.x, (T)zs.y};
@@ -527,11 +487,7 @@ __device__ __forceinline__ void frugal_slot(cx<T>* v, const FrugalSlot& sl, cons
   };
   auto apply = [&](int k, cx<double> p) __attribute__((always_inline)) {
     const cx<double> vd = {(double)v[k].x, (double)v[k].y};
-#if defined(PAOS_DIAG_NOSCALE)  // (timing diagnostic: what folding sign and scale into the table would save -- results wrong)
-    v[k] = {(T)(fma(vd.x, p.x, -(vd.y * p.y))), (T)(fma(vd.x, p.y, vd.y * p.x))};
-#else
     v[k] = {(T)(fma(vd.x, p.x, -(vd.y * p.y)) * f), (T)(fma(vd.x, p.y, vd.y * p.x) * fy)};
-#endif
   };
   if constexpr (K > 0 && TAB != 0) {
     // TAB builds (round 4): the factors of this item's slot by position, from phase_table_kernel's table -- a compile-time
@@ -544,11 +500,7 @@ __device__ __forceinline__ void frugal_slot(cx<T>* v, const FrugalSlot& sl, cons
     constexpr int kFence = Map::kLinesPerWorkgroup == 1 ? 4 : PAOS_TABLE_FENCE;
 #pragma unroll
     for (int k = kFirst; k < kEnd; ++k) {
-#if defined(PAOS_DIAG_NOTABLE)  // (timing diagnostic: what the table loads cost -- results wrong)
-      apply(k, cx<double>{0.6, 0.8});
-#else
       apply(k, tb[k * TL]);
-#endif
       if ((k - kFirst + 1) % kFence == 0) __builtin_amdgcn_sched_barrier(0);  // (groups counted from the first element: the last one ends on a fence)
     }
     return;
@@ -678,21 +630,18 @@ __device__ __forceinline__ void frugal_fft(cx<T>* v, void* lds, int t, const cx<
 #pragma unroll
     for (int k = 0; k < E; ++k) v[k].y = flip_sign(v[k].y, mask);
   }
-  if constexpr (!(FLIP && PAOS_TAIL_FENCE == 0)) __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_sched_barrier(0);
 }
 
 // dynamic LDS of one workgroup: exchange areas | stage twiddles | (c128 with phases) circle table
 constexpr size_t kStoreScratch = 16 * sizeof(double);  // one partial sum per wave (<= 16 waves) of a STORE = 1 workgroup
-#ifndef PAOS_HOIST_RECORDS
-#define PAOS_HOIST_RECORDS 1  // experiment knob: 0 = the slot between the transforms loads its aperture record itself
-#endif
 // How the slot between the transforms gets the aperture line records of the workgroup's lines: 2 = fetched in front of
 // the tile's loads into scalar registers (two-line workgroups with an empty first slot), 1 = fetched behind the tile's
 // loads into a few bytes of LDS (the others: more lines, or a first slot whose register budget has no room),
 // 0 = loaded by the slot when it gets there.
 template <int LINES, int TILES, int KPRE>
 constexpr int frugal_record_mode() {
-  return PAOS_HOIST_RECORDS == 0 ? 0 : ((TILES * LINES == 2 && KPRE == 0) ? 2 : (TILES * LINES <= 16 ? 1 : 0));
+  return (TILES * LINES == 2 && KPRE == 0) ? 2 : (TILES * LINES <= 16 ? 1 : 0);
 }
 // One-line workgroups (round 5: 4096-point complex128 lines, 256 threads): the only stage twiddle that is not a 256th root of
 // unity is the last stage's tw[t] -- one value per thread for the whole kernel, kept in registers -- so the 4 KiB stage table
@@ -718,12 +667,6 @@ constexpr size_t frugal_lds_bytes() {
 // tiles fill the register file) = 4 waves per SIMD = 128 VGPRs.  Smaller N: 256-thread workgroups
 // whose number per CU is bounded by LDS -- three of ~43 KiB -- so the compiler may as well have the 168
 // VGPRs three waves per SIMD leave it (at 128 these shapes spilled 50-180 B per lane).
-#ifndef PAOS_NT_FULL_LINES
-#define PAOS_NT_FULL_LINES 1
-#endif
-#ifndef PAOS_SHARED_NT_LOADS
-#define PAOS_SHARED_NT_LOADS 0
-#endif
 #ifndef PAOS_MINW_SMALL
 #define PAOS_MINW_SMALL 3
 #endif
@@ -739,9 +682,6 @@ constexpr int frugal_min_waves() {
   if (sizeof(T) == 4 && THREADS >= 1024) return 8;  // 4-row tiles of complex64: two 1024-thread workgroups per CU
   if (sizeof(T) == 4 && THREADS >= 512) return PAOS_F32_MINW;
   if (sizeof(T) == 8 && N == 4096 && THREADS == 256) return 4;  // one-line workgroups: four per CU, one wave each per SIMD
-#ifdef PAOS_E8_MINW
-  if (sizeof(T) == 8 && N == 4096 && THREADS == 512) return PAOS_E8_MINW;  // (experiment: 8 points per thread, one line per workgroup)
-#endif
   return THREADS >= 512 ? 4 : PAOS_MINW_SMALL;
 }
 
@@ -788,13 +728,13 @@ __device__ __forceinline__ void tile_power_out(double acc, double* scratch, doub
 // passes of a LONG launch included -- sees full lines and is the ordinary code.  Every value the CH = 0 build computes
 // is reproduced by the same operations or was an exact zero (whose sign alone may differ in an intermediate).
 // There is NO device-side guard: the build never looks at an outer element, so an item whose [pos_lo, pos_hi) reaches beyond
-// the central half would silently lose those positions.  Whoever sets FrugalArgs::central must have checked every active
-// item of the first pass (passes.hip: launch_lowered is the only place that does).
+// the central half would silently lose those positions.  Whoever asks for the build (FrugalBuild::central) must have checked every
+// active item of the first pass (passes.hip: pick_build is the only place that does).
 template <typename T, int N, int E, int LINES, int TILES, int AXIS, int BR, int BC, bool SPLIT,
           int KPRE, int KMID, int NFFT, int STORE = 0, int TAB = 0, int LONG = 0, int OCC = 0, int CH = 0>
 __global__ void __launch_bounds__(TILES* LINES* N / E, (frugal_min_waves<T, N, TILES * LINES * N / E, OCC>()))
     frugal_pass_kernel(PAOS_FRUGAL_PARAMS) {
-  static_assert(LONG == 0 || (TAB != 0 && (NFFT == 2 || NFFT == 3) && KPRE == 1 && KMID == 1), "LONG builds: see above");
+  static_assert(LONG == 0 || (TAB != 0 && NFFT == 2 && KPRE == 1 && KMID == 1), "LONG builds: see above");
   static_assert(CH == 0 || (sizeof(T) == 8 && N == 4096 && E == 16 && TAB != 0 && KPRE == 1 && NFFT <= 2), "CH builds: see above");
   FrugalArgs a;
   a.items = k_items; a.field = k_field; a.pitch = k_pitch; a.item_stride = k_item_stride; a.wg0 = k_wg0;
@@ -827,11 +767,7 @@ __global__ void __launch_bounds__(TILES* LINES* N / E, (frugal_min_waves<T, N, T
   const double h_mask_on = it.mid.mask_on;
   const MaskLine* const h_lines = it.mid.lines;
   // (... and the item's dynamic scale factor: one more scalar load in the same round trip)
-#if defined(PAOS_NO_DYN)  // (A/B build: what the dynamic factor costs the passes that never see one)
-  const double h_dyn = 1.0;
-#else
   const double h_dyn = *((const __attribute__((address_space(4))) double*)a.dyn_scale + item);
-#endif
   if constexpr (frugal_record_mode<LINES, TILES, KPRE>() != 0)
     asm volatile("" ::"s"(h_active), "s"(h_line_lo), "s"(h_line_hi), "s"(h_line_fill), "s"(h_pos_lo), "s"(h_pos_hi), "s"(h_spos_lo),
                  "s"(h_spos_hi), "s"(h_mask_on), "s"(h_lines), "s"(h_dyn));
@@ -839,24 +775,19 @@ __global__ void __launch_bounds__(TILES* LINES* N / E, (frugal_min_waves<T, N, T
     asm volatile("" ::"s"(h_active), "s"(h_line_lo), "s"(h_line_hi), "s"(h_line_fill), "s"(h_pos_lo), "s"(h_pos_hi), "s"(h_spos_lo),
                  "s"(h_spos_hi), "s"(h_dyn));
   if (h_active == 0.0) return;
-  if constexpr (PAOS_PRIO_LOAD > 0) __builtin_amdgcn_s_setprio(PAOS_PRIO_LOAD);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // a block of BR x BC elements is a whole 128-byte line for complex128, half of one for complex64
   constexpr bool kBlockIsLine = BR * BC * sizeof(cx<T>) >= 128;
   // (column tiles of fewer columns than a block has share the block's lines with BC / LINES - 1 siblings too)
   constexpr int COLSIB = (kBlockIsLine ? 1 : (int)(128 / (BR * BC * sizeof(cx<T>)))) * (AXIS == 1 && LINES < BC ? BC / LINES : 1);
   const unsigned wg = blockIdx.x + a.wg0;  // compact grids (FrugalArgs::wg0)
-  constexpr int kSwz = (PAOS_LDS_SWIZZLE != 0 && LONG == 0 && sizeof(T) == 8) ? 1 : 0;
-  const TileMap<N, E, LINES, TILES, AXIS, BR, BC, 1, COLSIB, kSwz> m(wg, threadIdx.x, a.pitch);
+  const TileMap<N, E, LINES, TILES, AXIS, BR, BC, 1, COLSIB> m(wg, threadIdx.x, a.pitch);
   cx<T>* f = reinterpret_cast<cx<T>*>(a.field) + (size_t)item * a.item_stride;
   // tiles that own whole 128-byte lines (c128 column tiles; row tiles that span a full block row) stream
   // around the caches; tiles that share lines with a sibling need the L2 to merge the halves
-  constexpr bool NT = kBlockIsLine && (PAOS_NT_FULL_LINES ? ((AXIS == 1 && LINES >= BC) || (AXIS == 0 && LINES == BR)) : (AXIS == 1 && LINES >= BC));
-  // experiment knob (tools/build_variant.sh): nontemporal LOADS for tiles that share their lines with a sibling
-  // (stores stay ordinary so that the L2 can merge the halves)
-  constexpr bool NTL = NT || (PAOS_SHARED_NT_LOADS != 0);
-  {  // a workgroup of dead lines only: nothing to transform (its tiles are consecutive lines)
-    const int l0 = TILES == 1 ? (AXIS == 0 ? m.row0 : m.col0) : (int)wg * (TILES * LINES);
+  constexpr bool NT = kBlockIsLine && ((AXIS == 1 && LINES >= BC) || (AXIS == 0 && LINES == BR));
+  const int l0 = TILES == 1 ? (AXIS == 0 ? m.row0 : m.col0) : (int)wg * (TILES * LINES);  // the workgroup's first line (its tiles are consecutive lines)
+  {  // a workgroup of dead lines only: nothing to transform
     if (l0 + TILES * LINES <= (int)h_line_lo || l0 >= (int)h_line_hi) {
       if constexpr (STORE == 1) {  // the PSF of a dead tile is zero (and so is its share of the power)
         if (h_line_fill == 0.0) return;  // ... and the buffer is known to hold those zeros already (host: psf_zero_*)
@@ -927,7 +858,7 @@ __global__ void __launch_bounds__(TILES* LINES* N / E, (frugal_min_waves<T, N, T
   constexpr int kRecMode = frugal_record_mode<LINES, TILES, KPRE>();
   constexpr int kRecs = kRecMode == 2 ? 2 : 0;
   MaskLine mrec[kRecs > 0 ? kRecs : 1] = {};
-  const int lbase = __builtin_amdgcn_readfirstlane(TILES == 1 ? (AXIS == 0 ? m.row0 : m.col0) : (int)wg * (TILES * LINES));
+  const int lbase = __builtin_amdgcn_readfirstlane(l0);
   if constexpr (kRecs > 0) {
     if (h_mask_on != 0.0) {
 #pragma unroll
@@ -939,42 +870,23 @@ __global__ void __launch_bounds__(TILES* LINES* N / E, (frugal_min_waves<T, N, T
   constexpr int kPlainPre = KPRE != 0 ? 0 : (AXIS == 1 ? PAOS_COL_PRE : PAOS_ROW_PRE);
   cx<T> v[E];
   const int plo = (int)h_pos_lo, phi = (int)h_pos_hi;
-  // PAOS_PREFETCH: one dword out of every 64 bytes of the tile of workgroup wg + d, issued IN FRONT of the own tile's
-  // loads.  Loads return in order, so once any tile element has arrived these have too: their (single, never read)
-  // destination register stays reserved until the tile's stores (the empty asm in front of them).
-  unsigned pf_sink = 0;
-  if constexpr (PAOS_PREFETCH > 0) {
-    const unsigned wgp = wg + (unsigned)PAOS_PREFETCH;
-    if (wgp < a.wg0 + gridDim.x) {
-      const TileMap<N, E, LINES, TILES, AXIS, BR, BC, 1, COLSIB, kSwz> mp(wgp, threadIdx.x & ~3u, a.pitch);
-      // threads 4 q .. 4 q + 3 own one 64-byte piece per element index k: lane (tid & 3) touches the pieces k = 4 j + (tid & 3)
-      typedef const __attribute__((address_space(1))) char* GlobalBytes;
-      const GlobalBytes pbase = (GlobalBytes)fb;
-#pragma unroll
-      for (int j = 0; j < E / 4; ++j) {
-        const unsigned off = (mp.base + (unsigned)(4 * j + (threadIdx.x & 3)) * mp.stride) * (unsigned)sizeof(cx<T>);
-        asm volatile("global_load_dword %0, %1, %2" : "+v"(pf_sink) : "v"(off), "s"(pbase) : "memory");
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
   if constexpr (CH != 0) {  // [plo, phi) lies inside [N / 4, 3 N / 4): the outer elements are never loaded
 #pragma unroll
     for (int k = 0; k < E; ++k) v[k] = cx<T>{(T)0, (T)0};
 #pragma unroll
     for (int k = E / 4; k < 3 * E / 4; ++k) {
       const int pos = m.t + k * (N / E);
-      if (pos >= plo && pos < phi) v[k] = stream_load<NTL>(at(k));
+      if (pos >= plo && pos < phi) v[k] = stream_load<NT>(at(k));
     }
   } else if (plo <= 0 && phi >= N) {  // wave-uniform: the whole line is live
 #pragma unroll
-    for (int k = 0; k < E; ++k) v[k] = stream_load<NTL>(at(k));
+    for (int k = 0; k < E; ++k) v[k] = stream_load<NT>(at(k));
   } else {
 #pragma unroll
     for (int k = 0; k < E; ++k) {
       const int pos = m.t + k * (N / E);
       v[k] = cx<T>{(T)0, (T)0};
-      if (pos >= plo && pos < phi) v[k] = stream_load<NTL>(at(k));
+      if (pos >= plo && pos < phi) v[k] = stream_load<NT>(at(k));
     }
   }
   __builtin_amdgcn_sched_barrier(0);
@@ -1034,63 +946,13 @@ __global__ void __launch_bounds__(TILES* LINES* N / E, (frugal_min_waves<T, N, T
   // transform (sincos_tab in the pre slot), or when the first transform is switched off: publish them here,
   // with the tile's loads already in flight.  LDS only -- a __syncthreads() would also wait for those loads.
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  if constexpr (PAOS_PRIO_LOAD > 0) __builtin_amdgcn_s_setprio(0);
   PAOS_STAMP_WAIT_VM();
   PAOS_STAMP(1);
 
-  if constexpr (NFFT == 3) {
-    // two transforms with a digit-swapped layout in between (fft_core.h: fft4096_nat_to_swapped): the host
-    // launches this shape only when both transforms run for every active item of the batch
-    static_assert(N == 4096 && E == 16 && sizeof(T) == 8 && SPLIT, "digit-swapped passes: 4096-point complex128 lines");
-    T* area = reinterpret_cast<T*>(lds);
-    // (round 5 experiment: LONG = 2 runs the next pass of the program the same way -- two digit-swapped pairs per launch, three
-    // workgroup barriers per transform instead of seven; every transform of both passes must be on for every item)
-#define PAOS_SWAPPED_PASS(ix, kpre, plain, idle, dyn)                                                                                        \
-  {                                                                                                                                          \
-    frugal_slot<T, N, E, kpre, decltype(m), plain, false, 0, TAB>(v, (ix).pre, (ix).pre_ph, m, circle, false, (ix).fft1_inv != 0.0, m.t);    \
-    fft4096_nat_to_swapped<T>(v, area, m.t, tw, circle, idle);                                                                               \
-    {                                                                                                                                        \
-      const unsigned mask = (ix).fft1_inv != 0.0 ? 0x80000000u : 0u;                                                                         \
-      _Pragma("unroll") for (int k = 0; k < E; ++k) v[k].y = flip_sign(v[k].y, mask);                                                        \
-      __builtin_amdgcn_sched_barrier(0);                                                                                                     \
-    }                                                                                                                                        \
-    /* (dyn: a deferred stop's 1 / sqrt(power) rides on this slot like on the NFFT <= 2 shapes' -- ADVICE r04) */                            \
-    frugal_slot<T, N, E, KMID, decltype(m), 0, false, 0, TAB>(v, (ix).mid, (ix).mid_ph, m, circle, false, (ix).fft2_inv != 0.0,              \
-                                                              swap_nibbles(m.t), nullptr, false, nullptr, 0, dyn);                           \
-    fft4096_swapped_to_nat<T>(v, area, m.t, tw, circle);                                                                                     \
-    {                                                                                                                                        \
-      const unsigned mask = (ix).fft2_inv != 0.0 ? 0x80000000u : 0u;                                                                         \
-      _Pragma("unroll") for (int k = 0; k < E; ++k) v[k].y = flip_sign(v[k].y, mask);                                                        \
-      __builtin_amdgcn_sched_barrier(0);                                                                                                     \
-    }                                                                                                                                        \
-  }
-    PAOS_SWAPPED_PASS(it, KPRE, kPlainPre, true, h_dyn)
-    if constexpr (LONG == 2) {
-      const FrugalItem& it2 = *(const FrugalItem*)((ConstItemPtr)a.items + item + gridDim.y);
-      __syncthreads();  // the exchange area is still being read by the transform in front
-      PAOS_SWAPPED_PASS(it2, 1, 0, true, 1.0)
-    }
-#undef PAOS_SWAPPED_PASS
-    PAOS_STAMP(5);
-    {
-      const int slo3 = (int)h_spos_lo, shi3 = (int)h_spos_hi;
-      if (slo3 <= 0 && shi3 >= N) {
-#pragma unroll
-        for (int k = 0; k < E; ++k) stream_store<NT>(at(k), v[k]);
-      } else {
-#pragma unroll
-        for (int k = 0; k < E; ++k) {
-          const int pos = m.t + k * (N / E);
-          if (pos >= slo3 && pos < shi3) stream_store<NT>(at(k), v[k]);
-        }
-      }
-    }
-    return;
-  }
   const bool ran1 = it.fft1_on != 0.0;
   const bool ran2 = NFFT == 2 && it.fft2_on != 0.0;
   const bool inv1 = ran1 && it.fft1_inv != 0.0;
-  constexpr bool kShare = PAOS_SHARE_PHASES != 0 && TAB == 0;
+  constexpr bool kShare = TAB == 0;
   // (with phases in BOTH slots the second sharing loop costs the shape its spill-free register allocation: there
   // only the slot between the transforms shares)
   frugal_slot<T, N, E, KPRE, decltype(m), kPlainPre, kShare && KMID == 0, 0, TAB, CH>(v, it.pre, it.pre_ph, m, circle, false, inv1, m.t, lds, false);
@@ -1141,6 +1003,9 @@ __global__ void __launch_bounds__(TILES* LINES* N / E, (frugal_min_waves<T, N, T
 #undef PAOS_EXTRA_PASS
   }
   PAOS_STAMP(5);
+  // (STORE = 1, 2) one partial sum per wave, in front of the record area
+  [[maybe_unused]] double* const scratch = reinterpret_cast<double*>(
+      smem + frugal_lds_bytes<T, N, LINES, TILES, SPLIT, KPRE, KMID, E, 0, OCC>() - kStoreScratch - (kRecMode == 1 ? (size_t)TILES * LINES * sizeof(MaskLine) : 0));
   if constexpr (STORE == 1) {
     // |u|^2 as export_kernel forms it (x x + y y, unfused), 8 B per element at the element's own offset; the sum in
     // a fixed order: element by element per thread, lanes, waves
@@ -1153,14 +1018,10 @@ __global__ void __launch_bounds__(TILES* LINES* N / E, (frugal_min_waves<T, N, T
       ps[m.base + (unsigned)k * m.stride] = w;
       acc += w;
     }
-    double* scratch = reinterpret_cast<double*>(smem + frugal_lds_bytes<T, N, LINES, TILES, SPLIT, KPRE, KMID, E, 0, OCC>() - kStoreScratch -
-                                                (kRecMode == 1 ? (size_t)TILES * LINES * sizeof(MaskLine) : 0));
     tile_power_out<TILES * LINES * N / E>(acc, scratch, a.psf_partial + (size_t)item * (N / LINES / TILES) + wg);
     return;
   }
   const int slo = (int)h_spos_lo, shi = (int)h_spos_hi;
-  if constexpr (PAOS_PREFETCH > 0) asm volatile("" ::"v"(pf_sink));
-  if constexpr (PAOS_PRIO_STORE > 0) __builtin_amdgcn_s_setprio(PAOS_PRIO_STORE);
   if (slo <= 0 && shi >= N) {  // wave-uniform: everything is stored
 #pragma unroll
     for (int k = 0; k < E; ++k) stream_store<NT>(at(k), v[k]);
@@ -1178,8 +1039,6 @@ __global__ void __launch_bounds__(TILES* LINES* N / E, (frugal_min_waves<T, N, T
       const double x = (double)v[k].x, y = (double)v[k].y;
       acc += __dadd_rn(__dmul_rn(x, x), __dmul_rn(y, y));
     }
-    double* scratch = reinterpret_cast<double*>(smem + frugal_lds_bytes<T, N, LINES, TILES, SPLIT, KPRE, KMID, E, 0, OCC>() - kStoreScratch -
-                                                (kRecMode == 1 ? (size_t)TILES * LINES * sizeof(MaskLine) : 0));
     tile_power_out<TILES * LINES * N / E>(acc, scratch, a.pow_partial + (size_t)item * (N / LINES / TILES) + wg);
   }
   PAOS_STAMP(6);

@@ -250,6 +250,9 @@ struct FftCfg {
   static constexpr bool COL_SPLIT = (size_t)COL_LINES * COL_TILES * line_lds_bytes<T, N, false>() > 144 * 1024;
   static constexpr int MINW = 1;
 };
+// lines per workgroup of the frugal kernels' ordinary tiles along `axis` for the context's grid: FftCfg's FR_ROW_LINES /
+// COL_LINES at run time (what the per-workgroup sums of a PSF- or power-storing pass are laid out by)
+inline int frugal_tile_lines(const paos_ctx* c, int axis) { return axis == 0 ? (c->n >= 2048 ? c->br / 2 : c->br) : 2; }
 
 // ---- context.hip ---------------------------------------------------------------------------------------------
 // the parameter arena: make room for `total` doubles that must all stay live / copy `count` doubles, *dev: where they are
@@ -334,12 +337,26 @@ bool mask_rect_blocks();
 // optional operators (phase tables, aperture weight maps) ----
 int generic_pass(paos_ctx* c, int axis, const PassArgs& a, int feat);
 
-// ---- frugal_<family>.hip: the pass-kernel shapes of one (type, N) family behind one ordinary function each ----
-int paos_frugal_d1024(paos_ctx* c, const FrugalArgs& a, int axis, int kpre, int kmid, int nfft);
-int paos_frugal_d2048(paos_ctx* c, const FrugalArgs& a, int axis, int kpre, int kmid, int nfft);
-int paos_frugal_d4096(paos_ctx* c, const FrugalArgs& a, int axis, int kpre, int kmid, int nfft);
-int paos_frugal_f2048(paos_ctx* c, const FrugalArgs& a, int axis, int kpre, int kmid, int nfft);
-int paos_frugal_f4096(paos_ctx* c, const FrugalArgs& a, int axis, int kpre, int kmid, int nfft);
+// ---- frugal_<family>.hip: the pass-kernel builds of one (type, N) family behind one ordinary function each ----
+// One build of the pass kernel, by name: the record passes.hip picks per launch (pick_build) and frugal_launch.h turns into
+// template arguments (frugal_built says which records have a build).  The fields stand in frugal_launch<>'s order.
+struct FrugalBuild {
+  int axis;      // 0 rows, 1 columns
+  int kpre;      // phases in front of the first transform: 0 .. kFrugalMaxPre (table builds: 1 = however many)
+  int kmid;      // phases behind it: 0 .. kFrugalMaxMid (table builds likewise)
+  int nfft;      // transforms of the launch's first pass: 1 or 2
+  int store;     // 0 the field, 1 the PSF instead (FrugalArgs::psf), 2 the field and its power (FrugalArgs::pow_partial)
+  int tab;       // every slot with phases reads FrugalSlot::table
+  int fuse;      // the transforms of the NEXT one or two passes of the program that ride along: 0, [1], [2], 3 = [2][1], 4 = [2][2]
+                 // (same axis, same lines; their item records follow this pass's in FrugalArgs::items: [2 or 3][batch])
+  int one_line;  // a single table pass on the one-line workgroups of the fused launches
+  int central;   // every active item of the first pass loads positions of [n / 4, 3 n / 4) only: the central-half build
+};
+int paos_frugal_d1024(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a);
+int paos_frugal_d2048(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a);
+int paos_frugal_d4096(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a);
+int paos_frugal_f2048(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a);
+int paos_frugal_f4096(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a);
 
 // ---- paos_hip.hip: the one unit that includes pointwise.h (its non-template kernels can be compiled once only), so
 // whatever another unit needs of that header's kernels is launched through these ----

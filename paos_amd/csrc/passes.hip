@@ -1,6 +1,6 @@
 // passes.hip -- pass programs: which kernel runs each pass, the aperture line records that ride on the frugal passes, the
 // staging of item records and phase tables, the launches, and the reference's primitives as programs (paos_ptp / stw / wts).
-#include "host.h"
+#include "frugal_launch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -217,21 +217,51 @@ int stage_groups(paos_ctx* c, std::vector<FusedGroup>& groups, const FrugalItem*
   return PAOS_OK;
 }
 
+// Is there a build of this name in the context's family (frugal_launch.h: frugal_built)?
+bool build_exists(const paos_ctx* c, const FrugalBuild& b) {
+  if (c->precision != PAOS_F64) return c->n == 2048 ? frugal_built<float, 2048>(b) : frugal_built<float, 4096>(b);
+  return c->n == 1024 ? frugal_built<double, 1024>(b) : (c->n == 2048 ? frugal_built<double, 2048>(b) : frugal_built<double, 4096>(b));
+}
+
+// THE place that says which build a launch takes: from the passes it runs (`lp` and the one or two that ride along), whether
+// their slots read tables (stage_groups) and what it stores (FrugalBuild::store) to the name of the build.
+FrugalBuild pick_build(const paos_ctx* c, int axis, const LoweredPass& lp, const LoweredPass* next, const LoweredPass* next2, bool tables,
+                       int store) {
+  FrugalBuild b{};
+  b.axis = axis;
+  // The table builds take "has phases" for the number of phases -- their slots read one factor --, and a fused launch runs on
+  // the one build whose slots all read tables (a slot without phases: a table of ones).
+  b.kpre = next ? 1 : (tables && lp.kpre > 1 ? 1 : lp.kpre);
+  b.kmid = next ? 1 : (tables && lp.kmid > 1 ? 1 : lp.kmid);
+  b.nfft = lp.nfft >= 2 ? 2 : 1;
+  b.store = store;
+  b.tab = tables ? 1 : 0;
+  b.fuse = next2 ? 2 + next2->nfft : (next ? next->nfft : 0);
+  // The PSF- and power-storing launches take neither of the builds below: their sums are laid out per two-line tile.
+  if (!tables || store != 0) return b;
+  // light: a single table pass whose every item loads and stores at most half of its positions -- one-line workgroups.
+  // central: every active item of the FIRST pass loads positions of the central half only -- the central-half build of the
+  // shape.  Per launch, not per item: one item outside sends the whole launch to the ordinary build.  (There is no device-side
+  // guard: frugal_pass.h, CH.)
+  bool light = !next, central = c->central_half, any = false;
+  for (const FrugalItem& fi : lp.items) {
+    if (fi.active == 0.0) continue;
+    any = true;
+    light = light && 2.0 * (fi.pos_hi - fi.pos_lo) <= (double)c->n && 2.0 * (fi.spos_hi - fi.spos_lo) <= (double)c->n;
+    central = central && 4.0 * fi.pos_lo >= (double)c->n && 4.0 * fi.pos_hi <= 3.0 * (double)c->n;
+  }
+  // ... where there is one (the central-half builds run on one-line workgroups: a fused launch, or a light pass)
+  b.one_line = light ? 1 : 0;
+  if (!build_exists(c, b)) b.one_line = 0;
+  b.central = central && any ? 1 : 0;
+  if (!build_exists(c, b)) b.central = 0;
+  return b;
+}
+
 int launch_lowered(paos_ctx* c, const paos_pass& p, LoweredPass& lp, const double* dblocks, bool store_psf = false,
                    bool sum_power = false, LoweredPass* next = nullptr, LoweredPass* next2 = nullptr,
                    const FrugalItem* staged = nullptr, bool staged_tables = false) {
   LoweredPass* const last = next2 ? next2 : next;  // the pass whose stores leave the launch (nullptr: this one)
-  // PAOS_DUMP_PASSES=1: one line per pass launch on stderr (shape and what item 0's two slots carry)
-  static const bool dump = env_is("PAOS_DUMP_PASSES", '1');
-  if (dump)
-    for (const LoweredPass* l : {(const LoweredPass*)&lp, (const LoweredPass*)next, (const LoweredPass*)next2}) {
-      if (!l || l->items.empty()) continue;
-      const FrugalItem& f = l->items[0];  // ("+pass": rides in the launch of the pass above it)
-      std::fprintf(stderr, "%spass axis %d kpre %d kmid %d nfft %d | pre: sign %g scale %g mask %g | fft1 on %g inv %g | mid: sign %g scale %g mask %g | "
-                   "fft2 on %g inv %g | lines [%g, %g) fill %g loads [%g, %g) stores [%g, %g)\n", l == &lp ? "" : "+", p.axis, l->kpre, l->kmid, l->nfft,
-                   f.pre.sign_on, f.pre.scale, f.pre.mask_on, f.fft1_on, f.fft1_inv, f.mid.sign_on, f.mid.scale, f.mid.mask_on, f.fft2_on, f.fft2_inv,
-                   f.line_lo, f.line_hi, f.line_fill, f.pos_lo, f.pos_hi, f.spos_lo, f.spos_hi);
-    }
   for (LoweredPass* l : {&lp, next, next2}) {  // render the records along the pass axis, right before the pass (every pass of a chain)
     if (!l || l->mask_block < 0 || !l->mask_render) continue;
     const double* ap = dblocks + (size_t)l->mask_block * c->batch * FP_STRIDE;
@@ -285,7 +315,6 @@ int launch_lowered(paos_ctx* c, const paos_pass& p, LoweredPass& lp, const doubl
       a.live_hi = (unsigned)hi;
     }
   }
-  const int nfft = lp.nfft;
   // for the launch timer: what does this launch skip?  bit 0: whole tiles of dead lines, bit 1: loads of dead
   // positions, bit 2: stores nobody reads, bit 3: it stores the PSF instead of the field
   c->prof_next_tag = store_psf ? 8 : 0;
@@ -309,40 +338,31 @@ int launch_lowered(paos_ctx* c, const paos_pass& p, LoweredPass& lp, const doubl
       c->prof_next_lines += (fi.line_hi - fi.line_lo) * ((fk.fft1_on != 0.0 ? 1.0 : 0.0) + (l->nfft >= 2 && fk.fft2_on != 0.0 ? 1.0 : 0.0));
     }
   }
-  a.tab = tables ? 1 : 0;  // (the TAB builds take "has phases" for the number of phases: their slots read one factor)
-  {  // a single table pass whose every item loads and stores at most half of its positions: one-line workgroups (frugal_launch)
-    bool light = tables && !next && !store_psf && !sum_power;
-    for (int it = 0; it < c->batch && light; ++it) {
-      const FrugalItem& fi = lp.items[it];
-      if (fi.active == 0.0) continue;
-      light = 2.0 * (fi.pos_hi - fi.pos_lo) <= (double)c->n && 2.0 * (fi.spos_hi - fi.spos_lo) <= (double)c->n;
+  const FrugalBuild b = pick_build(c, p.axis, lp, next, next2, tables, store_psf ? 1 : (sum_power ? 2 : 0));
+  // PAOS_DUMP_PASSES=1: on stderr, the build the launch takes and one line per pass it runs (what item 0's two slots carry)
+  static const bool dump = env_is("PAOS_DUMP_PASSES", '1');
+  if (dump) {
+    std::fprintf(stderr, "build axis %d kpre %d kmid %d nfft %d store %d tab %d fuse %d one_line %d central %d\n", b.axis, b.kpre, b.kmid, b.nfft,
+                 b.store, b.tab, b.fuse, b.one_line, b.central);
+    for (const LoweredPass* l : {(const LoweredPass*)&lp, (const LoweredPass*)next, (const LoweredPass*)next2}) {
+      if (!l || l->items.empty()) continue;
+      const FrugalItem& f = l->items[0];  // ("+pass": rides in the launch of the pass above it)
+      std::fprintf(stderr, "%spass axis %d kpre %d kmid %d nfft %d | pre: sign %g scale %g mask %g | fft1 on %g inv %g | mid: sign %g scale %g mask %g | "
+                   "fft2 on %g inv %g | lines [%g, %g) fill %g loads [%g, %g) stores [%g, %g)\n", l == &lp ? "" : "+", p.axis, l->kpre, l->kmid, l->nfft,
+                   f.pre.sign_on, f.pre.scale, f.pre.mask_on, f.fft1_on, f.fft1_inv, f.mid.sign_on, f.mid.scale, f.mid.mask_on, f.fft2_on, f.fft2_inv,
+                   f.line_lo, f.line_hi, f.line_fill, f.pos_lo, f.pos_hi, f.spos_lo, f.spos_hi);
     }
-    a.one_line = light ? 1 : 0;
   }
-  {  // every active item of the FIRST pass loads positions of the central half only: the central-half build of the shape,
-    // where there is one (frugal_launch.h).  Per launch, not per item: one item outside sends the whole launch to the old build.
-    bool central = c->central_half && tables, any = false;
-    for (int it = 0; it < c->batch && central; ++it) {
-      const FrugalItem& fi = lp.items[it];
-      if (fi.active == 0.0) continue;
-      any = true;
-      central = 4.0 * fi.pos_lo >= (double)c->n && 4.0 * fi.pos_hi <= 3.0 * (double)c->n;
-    }
-    a.central = central && any ? 1 : 0;
-  }
-  a.fuse = next2 ? 2 + next2->nfft : (next ? next->nfft : 0);  // LONG: the transforms of the passes that ride along
-  // (a fused pair runs on the one build whose four slots all read tables)
-  const int kpre = next ? 1 : (tables && lp.kpre > 1 ? 1 : lp.kpre), kmid = next ? 1 : (tables && lp.kmid > 1 ? 1 : lp.kmid);
   if (c->precision == PAOS_F64) {
     switch (c->n) {
-      case 1024: return paos_frugal_d1024(c, a, p.axis, kpre, kmid, nfft);
-      case 2048: return paos_frugal_d2048(c, a, p.axis, kpre, kmid, nfft);
-      default: return paos_frugal_d4096(c, a, p.axis, kpre, kmid, nfft);
+      case 1024: return paos_frugal_d1024(c, b, a);
+      case 2048: return paos_frugal_d2048(c, b, a);
+      default: return paos_frugal_d4096(c, b, a);
     }
   }
   switch (c->n) {
-    case 2048: return paos_frugal_f2048(c, a, p.axis, kpre, kmid, nfft);
-    default: return paos_frugal_f4096(c, a, p.axis, kpre, kmid, nfft);
+    case 2048: return paos_frugal_f2048(c, b, a);
+    default: return paos_frugal_f4096(c, b, a);
   }
 }
 
@@ -523,8 +543,7 @@ int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const do
     if (fused_power)
       for (const FrugalItem& fi : low[n_passes - 1].items) fused_power = fused_power && fi.active != 0.0;
     if (fused_power) {
-      const int lines = passes[n_passes - 1].axis == 0 ? (c->n >= 2048 ? c->br / 2 : c->br) : 2;  // FftCfg: FR_ROW_LINES / COL_LINES
-      power_groups = c->n / lines;
+      power_groups = c->n / frugal_tile_lines(c, passes[n_passes - 1].axis);
       if (c->pow_nparts < c->n / 2) {  // (sized for the finest tiling of either axis)
         if (c->pow_partial) (void)hipFree(c->pow_partial);
         c->pow_partial = nullptr; c->pow_nparts = 0;
@@ -542,8 +561,7 @@ int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const do
     if (fused_store)
       for (const FrugalItem& fi : low[n_passes - 1].items) fused_store = fused_store && fi.active != 0.0;
     if (fused_store) {
-      const int lines = passes[n_passes - 1].axis == 0 ? (c->n >= 2048 ? c->br / 2 : c->br) : 2;  // FftCfg: FR_ROW_LINES / COL_LINES
-      const int groups = c->n / lines;
+      const int groups = c->n / frugal_tile_lines(c, passes[n_passes - 1].axis);
       if (c->psf_nparts < groups) {
         if (c->psf_partial) (void)hipFree(c->psf_partial);
         c->psf_partial = nullptr; c->psf_nparts = 0;
@@ -699,8 +717,7 @@ int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const do
   if (final_ticket) {
     if (fused_store) {
       c->psf_zero_axis = passes[n_passes - 1].axis;  // every launch of the program went through
-      const int lines = passes[n_passes - 1].axis == 0 ? (c->n >= 2048 ? c->br / 2 : c->br) : 2;
-      return psf_power_ticket(c, c->psf_partial, c->n / lines, final_ticket);
+      return psf_power_ticket(c, c->psf_partial, c->n / frugal_tile_lines(c, passes[n_passes - 1].axis), final_ticket);
     }
     return psf_keep_power_impl(c, final_ticket);
   }

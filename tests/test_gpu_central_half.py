@@ -1,5 +1,5 @@
 """The central-half builds of the 4096^2 complex128 pass kernel (frugal_pass.h: CH; frugal_launch.h; passes.hip:
-launch_lowered, `central`): a launch whose first pass loads positions of [N / 4, 3 N / 4) only skips the table factors, the
+pick_build, `central`): a launch whose first pass loads positions of [N / 4, 3 N / 4) only skips the table factors, the
 aperture weights and the first butterfly layer of the outer positions, which are exact zeros.
 
 Every case runs the same program three times through the C ABI, on the harness of test_gpu_xprec.py: on a context with

@@ -153,7 +153,7 @@ def test_host_refuses_phase_arguments_at_1e12_and_nan(precision):
 
 # ---- b) phase factors riding on transforms ------------------------------------------------------------------------
 # (family, precision, n, K, where): the builds that evaluate phases (pass_plan.hip: lower_frugal; passes.hip: phases_along_lines,
-# can_fuse_pair, launch_lowered)
+# can_fuse_pair, pick_build)
 #   generic   fp64 N <= 512, fp32 N <= 1024; at any N a pass with a post operator ("post") or a phase with |sgn| != 1
 #   frugal    fp64 N >= 1024, phases across the lines: sincos_tab; K = 2 in one slot: merged (slot_factor<2>); K = 3 sits in
 #             the middle slot (kFrugalMaxPre = 2), in front of it the empty slot (PLAIN)
@@ -475,7 +475,7 @@ def test_pruned_windows_on_stale_rows(generic):
 @pytest.mark.parametrize("n", [2048, 4096])
 def test_single_table_pass_on_one_line_workgroups(n):
     """A single table pass whose items load AND store at most half of their positions runs on one-line workgroups
-    (passes.hip: launch_lowered, `one_line`; frugal_launch.h: frugal_launch, ONE).  How this program gets there: the entry box
+    (passes.hip: pick_build, `one_line`; frugal_launch.h: FrugalGeometry, ONE).  How this program gets there: the entry box
     (rows_stale with live_rows and live_cols, a quarter of the grid each way) makes the first pass -- along columns, its
     phases along the columns only -- work on a quarter of the lines (few enough for tables) and load a quarter of its
     positions; the second pass, along rows, carries an aperture whose bounding box spans a quarter of the rows, so the

@@ -12,7 +12,7 @@
 #include <vector>
 #include <algorithm>
 
-#include "frugal_pass.h"
+#include "frugal_launch.h"
 
 using namespace paos;
 
@@ -142,12 +142,14 @@ void bench_variant(const char* name, int batch, int reps, int pad_blocks = 0) {
   CK(hipFree(dtw));
 }
 
-template <typename T, int N, int AXIS, int KPRE, int KMID, int NFFT, int LINES = 2, int TILES = 1, int E = 16, int BC = 2>
+// The tile (LINES x TILES) is the experiment's; SPLIT, threads and LDS bytes follow from it as in the library (FrugalGeometry).
+template <typename T, int N, int AXIS, int KPRE, int KMID, int NFFT, int LINES = 2, int TILES = 1>
 void bench_frugal(const char* name, int batch, int reps, int pad_blocks) {
 #ifndef PAOS_BENCH_BR
 #define PAOS_BENCH_BR 4
 #endif
-  constexpr int BR = PAOS_BENCH_BR;
+  using G = FrugalGeometry<T, N, AXIS, KPRE, KMID, 0, 0, 0, LINES, TILES>;
+  constexpr int BR = PAOS_BENCH_BR, BC = 2, E = G::C::E;
   if (getenv("PAOS_BENCH_BATCH")) batch = atoi(getenv("PAOS_BENCH_BATCH"));
   const unsigned pitch = (unsigned)N * BR + (unsigned)pad_blocks * BR * BC;
   const unsigned item_stride = pitch * (N / BR);
@@ -208,13 +210,9 @@ void bench_frugal(const char* name, int batch, int reps, int pad_blocks) {
   CK(hipMemcpy(dones, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice));
   FrugalArgs a{d, dtw, ditems, pitch, item_stride};
   a.dyn_scale = dones;
-  const dim3 grid(N / LINES / TILES, batch), block(TILES * LINES * N / E);
-#ifndef PAOS_F32_SPLIT
-#define PAOS_F32_SPLIT 0
-#endif
-  constexpr bool SPLIT = sizeof(T) == 8 || PAOS_F32_SPLIT || E == 32;
-  const size_t lds = frugal_lds_bytes<T, N, LINES, TILES, SPLIT, KPRE, KMID, E>();
-  auto kf = frugal_pass_kernel<T, N, E, LINES, TILES, AXIS, BR, BC, SPLIT, KPRE, KMID, NFFT>;
+  const dim3 grid(G::GROUPS, batch), block(G::THREADS);
+  const size_t lds = G::LDS;
+  auto kf = frugal_pass_kernel<T, N, E, LINES, TILES, AXIS, BR, BC, G::SPLIT, KPRE, KMID, NFFT>;
   CK(hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   Timer tm;
   float ms = tm.run([&] { hipLaunchKernelGGL(kf, grid, block, lds, 0, PAOS_FRUGAL_PASS(a)); }, reps);
@@ -232,10 +230,12 @@ void bench_frugal(const char* name, int batch, int reps, int pad_blocks) {
 // library's two-line workgroups (512 threads, two per CU) against one-line workgroups (256 threads, four per CU).
 // Round 11, CH = 1: the central-half build of the same launch (frugal_pass.h: CH) -- the live quarter [1536, 2560) lies inside
 // [1024, 3072), so both builds run the same program and their checksums must agree (PAOS_BENCH_CENTRAL below).
-template <int AXIS, int LINES, int LONG = 2, int NFFT = 2, int E = 16, int CH = 0>
+template <int AXIS, int LINES, int LONG = 2, int NFFT = 2, int CH = 0>
 void bench_fused(const char* name, int batch, int reps, int pad_blocks) {
   using T = double;
-  constexpr int N = 4096, BR = 4, BC = 2, TILES = 1;
+  constexpr int N = 4096, TILES = 1;
+  using G = FrugalGeometry<T, N, AXIS, 1, 1, 0, LONG, 0, LINES, TILES>;  // (LINES = 1: the library's build)
+  constexpr int BR = G::C::BR, BC = G::C::BC, E = G::C::E;
   if (getenv("PAOS_BENCH_BATCH")) batch = atoi(getenv("PAOS_BENCH_BATCH"));
   const unsigned pitch = (unsigned)N * BR + (unsigned)pad_blocks * BR * BC;
   const unsigned item_stride = pitch * (N / BR);
@@ -283,7 +283,7 @@ void bench_fused(const char* name, int batch, int reps, int pad_blocks) {
   FrugalArgs a{d, dtw, ditems, pitch, item_stride};
   a.dyn_scale = dones;
   a.wg0 = lo / (LINES * TILES);
-  const dim3 grid((hi - lo) / (LINES * TILES), batch), block(TILES * LINES * N / E);
+  const dim3 grid((hi - lo) / (LINES * TILES), batch), block(G::THREADS);
 #if PAOS_STAMPS
   unsigned long long* dstamps;
   const size_t nstamps = (size_t)grid.x * grid.y * kStampSlots;
@@ -291,9 +291,8 @@ void bench_fused(const char* name, int batch, int reps, int pad_blocks) {
   CK(hipMemset(dstamps, 0, nstamps * sizeof(unsigned long long)));
   a.stamps = dstamps;
 #endif
-  constexpr bool SPLIT = true;
-  const size_t lds = frugal_lds_bytes<T, N, LINES, TILES, SPLIT, 1, 1, E>();
-  auto kf = frugal_pass_kernel<T, N, E, LINES, TILES, AXIS, BR, BC, SPLIT, 1, 1, NFFT, 0, 1, LONG, 0, CH>;
+  const size_t lds = G::LDS;
+  auto kf = frugal_pass_kernel<T, N, E, LINES, TILES, AXIS, BR, BC, G::SPLIT, 1, 1, NFFT, 0, 1, LONG, G::OCC, CH>;
   CK(hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   // checksum of one launch on a fresh copy (the variants must agree bit for bit)
   hipLaunchKernelGGL(kf, grid, block, lds, 0, PAOS_FRUGAL_PASS(a));
@@ -363,23 +362,19 @@ int main(int argc, char** argv) {
       bench_fused<0, 1>("fused rows, 1 line per workgroup", 32, reps, pad);
       bench_fused<1, 2>("fused cols, 2 lines per workgroup", 32, reps, pad);
       bench_fused<1, 1>("fused cols, 1 line per workgroup", 32, reps, pad);
-#ifdef PAOS_E8_MINW
-      bench_fused<0, 1, 2, 2, 8>("fused rows, 1 line, 8 points per thread", 32, reps, pad);
-      bench_fused<1, 1, 2, 2, 8>("fused cols, 1 line, 8 points per thread", 32, reps, pad);
-#endif
     }
     return 0;
   }
   if (getenv("PAOS_BENCH_CENTRAL")) {  // round 11: the one-line fused launches, ordinary against central-half build, interleaved
     for (int round = 0; round < 3; ++round) {
       bench_fused<0, 1, 2>("fused rows [2][2], base", 32, reps, pad);
-      bench_fused<0, 1, 2, 2, 16, 1>("fused rows [2][2], central half", 32, reps, pad);
+      bench_fused<0, 1, 2, 2, 1>("fused rows [2][2], central half", 32, reps, pad);
       bench_fused<1, 1, 2>("fused cols [2][2], base", 32, reps, pad);
-      bench_fused<1, 1, 2, 2, 16, 1>("fused cols [2][2], central half", 32, reps, pad);
+      bench_fused<1, 1, 2, 2, 1>("fused cols [2][2], central half", 32, reps, pad);
       bench_fused<0, 1, 4>("fused rows [2][2][2], base", 32, reps, pad);
-      bench_fused<0, 1, 4, 2, 16, 1>("fused rows [2][2][2], central half", 32, reps, pad);
+      bench_fused<0, 1, 4, 2, 1>("fused rows [2][2][2], central half", 32, reps, pad);
       bench_fused<1, 1, 4>("fused cols [2][2][2], base", 32, reps, pad);
-      bench_fused<1, 1, 4, 2, 16, 1>("fused cols [2][2][2], central half", 32, reps, pad);
+      bench_fused<1, 1, 4, 2, 1>("fused cols [2][2][2], central half", 32, reps, pad);
     }
     return 0;
   }
@@ -401,9 +396,6 @@ int main(int argc, char** argv) {
   bench_frugal<double, 4096, 1, 0, 0, 1>("cols single", b4, reps, pad);
   bench_frugal<double, 4096, 0, 0, 1, 2>("rows double 1 phase", b4, reps, pad);
   bench_frugal<double, 4096, 1, 0, 1, 2>("cols double 1 phase", b4, reps, pad);
-  bench_frugal<double, 4096, 0, 0, 1, 3>("rows double 1 phase, digit-swapped", b4, reps, pad);
-  bench_frugal<double, 4096, 1, 0, 1, 3>("cols double 1 phase, digit-swapped", b4, reps, pad);
-  bench_frugal<double, 4096, 1, 0, 0, 3>("cols double 0 phases, digit-swapped", b4, reps, pad);
   bench_frugal<double, 4096, 1, 0, 0, 2>("cols double 0 phases", b4, reps, pad);
   if (getenv("PAOS_BENCH_CORE")) return 0;  // the 4096^2 complex128 shapes only (counter runs)
   // N = 2048: 256-thread workgroups (library, round 2a) against 512-thread ones (two tiles per workgroup)
@@ -434,13 +426,6 @@ int main(int argc, char** argv) {
   // complex64 row tiles of 4 rows (1024 threads, 64-byte pieces of 8 x 2 blocks when PAOS_BENCH_BR=8)
   bench_frugal<float, 4096, 0, 0, 0, 1, 4, 1>("rows single 4-row tiles", 16, reps, pad);
   bench_frugal<float, 4096, 0, 0, 1, 2, 4, 1>("rows double 1 phase 4-row tiles", 16, reps, pad);
-#endif
-#ifdef PAOS_BENCH_E32
-  // complex64 with 32 points per thread over 4 x 4 blocks (128 B): 4-line tiles, 512 threads, whole lines on both axes
-  bench_frugal<float, 4096, 0, 0, 0, 1, 4, 1, 32, 4>("rows single E=32 4x4 blocks", 16, reps, pad);
-  bench_frugal<float, 4096, 1, 0, 0, 1, 4, 1, 32, 4>("cols single E=32 4x4 blocks", 16, reps, pad);
-  bench_frugal<float, 4096, 0, 0, 1, 2, 4, 1, 32, 4>("rows double 1 phase E=32 4x4 blocks", 16, reps, pad);
-  bench_frugal<float, 4096, 1, 0, 1, 2, 4, 1, 32, 4>("cols double 1 phase E=32 4x4 blocks", 16, reps, pad);
 #endif
   return 0;
 }

@@ -16,7 +16,7 @@
 #include <map>
 #include <vector>
 
-#include "frugal_pass.h"
+#include "frugal_launch.h"
 
 using namespace paos;
 
@@ -31,7 +31,8 @@ using namespace paos;
 
 template <typename T, int N, int AXIS, int KPRE, int KMID, int NFFT, int LINES = 2>
 void timeline(const char* name, int batch, int pad_blocks) {
-  constexpr int E = 16, BR = 4, BC = 2;
+  using G = FrugalGeometry<T, N, AXIS, KPRE, KMID, 0, 0, 0, LINES, 1>;  // (the tile is the caller's, the rest the library's)
+  constexpr int E = G::C::E, BR = 4, BC = 2;
   const unsigned pitch = (unsigned)N * BR + (unsigned)pad_blocks * BR * BC;
   const unsigned item_stride = pitch * (N / BR);
   cx<T>* d;
@@ -61,7 +62,7 @@ void timeline(const char* name, int batch, int pad_blocks) {
   FrugalItem* ditems;
   CK(hipMalloc(&ditems, items.size() * sizeof(FrugalItem)));
   CK(hipMemcpy(ditems, items.data(), items.size() * sizeof(FrugalItem), hipMemcpyHostToDevice));
-  const dim3 grid(N / LINES, batch), block(LINES * N / E);
+  const dim3 grid(G::GROUPS, batch), block(G::THREADS);
   const size_t nwg = (size_t)grid.x * grid.y;
   unsigned long long* dst;
   CK(hipMalloc(&dst, nwg * kStampSlots * sizeof(unsigned long long)));
@@ -71,9 +72,8 @@ void timeline(const char* name, int batch, int pad_blocks) {
   CK(hipMalloc(&dones, ones.size() * sizeof(double)));
   CK(hipMemcpy(dones, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice));
   FrugalArgs a{d, dtw, ditems, pitch, item_stride, nullptr, nullptr, nullptr, dones, dst};
-  constexpr bool SPLIT = sizeof(T) == 8;
-  const size_t lds = frugal_lds_bytes<T, N, LINES, 1, SPLIT, KPRE, KMID, E>();
-  auto kf = frugal_pass_kernel<T, N, E, LINES, 1, AXIS, BR, BC, SPLIT, KPRE, KMID, NFFT>;
+  const size_t lds = G::LDS;
+  auto kf = frugal_pass_kernel<T, N, E, LINES, 1, AXIS, BR, BC, G::SPLIT, KPRE, KMID, NFFT>;
   CK(hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));

@@ -1,7 +1,7 @@
 // xposebench: the exchange INSIDE a group of 16 lanes that the 16 x [16 x 16] decomposition of a 4096-point
-// transform needs between its second and third radix-16 stage (fft_core.h: fft4096_nat_to_swapped, X2) -- a
+// transform needs between its second and third radix-16 stage (the retired variant of DESIGN.md, "Retired with numbers": X2) -- a
 // 16 x 16 transposition between the register index and the low four lane bits of complex128 values -- done
-//   (a) through LDS without a barrier (what the library's digit-swapped variant does: 17-padded rows), and
+//   (a) through LDS without a barrier (what that variant did: 17-padded rows), and
 //   (b) with wavefront shuffles only (north star: "wavefront __shfl butterflies for the inner radices"):
 //       four xor-butterfly steps, each swapping half of the registers with the lane 1 << s away.
 // Count per thread and transposition: (a) 32 ds_write_b64 + 32 ds_read_b64 (re and im in turn), a dozen VALU;
