@@ -370,6 +370,12 @@ enum { PAOS_ZOOM_PSF = 0, PAOS_ZOOM_FIELD = 1 };
  * than 256 distinct fractional parts among the centres of one call.
  * PAOS_EHIP when the scratch cannot be allocated (the context stays usable; no window is available then). */
 int paos_zoom_compute(paos_ctx* ctx, int m, int s, const double* centres, int want_field);
+/* The launch plan of paos_zoom_compute for a context of `batch` items on an n x n grid and windows of m samples, host only
+ * and context-free like paos_zoom_weights: the number of 16-row tiles a wave owns (8, 4, 2 or 1) in the column contraction
+ * (*pt_y) and in the row contraction (*pt_x).  It is the rule paos_zoom_compute itself launches by, so a test can tell
+ * which builds of the kernel a case reaches; a window's bits do not depend on it.  PAOS_EINVAL for m as for
+ * paos_zoom_compute, n not a multiple of 16 in 16 .. 2^20, batch < 1 and null pointers. */
+int paos_zoom_tiles(int n, int batch, int m, int* pt_y, int* pt_x);
 /* One item's window to the host, row-major [p][q]: PAOS_ZOOM_PSF m x m doubles, PAOS_ZOOM_FIELD m x m complex128.
  * Synchronises.  The buffers are a snapshot of the field at the time of paos_zoom_compute: nothing tracks whether the
  * field has changed since.  PAOS_EINVAL before any paos_zoom_compute, for a bad item or `what`, a null buffer, and for

@@ -97,6 +97,8 @@ SYMBOLS = {
     "paos_zoom_weights": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_double, _dbl_p, ctypes.POINTER(ctypes.c_int)]),
     "paos_zoom_compute": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, _dbl_p, ctypes.c_int]),
     "paos_zoom_fetch": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "paos_zoom_tiles": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                       ctypes.POINTER(ctypes.c_int)]),
     "paos_run_passes": (ctypes.c_int, [_c_ctx, ctypes.POINTER(Pass), ctypes.c_int, _dbl_p, ctypes.c_int]),
     "paos_copy_yardstick": (ctypes.c_int, [_c_ctx, ctypes.c_int, _dbl_p, _dbl_p]),
     "paos_record_set_stats": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
@@ -187,6 +189,15 @@ def zoom_check(size, oversample, n):
         raise ValueError(f"a zoomed window's oversampling must be an integer in 1 .. 64, got {oversample!r}")
     if size > oversample * n:
         raise ValueError(f"a zoomed window of {size} samples at oversampling {oversample} is wider than the {n}-pixel grid")
+
+
+def zoom_tiles(n, batch, size):
+    """(tiles per wave of stage Y, of stage X): the launch plan paos_zoom_compute uses for windows of ``size`` samples in
+    a context of ``batch`` items on an n x n grid (paos_zoom_tiles: host only, needs no device)."""
+    pty, ptx = ctypes.c_int(0), ctypes.c_int(0)
+    if load().paos_zoom_tiles(int(n), int(batch), int(size), ctypes.byref(pty), ctypes.byref(ptx)) != 0:
+        raise ValueError(f"paos_zoom_tiles refused n={n!r}, batch={batch!r}, size={size!r}")
+    return pty.value, ptx.value
 
 
 def zoom_centres(centres, batch, n):

@@ -40,6 +40,37 @@ int paos_zoom_weights(int n, int s, double frac, double* w, int* carry) {
 
 namespace {
 
+const char* const kZoomBadSize = "the window size must be a multiple of 16 in 16 .. 1024";
+
+bool zoom_size_ok(int m) { return m >= 16 && m <= 1024 && !(m & 15); }
+
+// the largest number of 16-row tiles per wave (8, 4, 2, 1) that still leaves a wave for every SIMD of the chip
+int zoom_tiles_per_wave(int tiles, long waves_at_one) {
+  int pt = 8;
+  while (pt > 1 && (pt > tiles || waves_at_one / pt < 1024)) pt /= 2;
+  return pt;
+}
+
+}  // namespace
+
+extern "C" {
+
+int paos_zoom_tiles(int n, int batch, int m, int* pt_y, int* pt_x) {
+  if (n < 16 || (n & 15) || n > (1 << 20)) return fail(nullptr, PAOS_EINVAL, "paos_zoom_tiles: n must be a multiple of 16 in 16 .. 2^20");
+  if (batch < 1) return fail(nullptr, PAOS_EINVAL, "paos_zoom_tiles: batch must be at least 1");
+  if (!zoom_size_ok(m)) return fail(nullptr, PAOS_EINVAL, std::string("paos_zoom_tiles: ") + kZoomBadSize);
+  if (!pt_y || !pt_x) return fail(nullptr, PAOS_EINVAL, "paos_zoom_tiles: null argument");
+  const int tiles = m / 16;
+  // a wave owns 16 columns d: N / 16 column tiles in stage Y (d runs over the grid), M / 16 in stage X (over the window)
+  *pt_y = zoom_tiles_per_wave(tiles, (long)batch * (n / 16) * tiles);
+  *pt_x = zoom_tiles_per_wave(tiles, (long)batch * tiles * tiles);
+  return PAOS_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
 constexpr int kZoomMaxTables = 256;  // tables the pool keeps; also the most distinct fractional parts of one call
 
 // Slots of the [s][n] phase tables of `fracs` (distinct values, all of ONE call) in the context's pool.  Every slot of
@@ -109,13 +140,6 @@ int zoom_table_slots(paos_ctx* c, int s, const std::vector<double>& fracs, std::
   return PAOS_OK;
 }
 
-// the largest number of 16-row tiles per wave (8, 4, 2, 1) that still leaves a wave for every SIMD of the chip
-int zoom_tiles_per_wave(int tiles, long waves_at_one) {
-  int pt = 8;
-  while (pt > 1 && (pt > tiles || waves_at_one / pt < 1024)) pt /= 2;
-  return pt;
-}
-
 template <typename T, int STAGE>
 void zoom_launch(paos_ctx* c, const ZoomArgs& a, int pt) {
   const dim3 block(64 * kZoomWaves);
@@ -136,7 +160,7 @@ int paos_zoom_compute(paos_ctx* c, int m, int s, const double* centres, int want
   SETTLE_SCALE(c);  // a deferred stop factor belongs to the field the window is taken of
   if (c) (void)hipSetDevice(c->device);
   if (!c) return fail(c, PAOS_EINVAL, "null context");
-  if (m < 16 || m > 1024 || (m & 15)) return fail(c, PAOS_EINVAL, "paos_zoom_compute: the window size must be a multiple of 16 in 16 .. 1024");
+  if (!zoom_size_ok(m)) return fail(c, PAOS_EINVAL, std::string("paos_zoom_compute: ") + kZoomBadSize);
   if (s < 1 || s > 64) return fail(c, PAOS_EINVAL, "paos_zoom_compute: the oversampling must be an integer in 1 .. 64");
   if ((long)m > (long)s * c->n) return fail(c, PAOS_EINVAL, "paos_zoom_compute: the window is wider than the grid (m > s n)");
   const int n = c->n, nb = c->batch;
@@ -222,7 +246,9 @@ int paos_zoom_compute(paos_ctx* c, int m, int s, const double* centres, int want
   a.src = c->field;
   a.dst_c = c->zoom_t;
   a.nd = n / 16;
-  const int pty = zoom_tiles_per_wave(m / 16, (long)nb * (n / 16) * (m / 16));
+  int pty = 1, ptx = 1;
+  rc = paos_zoom_tiles(n, nb, m, &pty, &ptx);  // the one rule of the launch plan, as the host-side query reports it
+  if (rc) return rc;
   if (c->precision == PAOS_F64) zoom_launch<double, 0>(c, a, pty);
   else zoom_launch<float, 0>(c, a, pty);
   HIPCHK(c, hipGetLastError());
@@ -231,7 +257,7 @@ int paos_zoom_compute(paos_ctx* c, int m, int s, const double* centres, int want
   a.dst_c = want_field ? c->zoom_field : nullptr;
   a.dst_i = c->zoom_psf;
   a.nd = m / 16;
-  zoom_launch<double, 1>(c, a, zoom_tiles_per_wave(m / 16, (long)nb * (m / 16) * (m / 16)));
+  zoom_launch<double, 1>(c, a, ptx);
   HIPCHK(c, hipGetLastError());
   c->zoom_done = true;
   c->zoom_has_field = want_field != 0;

@@ -19,13 +19,7 @@ TARGETS = (1.0, 1e3, 1e6, 1e9, 0.99e12)  # phase argument at the grid corner, ra
 # the runs of one phase case: two targets per run, the third item disabled
 RUNS = ((1.0, 1e3), (1e6, 1e9), (0.99e12, 1.0))
 DT = {"fp64": np.complex128, "fp32": np.complex64}
-# fp32 phase factors (slot_factor32: hardware v_sin_f32 / v_cos_f32 on a fraction of a turn; the generic kernels:
-# sincos_fast, then one rounding to fp32): largest error observed on an MI355X, per family, and the bound pinned at twice
-# that -- never above 16 u32 per factor.  generic: max |factor - exp(i q)| of the stand-alone passes (0.7 u32).  frugal:
-# the slots' factors cannot be read without a transform, so this is the largest per-line L2 error of a frugal32 case of
-# test_phases_riding_on_transforms, two 4096-point transforms included (8.6 u32): an upper bound on the factor's share.
-FP32_OBSERVED = {"generic": 4.21e-8, "frugal": 5.12e-7}
-FP32_FACTOR_BOUND = {k: min(2.0 * v, 16 * xp.U32) for k, v in FP32_OBSERVED.items()}
+FP32_FACTOR_BOUND = xp.FP32_FACTOR_BOUND  # (tests/xprec_np.py: one value for every module that prices fp32 phase factors)
 
 _FIELDS = {}
 

@@ -270,3 +270,52 @@ def test_without_the_keyword_nothing_changes():
     res = run_batch(1.0, [1.0e-6], 64, 4, FIELD, [syn20_chain()], outputs=("psf",), dev=dev)
     assert not any(k.startswith("zoom") for rec in res[0].values() for k in rec)
     assert not any(name.startswith("zoom") for name, _ in dev.log)
+
+
+# ---- the launch plan (paos_zoom_tiles) and what the long-double cases reach of it ----------------------------------------
+def test_launch_plan_query():
+    """paos_zoom_tiles is the rule paos_zoom_compute launches by: the largest of 8, 4, 2, 1 tiles per wave that still
+    leaves 1024 waves and is no more than the window has tiles."""
+    assert _lib.zoom_tiles(64, 1, 16) == (1, 1)
+    assert _lib.zoom_tiles(4096, 1, 64) == (1, 1)  # 256 x 4 waves at one tile: exactly 1024
+    assert _lib.zoom_tiles(4096, 2, 64) == (2, 1)
+    assert _lib.zoom_tiles(4096, 32, 1024) == (8, 8)
+    assert _lib.zoom_tiles(1024, 2, 256) == (2, 1)  # (what tests/test_gpu_zoom.py reaches)
+    lib = _lib.load()
+    a, b = ctypes.c_int(-1), ctypes.c_int(-1)
+    for n, batch, m in [(256, 1, 24), (256, 1, 8), (256, 1, 0), (256, 1, 1040), (256, 0, 16), (256, -3, 16), (250, 1, 16),
+                        (0, 1, 16), (-256, 1, 16)]:
+        assert lib.paos_zoom_tiles(n, batch, m, ctypes.byref(a), ctypes.byref(b)) == 1, (n, batch, m)
+    assert lib.paos_zoom_tiles(256, 1, 16, None, ctypes.byref(b)) == 1
+    assert lib.paos_zoom_tiles(256, 1, 16, ctypes.byref(a), None) == 1
+    assert (a.value, b.value) == (-1, -1)
+    with pytest.raises(ValueError):
+        _lib.zoom_tiles(256, 1, 24)
+
+
+def test_the_long_double_cases_reach_every_build():
+    """tests/test_gpu_products_xprec.py runs products_xprec.ZOOM_CASES and, for the bit-for-bit check, each of them in a
+    batch-1 context.  From the library's own rule: together they launch zoom_kernel<T, STAGE, PT> for both stages at
+    every PT, each stage with a partial last group at some PT > 1, and the batch-1 companions at PT 1 for both stages.
+    A changed rule that leaves a build unreached fails here."""
+    import products_xprec as px
+
+    table = {(1024, 16, 128, 4): (8, 1), (1024, 11, 192, 4): (8, 1), (1024, 7, 160, 3): (4, 1), (2048, 4, 128, 4): (4, 1),
+             (256, 16, 256, 2): (4, 4), (512, 8, 320, 3): (4, 2), (256, 10, 240, 2): (2, 2), (256, 9, 496, 4): (4, 8),
+             (256, 8, 512, 4): (4, 8)}
+    assert sorted(px.ZOOM_CASES) == sorted(table)
+    reached, partial = set(), set()
+    for n, batch, m, s in px.ZOOM_CASES:
+        _lib.zoom_check(m, s, n)
+        pt = _lib.zoom_tiles(n, batch, m)
+        assert pt == table[(n, batch, m, s)], ((n, batch, m, s), pt)
+        assert _lib.zoom_tiles(n, 1, m) == (1, 1), (n, m)
+        for stage, p in zip("YX", pt):
+            reached.update({(stage, p), (stage, 1)})  # (the case itself and its batch-1 companion)
+            if p > 1 and (m // 16) % p:
+                partial.add(stage)
+    assert reached == {(stage, p) for stage in "YX" for p in (1, 2, 4, 8)}, sorted(reached)
+    assert partial == {"Y", "X"}, partial
+    # a partial group at PT 8 and at PT 4 in stage Y, at PT 2 and PT 8 in stage X (the table of the cases)
+    assert _lib.zoom_tiles(1024, 11, 192) == (8, 1) and 12 % 8 and _lib.zoom_tiles(1024, 7, 160)[0] == 4 and 10 % 4
+    assert _lib.zoom_tiles(256, 10, 240) == (2, 2) and 15 % 2 and _lib.zoom_tiles(256, 9, 496)[1] == 8 and 31 % 8

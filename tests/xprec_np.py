@@ -25,6 +25,13 @@ LD = np.clongdouble
 U64 = 2.0**-53
 U32 = 2.0**-24
 TWO_PI = 6.283185307179586  # the fp64 constant of the reference (2 * np.pi) and the kernels
+# fp32 phase factors (slot_factor32: hardware v_sin_f32 / v_cos_f32 on a fraction of a turn; the generic kernels:
+# sincos_fast, then one rounding to fp32): largest error observed on an MI355X, per family, and the bound pinned at twice
+# that -- never above 16 u32 per factor.  generic: max |factor - exp(i q)| of the stand-alone passes (0.7 u32).  frugal:
+# the slots' factors cannot be read without a transform, so this is the largest per-line L2 error of a frugal32 case of
+# test_phases_riding_on_transforms, two 4096-point transforms included (8.6 u32): an upper bound on the factor's share.
+FP32_OBSERVED = {"generic": 4.21e-8, "frugal": 5.12e-7}
+FP32_FACTOR_BOUND = {k: min(2.0 * v, 16 * U32) for k, v in FP32_OBSERVED.items()}
 
 
 def require_long_double():
