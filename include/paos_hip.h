@@ -248,14 +248,18 @@ int paos_phase(paos_ctx* ctx, const double* params, int mul2pi);
 /* Tabulated phase screen, the field part of WFO.grid_sag (wfo.py:869-871) and WFO.psd
  * (wfo.py:945-949): u[item] *= exp(2 pi i wfe / wl) with wfe a host map in metres (row-major
  * n x n doubles, finite: masked pixels filled with 0 as the reference does).  The resampling of a
- * sag map and the random draw of a PSD screen stay on the host (paos_amd/wfo.py).  Synchronises. */
+ * sag map and the random draw of a PSD screen stay on the host (paos_amd/wfo.py).  Synchronises.
+ * PAOS_EINVAL, the field untouched, also for a finite map whose argument is not: the kernel forms fl(fl(2 pi w) / wl), and
+ * the map's largest |w| must leave that finite (|w| near 1e308, or any w over a tiny wl, would put NaN into the field). */
 int paos_phase_map(paos_ctx* ctx, int item, const double* host_wfe, double wl);
 /* Round 5: the same for `n_items` items that share ONE map (a measured surface map is the same for every wavelength of a
  * sweep and every draw of a Monte-Carlo study): items[k] (indices, as doubles) get u *= exp(2 pi i wfe / wl[k]).  The map
  * crosses PCIe once and stays on the device; `key` != 0 names its content: a later call with the same key skips the
  * validation and the upload (the caller vouches that the host buffer still holds what was uploaded under that key;
  * 0 = always upload).  `host_wfe` may be NULL when a map is kept under `key` (paos_psd_screen).  Does not synchronise when
- * the key matches. */
+ * the key matches.  PAOS_EINVAL, the field untouched: an item listed twice (two slices of the launch would update one field
+ * in no order), and a wavelength at which fl(fl(2 pi max|wfe|) / wl) is not finite -- max|wfe| is kept with the map, so a
+ * later call under the same key with a smaller wavelength is held to it as well. */
 int paos_phase_map_items(paos_ctx* ctx, const double* host_wfe, unsigned long long key, int n_items, const double* items,
                          const double* wl);
 /* Round 5: the random screen of WFO.psd built ON THE DEVICE (wfo.py:908-943 calling psd.py:100-160): the host draws the
@@ -409,6 +413,11 @@ int paos_record_set_stats(paos_ctx* ctx, unsigned long long* found, unsigned lon
  * the ordinary build (*plain).  PAOS_CENTRAL_HALF=0 / 1 in the environment when the context is created switches the
  * central-half builds off / on; results are equal as numbers either way. */
 int paos_central_half_stats(paos_ctx* ctx, unsigned long long* central, unsigned long long* plain);
+/* Test aid: what became of the factors paos_stop_defer_last_power left pending, since the context was created: *rode
+ * counts those the first pass of the next pass program multiplied into its middle slot, *settled those applied by the
+ * scaling sweep (or dropped, where the field was about to be overwritten) because something else came first.  A test
+ * that means to cover one route can tell that it did. */
+int paos_deferred_stop_stats(paos_ctx* ctx, unsigned long long* rode, unsigned long long* settled);
 /* Measurement / test aid: on = 0 makes every pass process every tile (no dead-line pruning). */
 int paos_ctx_set_pruning(paos_ctx* ctx, int on);
 int paos_run_passes_live(paos_ctx* ctx, const paos_pass* passes, int n_passes, const double* blocks,

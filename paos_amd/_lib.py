@@ -103,6 +103,7 @@ SYMBOLS = {
     "paos_copy_yardstick": (ctypes.c_int, [_c_ctx, ctypes.c_int, _dbl_p, _dbl_p]),
     "paos_record_set_stats": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
     "paos_central_half_stats": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
+    "paos_deferred_stop_stats": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
     "paos_ctx_set_pruning": (ctypes.c_int, [_c_ctx, ctypes.c_int]),
     "paos_run_passes_live": (ctypes.c_int, [_c_ctx, ctypes.POINTER(Pass), ctypes.c_int, _dbl_p, ctypes.c_int, _dbl_p]),
     "paos_zernike": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, _dbl_p, _dbl_p, ctypes.c_int, _dbl_p]),
@@ -719,6 +720,14 @@ class DeviceFields:
         self._check(self._lib.paos_central_half_stats(self._ctx, ctypes.byref(central), ctypes.byref(plain)),
                     "paos_central_half_stats")
         return int(central.value), int(plain.value)
+
+    def deferred_stop_stats(self):
+        """(rode, settled): deferred stop factors (``make_stop(power_known=True, defer=True)``) that went into the first pass
+        of the next program / that were applied by the scaling sweep or dropped, since creation."""
+        rode, settled = ctypes.c_ulonglong(0), ctypes.c_ulonglong(0)
+        self._check(self._lib.paos_deferred_stop_stats(self._ctx, ctypes.byref(rode), ctypes.byref(settled)),
+                    "paos_deferred_stop_stats")
+        return int(rode.value), int(settled.value)
 
     def set_pruning(self, on):
         """Dead-line pruning of the pass programs on (default) / off -- results are identical."""

@@ -488,6 +488,13 @@ int paos_central_half_stats(paos_ctx* c, unsigned long long* central, unsigned l
   return PAOS_OK;
 }
 
+int paos_deferred_stop_stats(paos_ctx* c, unsigned long long* rode, unsigned long long* settled) {
+  if (!c || !rode || !settled) return fail(c, PAOS_EINVAL, "bad deferred-stop request");
+  *rode = c->deferred_rode;
+  *settled = c->deferred_settled;
+  return PAOS_OK;
+}
+
 int paos_ctx_set_pruning(paos_ctx* c, int on) {
   if (!c) return fail(c, PAOS_EINVAL, "null context");
   c->prune = on != 0;

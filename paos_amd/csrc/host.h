@@ -103,6 +103,7 @@ struct paos_ctx {
   std::vector<std::vector<int>> zoom_carry;
   double* map_dev = nullptr;      // one n x n phase map kept on the device (paos_phase_map_items) and the key it was uploaded under
   unsigned long long map_key = 0;
+  double map_max = 0.0;  // max |w| of the kept map: fl(fl(2 pi max) / wl) must stay finite for every wavelength it is applied at
   // (round 5) the power sums of the last start, kept with everything they depend on (shape, constant, aperture records,
   // stop flags): the entrance pupil of a wavelength sweep or a Monte-Carlo study is the same step after step, and the sums
   // are a pure function of those -- the next start with the same key copies them instead of evaluating the exact pixel
@@ -121,6 +122,8 @@ struct paos_ctx {
   int ptab_slots = 0;          // program about to run (FrugalSlot::table; stage_groups)
   double* dyn_scale = nullptr;
   bool dyn_pending = false;
+  // a pending factor went into a program's first pass / was applied by the sweep or dropped (paos_deferred_stop_stats)
+  unsigned long long deferred_rode = 0, deferred_settled = 0;
   // c->norm2 holds sum |u|^2 of the field exactly as it is stored: set by a pass program whose last pass summed it on the
   // way out (paos_run_program, final_intensity = 2), cleared by every entry point that reads or rewrites the field or
   // reduces into c->norm2 (SETTLE_SCALE / DROP_SCALE sit at the top of all of them).  paos_stop_scale_last_power and

@@ -50,6 +50,7 @@ int dyn_scale_reset(paos_ctx* c) {
 // scaling is applied now, by the sweep make_stop would have run (same factor, same products: bit-identical).
 int settle_scale(paos_ctx* c, bool field_is_overwritten) {
   if (!c->dyn_pending) return PAOS_OK;
+  ++c->deferred_settled;
   if (!field_is_overwritten) {
     const dim3 grid(pw_blocks(c), c->batch), block(kPwThreads);
     if (c->precision == PAOS_F64)
@@ -120,6 +121,12 @@ int pointwise_pass(paos_ctx* c, const PassArgs& a) {
 }
 
 namespace {
+
+// The phase-map kernels form fl(fl(2 pi w) / wl): a finite map value can overflow there (|w| near 1e308, or any w over a
+// tiny wavelength), and sincos(inf) would write NaN into the field.  |.| and both roundings are monotone, so the map's
+// largest |w| decides for the whole map.
+const char* const kPhaseMapOverflow = "the phase argument 2 pi w / wl of the map's largest value is not finite";
+bool phase_map_argument_finite(double wmax, double wl) { return std::isfinite((6.283185307179586 * wmax) / wl); }
 
 // groups of items with one wfe map share its evaluation (start_impl, zernike_apply); PAOS_SHARE_WFE=0: never
 bool share_wfe_maps() {
@@ -791,8 +798,12 @@ int paos_phase_map(paos_ctx* c, int item, const double* host_wfe, double wl) {
   if (!c || !host_wfe || item < 0 || item >= c->batch) return fail(c, PAOS_EINVAL, "bad item or null buffer");
   if (!(wl > 0.0) || !std::isfinite(wl)) return fail(c, PAOS_EINVAL, "wavelength must be positive and finite");
   const size_t count = (size_t)c->n * c->n;
-  for (size_t i = 0; i < count; ++i)  // the device sincos handles any finite argument; reject the rest here
+  double wmax = 0.0;
+  for (size_t i = 0; i < count; ++i) {  // the device sincos handles any finite argument; reject the rest here
     if (!std::isfinite(host_wfe[i])) return fail(c, PAOS_EINVAL, "the phase map holds a non-finite value (fill masked pixels with 0)");
+    wmax = std::max(wmax, std::fabs(host_wfe[i]));
+  }
+  if (!phase_map_argument_finite(wmax, wl)) return fail(c, PAOS_EINVAL, kPhaseMapOverflow);
   HIPCHK(c, hipMemcpyAsync(c->staging, host_wfe, count * sizeof(double), hipMemcpyHostToDevice, c->stream));
   if (c->precision == PAOS_F64)
     hipLaunchKernelGGL((phase_map_kernel<double, BR, Lay<double>::BC>), dim3(pw_blocks(c)), dim3(kPwThreads), 0, c->stream,
@@ -814,17 +825,27 @@ int paos_phase_map_items(paos_ctx* c, const double* host_wfe, unsigned long long
   for (int k = 0; k < n_items; ++k) {
     if (!(items[k] >= 0.0) || items[k] >= (double)c->batch || items[k] != (double)(int)items[k]) return fail(c, PAOS_EINVAL, "bad item index");
     if (!(wl[k] > 0.0) || !std::isfinite(wl[k])) return fail(c, PAOS_EINVAL, "wavelength must be positive and finite");
+    // (two slices of one launch would read, modify and write the same field in no order)
+    for (int j = 0; j < k; ++j)
+      if (items[j] == items[k]) return fail(c, PAOS_EINVAL, "an item is listed twice");
   }
   const size_t count = (size_t)c->n * c->n;
   if (!c->map_dev) HIPCHK(c, hipMalloc(&c->map_dev, count * sizeof(double)));
   if (key == 0 || key != c->map_key) {  // (the same key again: the caller vouches that the map is the one uploaded under it)
-    for (size_t i = 0; i < count; ++i)  // the device sincos handles any finite argument; reject the rest here
+    double wmax = 0.0;
+    for (size_t i = 0; i < count; ++i) {  // the device sincos handles any finite argument; reject the rest here
       if (!std::isfinite(host_wfe[i])) return fail(c, PAOS_EINVAL, "the phase map holds a non-finite value (fill masked pixels with 0)");
+      wmax = std::max(wmax, std::fabs(host_wfe[i]));
+    }
     c->map_key = 0;
     HIPCHK(c, hipMemcpyAsync(c->map_dev, host_wfe, count * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // the host buffer is only borrowed
     c->map_key = key;
+    c->map_max = wmax;
   }
+  // (the kept map's largest value decides for every wavelength it is ever applied at, a later call's smaller one included)
+  for (int k = 0; k < n_items; ++k)
+    if (!phase_map_argument_finite(c->map_max, wl[k])) return fail(c, PAOS_EINVAL, kPhaseMapOverflow);
   const double *ditems = nullptr, *dwl = nullptr;
   int rc;
   if ((rc = arena_push(c, items, (size_t)n_items, &ditems))) return rc;
@@ -884,9 +905,15 @@ int paos_psd_screen(paos_ctx* c, const double* host_noise, const double* host_ro
   HIPCHK(c, hipMemcpyAsync(&bad, c->psd_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));  // (the host buffers were only borrowed)
   if (bad) return fail(c, PAOS_EINVAL, "the PSD screen holds a non-finite value");
-  if (host_out) {
-    rc = copy_to_host(c, host_out, c->map_dev, count * sizeof(double));
+  {  // the largest value of the map, for the wavelengths paos_phase_map_items will apply it at
+    std::vector<double> own;
+    double* host = host_out;
+    if (!host) { own.resize(count); host = own.data(); }
+    rc = copy_to_host(c, host, c->map_dev, count * sizeof(double));
     if (rc) return rc;
+    double wmax = 0.0;
+    for (size_t i = 0; i < count; ++i) wmax = std::max(wmax, std::fabs(host[i]));
+    c->map_max = wmax;
   }
   c->map_key = key;
   return PAOS_OK;

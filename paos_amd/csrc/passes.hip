@@ -476,6 +476,7 @@ int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const do
     bool ride = n_passes > 0 && low[0].ok;
     if (ride)
       for (const FrugalItem& fi : low[0].items) ride = ride && fi.active != 0.0;
+    if (ride) ++c->deferred_rode;
     if (!ride && (rc = settle_scale(c))) return rc;
   }
   const bool pruned = all_frugal && use_pruning() && c->prune;

@@ -699,7 +699,8 @@ def test_power_summed_by_the_storing_pass_equals_the_separate_reduction():
     """Round 4: the power of a saved surface rides on the pass that stores its field (STORE = 2 builds of the pass kernel,
     paos_run_program: final_intensity = 2).  Ariel_AIRS-CH0 (12 saved surfaces, apertures riding on passes) and
     Excite_TEL at 1024^2 / 2048^2, fp64 and fp32: the powers equal those of the ordinary reductions
-    (PAOS_POWER_ON_STORE off) and the sum over the downloaded field."""
+    (PAOS_POWER_ON_STORE off) and the sum over the downloaded field.  (Path against path; the sums themselves are held to a
+    long-double reference by tests/test_gpu_ledger_xprec.py::test_power_on_store_against_long_double.)"""
     import paos_amd.run as prun
     from paos_amd.chains import parse_config_variant
     from paos_amd.run import run_batch
@@ -730,7 +731,9 @@ def test_a_stop_whose_scaling_rides_on_the_next_pass():
     scaling 1 / sqrt(P) is multiplied into the middle slot of the NEXT program's first pass (paos_stop_defer_last_power):
     the stop costs no sweep over the field.  A lean walk (the ride) against the same walk with the scaling sweep at the
     stop and against the round-3 make_stop: PSFs and powers to 1e-13 (fp32: 1e-6); with arrays downloaded at the stop
-    (the library applies the factor before anything else reads the field) bit-identical to the sweep."""
+    (the library applies the factor before anything else reads the field) bit-identical to the sweep.  (Which of the two
+    happened, and the stop's error against a long-double reference:
+    tests/test_gpu_ledger_xprec.py::test_stop_from_a_known_power_swept_deferred_and_riding.)"""
     import paos_amd.run as prun
     from paos_amd import _lib
     from paos_amd.chains import parse_config_variant

@@ -150,7 +150,8 @@ def test_a_shared_grid_sag_screen_is_uploaded_once_and_equals_the_per_item_path(
     """Round 5: SYN20 behind ONE white-noise grid-sag screen for all items (bench.py's `extra.dense`
     chain): the map is built once (``run._sag_map_once``) and applied by ``paos_phase_map_items`` -- one upload for the
     batch, none for the next batch.  PSFs equal those of the per-item path (every item its own copy of the array ->
-    ``paos_phase_map`` per item) bit for bit, on the same context and on the next step."""
+    ``paos_phase_map`` per item) bit for bit, on the same context and on the next step.  (Both kernels against a long-double
+    reference at arguments up to 1e12 rad: tests/test_gpu_ledger_xprec.py::test_phase_maps_against_long_double.)"""
     import bench_extras
     from paos_amd import _lib
     from paos_amd.chains import syn20_wavelength
@@ -178,7 +179,9 @@ def test_a_shared_grid_sag_screen_is_uploaded_once_and_equals_the_per_item_path(
 def test_psd_screen_built_on_the_device_vs_reference_vectors():
     """Round 5: ``paos_psd_screen`` -- fft2(noise) -> power-law filter -> ifft2 -> roughness on the
     library's own passes -- against the reference's vectors (tests/golden/r2_phase_maps.npz; the host path reproduces them
-    bit for bit, test_gpu_r2.py): the maps to 1e-13 of their peak, the fields behind them to 1e-12."""
+    bit for bit, test_gpu_r2.py): the maps to 1e-13 of their peak, the fields behind them to 1e-12.  (The maps at
+    (8 log2 n + 8) u against a long-double reference, band edges placed on bins:
+    tests/test_gpu_ledger_xprec.py::test_psd_screen_against_long_double.)"""
     from conftest import load_golden
     from paos_amd import phase_maps
     from paos_amd.wfo import WFO
@@ -210,7 +213,8 @@ def test_psd_screen_built_on_the_device_vs_reference_vectors():
 def test_psd_screen_on_the_device_equals_the_host_path(n):
     """... and at the sizes that take the device path by default, against the host path (NumPy's FFTs) on the same draws:
     maps to 1e-13 of their peak, the generator left in the same state, the kept map applied to two items of a batch with
-    their own wavelengths; the error paths of the two entry points."""
+    their own wavelengths; the error paths of the two entry points.  (Stricter sibling at 64^2 .. 1024^2:
+    tests/test_gpu_ledger_xprec.py::test_psd_screen_against_long_double.)"""
     from paos_amd import _lib, phase_maps
 
     kw = dict(A=12.0, B=1.0, C=2.2, fknee=3.0, fmin=None, fmax=None, SR=0.5, units="nm")
