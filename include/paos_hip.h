@@ -339,6 +339,39 @@ int paos_otf_fetch(paos_ctx* ctx, int item, int what, void* host_out);
  * the fetched array by the mirror symmetry) -- bit for bit the values paos_otf_fetch hands out.  Synchronises.
  * PAOS_EINVAL as for paos_otf_fetch. */
 int paos_otf_cuts(paos_ctx* ctx, double* host_out);
+/* ---- blurred PSFs: jitter, charge diffusion and pixel aperture on the kept spectrum (README.md, "Blurred PSFs") --------- */
+/* No reference counterpart.  What an instrument records is the optical PSF convolved with the line-of-sight jitter of the
+ * exposure, the charge diffusion of the detector and, for a sampled "effective PSF", the pixel aperture: each a real, even
+ * transfer function on the PSF's spectrum.  Per axis one table of N/2 + 1 doubles, entry m = 0 .. N/2:
+ *   f_m = m / (N d)  (cycles per metre; d = dx or dy),   t[m] = exp(-2 pi^2 sigma^2 f_m^2) sinc(p f_m),
+ *   sinc(x) = sin(pi x) / (pi x), sinc(0) = 1
+ * with sigma the Gaussian 1-sigma blur along that axis in metres at the image plane (jitter and diffusion add in
+ * quadrature: pass their root sum of squares) and p the pixel width along that axis in metres (0: no pixel factor).
+ * The blurred PSF is
+ *   P' = ifft2(T fft2(P)),   T[ky][kx] = ty[min(ky, N - ky)] tx[min(kx, N - kx)]   (unshifted indices)
+ * T is real and even, so P' is real; the convolution is circular; sum P' = sum P to rounding; nothing is clamped (with
+ * p > 0 the band-limited box rings and negative values are genuine; with sigma alone values below zero are rounding and
+ * the truncation at Nyquist).  A rotated jitter ellipse (a cross term fx fy) is not separable and not offered.
+ *
+ * paos_blur_table: the table of one axis, host only and context-free like paos_zoom_weights, evaluated in long double and
+ * rounded to double once; t[n/2 + 1], t[0] == 1.0 exactly.  PAOS_EINVAL for n odd or outside 2 .. 2^20, a d that is not
+ * finite and positive, a sigma or pixel that is not finite or is negative, and a null pointer. */
+int paos_blur_table(int n, double d, double sigma, double pixel, double* t);
+enum { PAOS_BLUR_ITEM = 6 };   /* dx, dy, sigma_x, sigma_y, pixel_x, pixel_y */
+/* per_item[batch][PAOS_BLUR_ITEM].  Builds and uploads every item's two tables and turns the spectra paos_otf_compute
+ * left into blurred PSFs by a packed real-output inverse 2-D transform (csrc/blur_pass.h; about N line transforms per
+ * item): a pass along the columns 0 .. N/2 of the spectrum buffer that multiplies element [ky][kx] by
+ * g = fl64(tx[.] ty[.]) (in an fp32 context g is then rounded to float; real and imaginary part times g once each; zero
+ * frequency has g = 1 and is unchanged), stores the product back and writes the row-pair-packed half-transformed image
+ * into the PSF buffer, then a pass along the N/2 packed lines in place on the PSF buffer that applies the 1 / N^2 of the
+ * inverse once (an exact power of two).  fp32 contexts transform in float and store doubles, as paos_otf_compute does.
+ * Enqueues only (no synchronisation).  Afterwards the PSF buffer holds P' -- paos_psf_fetch and every paos_detector_*
+ * call read it -- and the transfer functions stay valid: paos_otf_fetch / paos_otf_cuts hand out those of P', the SYSTEM
+ * OTF / MTF, Hermitian bit for bit and exactly 1 at zero frequency as before.  A second call compounds: it multiplies
+ * T2 onto the spectrum that already carries T1, and the PSF buffer then holds the image blurred by T2 T1.  The field is
+ * neither read nor written.  PAOS_EINVAL, the context left usable and both buffers untouched: before paos_otf_compute or
+ * when its result is stale (the test of paos_otf_fetch), a parameter paos_blur_table refuses, a null pointer. */
+int paos_blur_apply(paos_ctx* ctx, const double* per_item);
 /* ---- zoomed PSF windows: the field interpolated exactly onto a finer grid (README.md, "Zoomed PSFs") ------------------- */
 /* No reference counterpart.  With u[k][j] the N x N field of item i (rows k along y), its band-limited interpolant with the
  * Nyquist term split evenly is u(y, x) = sum_k sum_j u[k][j] d(y - k) d(x - j), d(t) = sin(pi t) / (N tan(pi t / N)),

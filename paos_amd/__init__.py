@@ -20,6 +20,10 @@ computed on the GPU by a packed real-input 2-D transform (README.md, "Transfer f
 
 ``run_batch(..., psf_zoom=PsfWindow(size, oversample))`` adds a window of the last surface's PSF on a finer grid: the
 exact band-limited interpolant of the field, two fp64 matrix-instruction contractions (README.md, "Zoomed PSFs").
+
+``run_batch(..., psf_blur=PsfBlur(sigma_x, sigma_y, pixel=...))`` blurs the last surface's kept PSFs by pointing jitter,
+charge diffusion and the pixel aperture: one multiplication on their spectra and a packed real-output inverse transform
+on the GPU; detector images and transfer functions are then the system ones (README.md, "Blurred PSFs").
 """
 from .abcd import ABCD
 from .coordinate_break import coordinate_break
@@ -28,8 +32,8 @@ from .zernike import Zernike
 
 from .raytrace import raytrace
 
-__all__ = ["ABCD", "Detector", "PsfWindow", "WFO", "Zernike", "coordinate_break", "parse_config", "raytrace", "run_batch",
-           "run_broadband", "run_sharded"]
+__all__ = ["ABCD", "Detector", "PsfBlur", "PsfWindow", "WFO", "Zernike", "coordinate_break", "parse_config", "raytrace",
+           "run_batch", "run_broadband", "run_sharded"]
 __version__ = "0.1.0"
 
 
@@ -45,6 +49,8 @@ def __getattr__(name):
         return importlib.import_module(".run", __name__).run_batch
     if name in ("Detector", "run_broadband"):
         return getattr(importlib.import_module(".detector", __name__), name)
+    if name == "PsfBlur":
+        return importlib.import_module(".blur", __name__).PsfBlur
     if name == "PsfWindow":
         return importlib.import_module(".zoom", __name__).PsfWindow
     if name == "run_sharded":

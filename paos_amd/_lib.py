@@ -94,6 +94,8 @@ SYMBOLS = {
     "paos_otf_compute": (ctypes.c_int, [_c_ctx]),
     "paos_otf_fetch": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "paos_otf_cuts": (ctypes.c_int, [_c_ctx, _dbl_p]),
+    "paos_blur_table": (ctypes.c_int, [ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, _dbl_p]),
+    "paos_blur_apply": (ctypes.c_int, [_c_ctx, _dbl_p]),
     "paos_zoom_weights": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_double, _dbl_p, ctypes.POINTER(ctypes.c_int)]),
     "paos_zoom_compute": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, _dbl_p, ctypes.c_int]),
     "paos_zoom_fetch": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
@@ -199,6 +201,17 @@ def zoom_tiles(n, batch, size):
     if load().paos_zoom_tiles(int(n), int(batch), int(size), ctypes.byref(pty), ctypes.byref(ptx)) != 0:
         raise ValueError(f"paos_zoom_tiles refused n={n!r}, batch={batch!r}, size={size!r}")
     return pty.value, ptx.value
+
+
+def blur_table(n, d, sigma, pixel=0.0):
+    """``t[m] = exp(-2 pi^2 sigma^2 f_m^2) sinc(pixel f_m)``, ``f_m = m / (n d)``, ``m = 0 .. n/2``: the transfer function of
+    one axis as paos_blur_apply multiplies it onto the spectrum (paos_blur_table: host only, needs no device)."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 2:
+        raise ValueError(f"paos_blur_table refused n={n!r}")
+    out = np.empty(int(n) // 2 + 1, dtype=np.float64)
+    if load().paos_blur_table(int(n), float(d), float(sigma), float(pixel), _dptr(out)) != 0:
+        raise ValueError(f"paos_blur_table refused n={n!r}, d={d!r}, sigma={sigma!r}, pixel={pixel!r}")
+    return out
 
 
 def zoom_centres(centres, batch, n):
@@ -676,6 +689,22 @@ class DeviceFields:
         out = np.empty((self.batch, 2, self.n // 2 + 1), dtype=np.float64)
         self._check(self._lib.paos_otf_cuts(self._ctx, _dptr(out)), "paos_otf_cuts")
         return out
+
+    # -- blurred PSFs (paos_blur_*: README.md, "Blurred PSFs") --------------------------------------------------------
+    def blur_apply(self, dxs, dys, sigma_x, sigma_y, pixel_x=0.0, pixel_y=0.0):
+        """Blur every item's kept PSF in place: the spectra of the last ``otf_compute`` times the separable transfer
+        function ``exp(-2 pi^2 (sigma_x^2 fx^2 + sigma_y^2 fy^2)) sinc(pixel_x fx) sinc(pixel_y fy)`` and a packed
+        real-output inverse 2-D transform back into the PSF buffer.  ``dxs`` / ``dys``: every item's sampling in metres;
+        the sigmas and pixel widths (metres) are scalars or one value per item.  Afterwards ``psf_fetch`` and the
+        detector calls read the blurred PSFs and ``otf_fetch`` / ``otf_cuts`` hand out the system transfer functions; a
+        second call compounds.  Refused (``PaosHipError``) without a valid ``otf_compute``.  Enqueued only."""
+        cols = [dxs, dys, sigma_x, sigma_y, pixel_x, pixel_y]
+        try:
+            per_item = np.stack([np.broadcast_to(np.asarray(col, dtype=np.float64), (self.batch,)) for col in cols], axis=1)
+        except ValueError:
+            raise ValueError(f"blur_apply takes scalars or one value per item ({self.batch})") from None
+        per_item = np.ascontiguousarray(per_item)
+        self._check(self._lib.paos_blur_apply(self._ctx, _dptr(per_item)), "paos_blur_apply")
 
     # -- zoomed windows (paos_zoom_*: README.md, "Zoomed PSFs") ------------------------------------------------------
     def zoom_compute(self, size, oversample, centres=None, field=False):

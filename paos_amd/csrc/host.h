@@ -89,6 +89,11 @@ struct paos_ctx {
   void* otf_spec = nullptr;
   bool otf_computed = false, otf_valid = false;
   double* otf_cuts = nullptr;  // [batch][2][N/2 + 1], allocated by the first paos_otf_cuts
+  // blurred PSFs (paos_blur_apply): the host copy of every item's two tables, [batch][2][N/2 + 1], and the (d, sigma, pixel)
+  // each was evaluated for, [batch][2][3] -- a table is a pure function of those, and its long-double evaluation costs
+  // more host time than the launches take on the device (the planes of a focus stack, the batches of a Monte-Carlo study
+  // and the steps of a benchmark ask for the same tables again)
+  std::vector<double> blur_tabs, blur_key;
   // zoomed windows (paos_zoom_compute): the column-contracted field T [batch][N][M] complex128, the windows [batch][M][M]
   // (intensities; the complex field when asked for) and the phase tables of the fractional centres seen so far -- slot k
   // of zoom_tabs holds the [s][N] table of zoom_fracs[k], zoom_carry[k] its carries (all for oversampling zoom_s)

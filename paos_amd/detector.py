@@ -64,12 +64,14 @@ class Detector:
 
 
 def run_broadband(pupil_diameter, wavelengths, weights, gridsize, zoom, field, opt_chains, detector, batch=32,
-                  precision="fp64", device=0, detector_origin=None):
+                  precision="fp64", device=0, detector_origin=None, psf_blur=None):
     """The broadband image of a wavelength sweep on ``detector``: ``sum_i w_i A_i`` over ``wavelengths[i]`` /
     ``weights[i]`` (``opt_chains``: one chain per wavelength, or one chain for all; their last surface must be saved).
     ``field``: one field point for all, or one per wavelength (the items are then (wavelength, field, weight) triples:
     a field-of-view study lists every wavelength once per field point).  ``detector_origin`` as for ``run_batch``: None,
-    ``"chief_ray"``, or an (items, 2) array of grid-centre positions.
+    ``"chief_ray"``, or an (items, 2) array of grid-centre positions.  ``psf_blur`` (a :class:`paos_amd.PsfBlur`, per-item
+    values one per wavelength) is passed on to ``run_batch``: every item's PSF is blurred before it is rebinned (README.md,
+    "Blurred PSFs"; blocks with a blur are issued with ``sync=True``, as ``run_batch`` asks).
 
     The sweep is walked in blocks of ``batch`` on one device context, each block issued as ``bench.measure`` issues a
     step (``run_batch`` with ``outputs=()``, the lean walk, ``keep_psf``, no synchronisation) and followed by
@@ -101,6 +103,12 @@ def run_broadband(pupil_diameter, wavelengths, weights, gridsize, zoom, field, o
         origins = np.array(detector_origin, dtype=np.float64)
         if origins.shape != (nw, 2):
             raise ValueError(f"detector_origin must have shape ({nw}, 2), got {origins.shape}")
+    if psf_blur is not None:
+        from .blur import PsfBlur
+
+        if not isinstance(psf_blur, PsfBlur):
+            raise ValueError(f"psf_blur must be a paos_amd.PsfBlur, got {psf_blur!r}")
+        psf_blur.check(nw)
     nb = min(int(batch), nw)
     dev = _lib.DeviceFields(int(gridsize), nb, precision, device)
     try:
@@ -121,9 +129,10 @@ def run_broadband(pupil_diameter, wavelengths, weights, gridsize, zoom, field, o
             f_blk = field if isinstance(field, dict) else [fields[i] for i in idx] + [fields[idx[-1]]] * pad
             o_blk = detector_origin if origins is None else origins[idx + [idx[-1]] * pad]
             w_blk = np.concatenate([w[idx], np.zeros(pad)])
+            blur = {} if psf_blur is None else {"psf_blur": psf_blur.take(idx + [idx[-1]] * pad)}
             res = run_batch(pupil_diameter, wl_blk, gridsize, zoom, f_blk, ch_blk, precision=precision, device=device,
-                            outputs=(), dev=dev, sync=False, keep_psf=True, detector=detector, detector_weights=w_blk,
-                            detector_origin=o_blk)
+                            outputs=(), dev=dev, sync=psf_blur is not None, keep_psf=True, detector=detector,
+                            detector_weights=w_blk, detector_origin=o_blk, **blur)
             num = _last_num(ch_blk[0])
             handle = res[0][num].get("power_ticket")
             # every other reduction of the block is given back unread (as bench.measure does)

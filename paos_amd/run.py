@@ -1262,7 +1262,8 @@ def _plan_focus(states, chains, focus_planes, last_key):
     return beams, planes
 
 
-# The products of the last surface -- detector images, transfer functions, zoomed windows (zoom.PsfWindow) -- share one
+# The products of the last surface -- a blur of the kept PSFs (blur.PsfBlur), detector images, transfer functions, zoomed
+# windows (zoom.PsfWindow) -- share one
 # method: ``attach(dev, recs, dxs, dys)`` gives ``recs[i]`` item i's entries from what ``dev`` holds right now (the kept
 # PSFs: ``reads_psf``, or the field) on the samplings ``dxs`` / ``dys``.  ``_attach_products`` walks them.
 class _DetectorRequest:
@@ -1292,15 +1293,18 @@ class _OtfRequest:
 
     reads_psf = True
 
-    def __init__(self, arrays, cuts):
-        self.arrays, self.cuts = tuple(arrays), bool(cuts)
+    def __init__(self, arrays, cuts, compute=True):
+        # compute=False: a blur attached before this request has transformed the PSFs already (blur.PsfBlur.attach), and
+        # the spectra ``dev`` holds are the system transfer functions
+        self.arrays, self.cuts, self.compute = tuple(arrays), bool(cuts), bool(compute)
 
     def __bool__(self):
         return bool(self.arrays) or self.cuts
 
     def attach(self, dev, recs, dxs, dys):
         """``recs[i]`` gets item i's entries, from the PSFs ``dev`` keeps right now.  Synchronises."""
-        dev.otf_compute()
+        if self.compute:
+            dev.otf_compute()
         for i, rec in enumerate(recs):
             for name in self.arrays:
                 rec[name] = dev.otf_fetch(i, name)
@@ -1383,7 +1387,7 @@ def _focus_stack(dev, focus, outputs, metrics_radii_px, power, products):
 def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, precision="fp64",
               device=0, outputs=("psf",), dev=None, sync=True, stats=None, metrics_radii_px=None,
               keep_psf=False, power=True, detector=None, detector_weights=None, detector_origin=None, focus_planes=None,
-              mtf_cuts=False, psf_zoom=None):
+              mtf_cuts=False, psf_zoom=None, psf_blur=None):
     """Propagate ``B = len(opt_chains)`` wavefronts together on one GPU.
 
     ``wavelengths[i]`` / ``opt_chains[i]`` describe wavefront ``i`` (chains must
@@ -1462,6 +1466,20 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     gets the same keys.  It needs the field of the last surface, so the run takes the ordinary walk, and it synchronises:
     ``sync=False``, a last surface that is not saved, a size, oversampling or centres that ``paos_zoom_compute`` would
     refuse are a ``ValueError`` -- before anything is launched.
+
+    ``psf_blur`` (a :class:`paos_amd.PsfBlur`) blurs every item's kept PSF at the LAST surface, which must be saved, on
+    the GPU (README.md, "Blurred PSFs"; it implies ``keep_psf``): ``P' = ifft2(T fft2(P))`` with the separable transfer
+    function of a Gaussian (jitter, charge diffusion) and, optionally, the pixel aperture on the item's sampling at the
+    last surface -- ``paos_otf_compute``, then ``paos_blur_apply`` in place on the PSF buffer.  It is attached first, so
+    everything made from the kept PSFs is made from ``P'``: ``'detector'`` images and the accumulator of
+    ``detector_weights``, and ``'mtf'`` / ``'otf'`` / ``mtf_cuts``, which are then the SYSTEM transfer functions (the
+    PSFs are transformed once for both).  The last surface's record gets ``'blur_sigma'`` = ``(sigma_x_i, sigma_y_i)``
+    and, with ``array=True``, ``'psf_blur'``, ``P'`` as a (N, N) float64 array read from the PSF buffer.  What is read
+    from the FIELD stays optical: ``'psf'`` (and the other arrays of ``outputs``), ``'metrics'``, ``'power'`` and
+    ``psf_zoom``.  With ``focus_planes`` every plane is treated alike; ``outputs=()`` stays on the lean walk.
+    ``ValueError``, before anything is launched: an argument that is not a ``PsfBlur``; a last surface that is not saved;
+    ``sync=False``; per-item values of another length than the batch; ``pixel`` together with ``detector`` (the rebinning
+    already integrates over the pixel).
     """
     nb = len(opt_chains)
     if len(wavelengths) != nb:
@@ -1473,8 +1491,19 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
         raise ValueError(f"unknown outputs {sorted(unknown)}")
     last_key = list(opt_chains[0].keys())[-1] if len(opt_chains[0]) else None
     # the transfer functions of the last surface's PSFs: not arrays of the field (they are not downloaded per saved surface)
-    otf = _OtfRequest([name for name in ("mtf", "otf") if name in outputs], mtf_cuts)
+    otf = _OtfRequest([name for name in ("mtf", "otf") if name in outputs], mtf_cuts, compute=psf_blur is None)
     outputs = tuple(name for name in outputs if name not in ("mtf", "otf"))
+    if psf_blur is not None:
+        from .blur import PsfBlur
+
+        if not isinstance(psf_blur, PsfBlur):
+            raise ValueError(f"psf_blur must be a paos_amd.PsfBlur, got {psf_blur!r}")
+        if not sync:
+            raise ValueError("psf_blur cannot be combined with sync=False")
+        _need_saved_last(opt_chains, last_key, "psf_blur needs")
+        psf_blur.check(nb)
+        if psf_blur.pixel is not None and detector is not None:
+            raise ValueError("psf_blur with a pixel aperture and a detector: the rebinning already integrates over the pixel")
     if otf:
         if not sync:
             raise ValueError("'mtf' / 'otf' outputs and mtf_cuts synchronise: they cannot be combined with sync=False")
@@ -1512,7 +1541,8 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
             if not np.all(np.isfinite(origins)):
                 raise ValueError("detector_origin must be finite")
     det = None if detector is None else _DetectorRequest(detector, detector_weights, origins, isinstance(detector_origin, str))
-    products = [p for p in (det, otf, psf_zoom) if p]  # (in the order in which they are attached)
+    # (in the order in which they are attached: a blur rewrites the kept PSFs, so it goes before everything that reads them)
+    products = [p for p in (psf_blur, det, otf, psf_zoom) if p]
     keep_psf = keep_psf or any(p.reads_psf for p in products)
     fields = _fields_of(field, nb)
     states = [_Item(pupil_diameter, wl, gridsize, zoom, f) for wl, f in zip(wavelengths, fields)]

@@ -8,7 +8,8 @@ a few dwords spilled once per wave in a four- to six-transform kernel) and, sinc
 shapes like the others and fall under the same rules.  Exit status 1 if any other shape spills: a
 change to the kernel header that costs the ordinary shapes their allocation shows here, not only in the bench (round 4:
 a generic lambda inside a discarded `if constexpr` branch did exactly that to every shape).  The row and column kernels
-of the transfer functions (otf_pass.h) are listed too; any scratch in them is unexpected."""
+of the transfer functions (otf_pass.h) and of the blurred PSFs (blur_pass.h) are listed too; any scratch in them is
+unexpected."""
 import re
 import sys
 
@@ -37,19 +38,20 @@ def expected(r):
 
 bad = [r for r in rows if r[2] > 0 and not expected(r)]
 
-# The packed real-input passes of the transfer functions (otf_pass.h) share the register budget of the generic pass
-# shapes they borrow their tiles from and are allowed no scratch at all.
+# The packed real-input passes of the transfer functions (otf_pass.h) and the packed real-output passes of the blurred PSFs
+# (blur_pass.h) share the register budget of the generic pass shapes they borrow their tiles from and are allowed no
+# scratch at all.
 otf = []
 for b in txt.split("Function Name: ")[1:]:
     name = b.split("\n")[0].strip()
-    m = re.search(r"otf_(row|col)_kernelI([df])Li(\d+)ELi\d+ELi(\d+)ELi(\d+)ELi(\d+)E", name)
+    m = re.search(r"(?:otf|blur)_(row|col)_kernelI([df])Li(\d+)ELi\d+ELi(\d+)ELi(\d+)ELi(\d+)E", name)
     v, c = re.search(r"VGPRs: (\d+)", b), re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b)
     if m and v and c:
         otf.append((m.groups(), int(v.group(1)), int(c.group(1))))
 if not otf:
     sys.exit("no otf_row_kernel / otf_col_kernel resource remarks in the log")
 otf_bad = [r for r in otf if r[2] > 0]
-print(f"{len(otf)} transfer-function pass shapes, max VGPRs {max(r[1] for r in otf)}, max scratch {max(r[2] for r in otf)} B/lane")
+print(f"{len(otf)} transfer-function and blur pass shapes, max VGPRs {max(r[1] for r in otf)}, max scratch {max(r[2] for r in otf)} B/lane")
 for r in sorted(otf):
     if r[2] > 0:
         print("  scratch:", dict(zip(("axis", "type", "N", "lines", "tiles", "BR"), r[0])), r[1:], "  <-- unexpected")
