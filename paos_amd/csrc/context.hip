@@ -304,13 +304,10 @@ int paos_ctx_create(int device, int n, int batch, int precision, paos_ctx** out)
   for (int k = 0; k < kArenaSlabs; ++k)
     if ((e = hipEventCreateWithFlags(&c->arena.fence[k], hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate(arena fence)");
   c->arena.used[0] = true;
-  if (precision == PAOS_F64) {
-    auto tw = twiddles<double>(n);
-    e = hipMemcpy(c->tw, tw.data(), (size_t)n * eb, hipMemcpyHostToDevice);
-  } else {
-    auto tw = twiddles<float>(n);
-    e = hipMemcpy(c->tw, tw.data(), (size_t)n * eb, hipMemcpyHostToDevice);
-  }
+  e = dispatch_layout(c, [&](auto t, auto) {
+    auto tw = twiddles<decltype(t)>(n);
+    return hipMemcpy(c->tw, tw.data(), (size_t)n * eb, hipMemcpyHostToDevice);
+  });
   if (e != hipSuccess) return bail(e, "hipMemcpy(tw)");
   *out = c;
   return PAOS_OK;

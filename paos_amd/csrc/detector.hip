@@ -93,12 +93,10 @@ int detector_run(paos_ctx* c, const double* per_item, int stride, double* host_o
     if (max_block_rows > 0) {
       const size_t threads = (size_t)max_block_rows * nx;
       const dim3 grid((unsigned)std::min<size_t>((threads + kThreads - 1) / kThreads, 16384), cnt);
-      if (c->precision == PAOS_F64)
-        hipLaunchKernelGGL((detector_rows_kernel<BR, Lay<double>::BC>), grid, block, 0, c->stream, (const double*)c->psf,
+      dispatch_layout(c, [&](auto t, auto br) {
+        hipLaunchKernelGGL((detector_rows_kernel<decltype(br)::value, Lay<decltype(t)>::BC>), grid, block, 0, c->stream, (const double*)c->psf,
                            c->item_stride, c->pitch, n, ditems, g, c->det_rows);
-      else
-        F32_BR_SWITCH(c, hipLaunchKernelGGL((detector_rows_kernel<FBR, Lay<float>::BC>), grid, block, 0, c->stream,
-                                            (const double*)c->psf, c->item_stride, c->pitch, n, ditems, g, c->det_rows));
+      });
       HIPCHK(c, hipGetLastError());
     }
     const dim3 grid2((unsigned)std::min<size_t>((npix + kThreads - 1) / kThreads, 16384));

@@ -14,39 +14,55 @@
 
 namespace {
 
-// ---- through-focus stacks: the out-of-place passes of focus_pass.h ----------------------
-// the generic pass kernel's geometry (FftCfg: one tile shape per grid size and type, 64 .. 4096)
-template <typename T, int N, int AXIS>
-int focus_launch(paos_ctx* c, const FocusArgs& a) {
-  using C = FftCfg<T, N>;
-  constexpr int LINES = AXIS == 0 ? C::ROW_LINES : C::COL_LINES;
-  constexpr int TILES = AXIS == 0 ? C::ROW_TILES : C::COL_TILES;
-  constexpr bool SPLIT = AXIS == 0 ? C::ROW_SPLIT : C::COL_SPLIT;
-  const dim3 grid(N / LINES / TILES, c->batch), block(TILES * LINES * N / C::E);
-  const size_t lds = (size_t)TILES * LINES * line_lds_bytes<T, N, SPLIT>();
-  // for the launch timer: a full pass -- every line of every item is loaded, transformed once and stored
-  c->prof_next_tag = 0;
-  c->prof_next_bytes = (double)c->batch * N * N * 2.0 * (double)elem_bytes(c);
-  c->prof_next_lines = (double)c->batch * N;
-  return TIMED_LAUNCH(c, focus_pass_kernel<T, N, C::E, LINES, TILES, AXIS, C::BR, C::BC, SPLIT, C::MINW>, grid, block, lds,
-                      generic_lds_opt_in(lds), AXIS == 0 ? PAOS_KERNEL_PASS_ROWS : PAOS_KERNEL_PASS_COLS, 0, a);
-}
-
-template <typename T>
-int focus_pass_t(paos_ctx* c, int axis, const FocusArgs& a) {
-  return dispatch_n(c, [&](auto n) {
-    constexpr int N = decltype(n)::value;
-    return axis == 0 ? focus_launch<T, N, 0>(c, a) : focus_launch<T, N, 1>(c, a);
+// ---- one launcher for the passes of all three products ---------------------------------------------------------------
+// The generic pass kernel's tile along AXIS (FftCfg: one tile shape per grid size and type, 64 .. 4096)
+template <typename T_, int N_, int AXIS_>
+struct Tile {
+  using T = T_;
+  using C = FftCfg<T, N_>;
+  static constexpr int N = N_, AXIS = AXIS_;
+  static constexpr int LINES = AXIS == 0 ? C::ROW_LINES : C::COL_LINES;
+  static constexpr int TILES = AXIS == 0 ? C::ROW_TILES : C::COL_TILES;
+  static constexpr bool SPLIT = AXIS == 0 ? C::ROW_SPLIT : C::COL_SPLIT;
+  static constexpr int PER_WG = LINES * TILES;  // lines per workgroup
+};
+// One pass of a product on those tiles.  What differs between the products is passed in: kernel(Tile<..>{}), the kernel's
+// build for the tile; `lines`, how many lines along `axis` the launch has to cover (whole workgroups: the grid along x);
+// `bytes`, what the launch moves, for the launch timer (its lines: those of whole workgroups)
+template <typename Kernel, typename Args>
+int tile_pass(paos_ctx* c, int axis, int lines, double bytes, Kernel kernel, const Args& a) {
+  return dispatch_layout(c, [&](auto t, auto) {
+    return dispatch_n(c, [&](auto n) {
+      return dispatch_either<0, 1>(axis == 0, [&](auto ax) {
+        using L = Tile<decltype(t), decltype(n)::value, decltype(ax)::value>;
+        const int wgs = (lines + L::PER_WG - 1) / L::PER_WG;
+        const dim3 grid(wgs, c->batch), block(L::PER_WG * L::N / L::C::E);
+        const size_t lds = (size_t)L::PER_WG * line_lds_bytes<typename L::T, L::N, L::SPLIT>();
+        c->prof_next_tag = 0;
+        c->prof_next_bytes = bytes;
+        c->prof_next_lines = (double)c->batch * wgs * L::PER_WG;
+        return TIMED_LAUNCH(c, kernel(L{}), grid, block, lds, generic_lds_opt_in(lds),
+                            L::AXIS == 0 ? PAOS_KERNEL_PASS_ROWS : PAOS_KERNEL_PASS_COLS, 0, a);
+      });
+    });
   });
 }
+// the packed real passes (OTF, blur): rows: the N/2 packed lines, columns: 0 .. N/2 (rounded up to whole workgroups)
+int packed_lines(const paos_ctx* c, int axis) { return axis == 0 ? c->n / 2 : c->n / 2 + 1; }
 
+// ---- through-focus stacks: the out-of-place passes of focus_pass.h ----------------------
 int focus_pass(paos_ctx* c, int axis, int mode, const void* src, void* dst, const double* dparams) {
   FocusArgs a{};
   a.src = src; a.dst = dst; a.tw = c->tw; a.params = dparams;
   a.scale = 1.0 / c->n;
   a.mode = mode;
   a.pitch = c->pitch; a.item_stride = c->item_stride;
-  return c->precision == PAOS_F64 ? focus_pass_t<double>(c, axis, a) : focus_pass_t<float>(c, axis, a);
+  // a full pass -- every line of every item is loaded, transformed once and stored
+  return tile_pass(c, axis, c->n, (double)c->batch * c->n * c->n * 2.0 * (double)elem_bytes(c), [](auto tile) {
+    using L = decltype(tile);
+    using C = typename L::C;
+    return focus_pass_kernel<typename L::T, L::N, C::E, L::LINES, L::TILES, L::AXIS, C::BR, C::BC, L::SPLIT, C::MINW>;
+  }, a);
 }
 
 }  // namespace
@@ -103,44 +119,19 @@ namespace {
 constexpr int kThreads = 256;  // per workgroup of the fetch and cut sweeps
 
 // ---- transfer functions: the packed real-input passes of otf_pass.h -----------------------
-// the generic pass kernel's geometry again; rows: the N/2 packed lines, columns: 0 .. N/2 rounded up to whole workgroups
-template <typename T, int N, int AXIS>
-int otf_launch(paos_ctx* c, const OtfArgs& a) {
-  using C = FftCfg<T, N>;
-  constexpr int LINES = AXIS == 0 ? C::ROW_LINES : C::COL_LINES;
-  constexpr int TILES = AXIS == 0 ? C::ROW_TILES : C::COL_TILES;
-  constexpr bool SPLIT = AXIS == 0 ? C::ROW_SPLIT : C::COL_SPLIT;
-  constexpr int PER_WG = LINES * TILES;
-  constexpr int WGS = AXIS == 0 ? N / 2 / PER_WG : (N / 2 + 1 + PER_WG - 1) / PER_WG;
-  const dim3 grid(WGS, c->batch), block(TILES * LINES * N / C::E);
-  const size_t lds = (size_t)TILES * LINES * line_lds_bytes<T, N, SPLIT>();
-  auto kern = [] {
-    if constexpr (AXIS == 0) return otf_row_kernel<T, N, C::E, LINES, TILES, C::BR, C::BC, SPLIT, C::MINW>;
-    else return otf_col_kernel<T, N, C::E, LINES, TILES, C::BR, C::BC, SPLIT, C::MINW>;
-  }();
-  // for the launch timer: the lines the launch transforms (the column launch: those of its last workgroup that lie beyond
-  // column N/2 included) and the bytes it moves (rows: N/2 x 2 PSF rows in, N/2 lines out; columns: N/2 rows of the
-  // column and of its mirror in, N rows out)
-  const double eb = (double)elem_bytes(c);
-  c->prof_next_tag = 0;
-  c->prof_next_lines = (double)c->batch * WGS * PER_WG;
-  c->prof_next_bytes = AXIS == 0 ? (double)c->batch * N * (N * 8.0 + N / 2 * eb) : (double)c->batch * (N / 2 + 1) * 2.0 * N * eb;
-  return TIMED_LAUNCH(c, kern, grid, block, lds, generic_lds_opt_in(lds), AXIS == 0 ? PAOS_KERNEL_PASS_ROWS : PAOS_KERNEL_PASS_COLS, 0, a);
-}
-
-template <typename T>
-int otf_pass_t(paos_ctx* c, int axis, const OtfArgs& a) {
-  return dispatch_n(c, [&](auto n) {
-    constexpr int N = decltype(n)::value;
-    return axis == 0 ? otf_launch<T, N, 0>(c, a) : otf_launch<T, N, 1>(c, a);
-  });
-}
-
 int otf_pass(paos_ctx* c, int axis) {
   OtfArgs a{};
   a.psf = c->psf; a.spec = c->otf_spec; a.tw = c->tw;
   a.pitch = c->pitch; a.item_stride = c->item_stride;
-  return c->precision == PAOS_F64 ? otf_pass_t<double>(c, axis, a) : otf_pass_t<float>(c, axis, a);
+  // the bytes it moves: rows: N/2 x 2 PSF rows in, N/2 lines out; columns: N/2 rows of the column and of its mirror in, N rows out
+  const double n = c->n, eb = (double)elem_bytes(c);
+  const double bytes = axis == 0 ? c->batch * n * (n * 8.0 + c->n / 2 * eb) : c->batch * (double)(c->n / 2 + 1) * 2.0 * n * eb;
+  return tile_pass(c, axis, packed_lines(c, axis), bytes, [](auto tile) {
+    using L = decltype(tile);
+    using C = typename L::C;
+    if constexpr (L::AXIS == 0) return otf_row_kernel<typename L::T, L::N, C::E, L::LINES, L::TILES, C::BR, C::BC, L::SPLIT, C::MINW>;
+    else return otf_col_kernel<typename L::T, L::N, C::E, L::LINES, L::TILES, C::BR, C::BC, L::SPLIT, C::MINW>;
+  }, a);
 }
 
 // fetch and cuts share their preconditions
@@ -152,36 +143,17 @@ int otf_ready(paos_ctx* c, const char* who) {
 }
 
 // ---- blurred PSFs: the packed real-output passes of blur_pass.h ---------------------------
-// otf_launch's geometry; columns first (spectrum -> PSF buffer), then the N/2 packed lines in place on the PSF buffer
-template <typename T, int N, int AXIS>
-int blur_launch(paos_ctx* c, const BlurArgs& a) {
-  using C = FftCfg<T, N>;
-  constexpr int LINES = AXIS == 0 ? C::ROW_LINES : C::COL_LINES;
-  constexpr int TILES = AXIS == 0 ? C::ROW_TILES : C::COL_TILES;
-  constexpr bool SPLIT = AXIS == 0 ? C::ROW_SPLIT : C::COL_SPLIT;
-  constexpr int PER_WG = LINES * TILES;
-  constexpr int WGS = AXIS == 0 ? N / 2 / PER_WG : (N / 2 + 1 + PER_WG - 1) / PER_WG;
-  const dim3 grid(WGS, c->batch), block(TILES * LINES * N / C::E);
-  const size_t lds = (size_t)TILES * LINES * line_lds_bytes<T, N, SPLIT>();
-  auto kern = [] {
-    if constexpr (AXIS == 0) return blur_row_kernel<T, N, C::E, LINES, TILES, C::BR, C::BC, SPLIT, C::MINW>;
-    else return blur_col_kernel<T, N, C::E, LINES, TILES, C::BR, C::BC, SPLIT, C::MINW>;
-  }();
-  // for the launch timer: the lines the launch transforms (columns: those of the last workgroup beyond N/2 included) and
-  // the bytes it moves (columns: N/2 + 1 columns of the spectrum in and out, N columns of doubles out; rows: the PSF in and out)
-  const double eb = (double)elem_bytes(c);
-  c->prof_next_tag = 0;
-  c->prof_next_lines = (double)c->batch * WGS * PER_WG;
-  c->prof_next_bytes = AXIS == 0 ? (double)c->batch * N * N * 16.0 : (double)c->batch * N * ((N / 2 + 1) * 2.0 * eb + N * 8.0);
-  return TIMED_LAUNCH(c, kern, grid, block, lds, generic_lds_opt_in(lds), AXIS == 0 ? PAOS_KERNEL_PASS_ROWS : PAOS_KERNEL_PASS_COLS, 0, a);
-}
-
-template <typename T>
-int blur_pass_t(paos_ctx* c, int axis, const BlurArgs& a) {
-  return dispatch_n(c, [&](auto n) {
-    constexpr int N = decltype(n)::value;
-    return axis == 0 ? blur_launch<T, N, 0>(c, a) : blur_launch<T, N, 1>(c, a);
-  });
+// columns first (spectrum -> PSF buffer), then the N/2 packed lines in place on the PSF buffer
+int blur_pass(paos_ctx* c, int axis, const BlurArgs& a) {
+  // the bytes it moves: columns: N/2 + 1 columns of the spectrum in and out, N columns of doubles out; rows: the PSF in and out
+  const double n = c->n, eb = (double)elem_bytes(c);
+  const double bytes = axis == 0 ? c->batch * n * n * 16.0 : c->batch * n * ((c->n / 2 + 1) * 2.0 * eb + n * 8.0);
+  return tile_pass(c, axis, packed_lines(c, axis), bytes, [](auto tile) {
+    using L = decltype(tile);
+    using C = typename L::C;
+    if constexpr (L::AXIS == 0) return blur_row_kernel<typename L::T, L::N, C::E, L::LINES, L::TILES, C::BR, C::BC, L::SPLIT, C::MINW>;
+    else return blur_col_kernel<typename L::T, L::N, C::E, L::LINES, L::TILES, C::BR, C::BC, L::SPLIT, C::MINW>;
+  }, a);
 }
 
 // why paos_blur_table refuses (n, d, sigma, pixel), or null
@@ -253,7 +225,7 @@ int paos_blur_apply(paos_ctx* c, const double* per_item) {
   // passes) is void.  The spectrum is rewritten along with it, so the transfer functions stay valid: those of P'.
   c->psf_zero_axis = -1;
   for (int axis = 1; axis >= 0; --axis) {
-    rc = c->precision == PAOS_F64 ? blur_pass_t<double>(c, axis, a) : blur_pass_t<float>(c, axis, a);
+    rc = blur_pass(c, axis, a);
     if (rc) {
       c->otf_valid = false;  // (a launch failed half way: neither buffer is to be trusted)
       return rc;
@@ -286,12 +258,11 @@ int paos_otf_fetch(paos_ctx* c, int item, int what, void* host_out) {
   const int cplx = what == PAOS_OTF_COMPLEX;
   const size_t n2 = (size_t)c->n * c->n;
   const dim3 grid((unsigned)std::min<size_t>((n2 + kThreads - 1) / kThreads, 2048)), block(kThreads);
-  if (c->precision == PAOS_F64)
-    hipLaunchKernelGGL((otf_fetch_kernel<double, BR, Lay<double>::BC>), grid, block, 0, c->stream,
-                       (const cx<double>*)c->otf_spec + (size_t)item * c->item_stride, c->staging, c->n, c->pitch, cplx);
-  else
-    F32_BR_SWITCH(c, hipLaunchKernelGGL((otf_fetch_kernel<float, FBR, Lay<float>::BC>), grid, block, 0, c->stream,
-                       (const cx<float>*)c->otf_spec + (size_t)item * c->item_stride, c->staging, c->n, c->pitch, cplx));
+  dispatch_layout(c, [&](auto t, auto br) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((otf_fetch_kernel<T, decltype(br)::value, Lay<T>::BC>), grid, block, 0, c->stream,
+                       (const cx<T>*)c->otf_spec + (size_t)item * c->item_stride, c->staging, c->n, c->pitch, cplx);
+  });
   HIPCHK(c, hipGetLastError());
   return copy_to_host(c, host_out, c->staging, n2 * (cplx ? 16 : 8));
 }
@@ -305,12 +276,11 @@ int paos_otf_cuts(paos_ctx* c, double* host_out) {
   const size_t bytes = (size_t)c->batch * 2 * len * sizeof(double);
   if (!c->otf_cuts) HIPCHK(c, hipMalloc(&c->otf_cuts, bytes));
   const dim3 grid((2 * len + kThreads - 1) / kThreads, c->batch), block(kThreads);
-  if (c->precision == PAOS_F64)
-    hipLaunchKernelGGL((otf_cuts_kernel<double, BR, Lay<double>::BC>), grid, block, 0, c->stream,
-                       (const cx<double>*)c->otf_spec, c->otf_cuts, c->n, c->pitch, c->item_stride);
-  else
-    F32_BR_SWITCH(c, hipLaunchKernelGGL((otf_cuts_kernel<float, FBR, Lay<float>::BC>), grid, block, 0, c->stream,
-                       (const cx<float>*)c->otf_spec, c->otf_cuts, c->n, c->pitch, c->item_stride));
+  dispatch_layout(c, [&](auto t, auto br) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((otf_cuts_kernel<T, decltype(br)::value, Lay<T>::BC>), grid, block, 0, c->stream, (const cx<T>*)c->otf_spec,
+                       c->otf_cuts, c->n, c->pitch, c->item_stride);
+  });
   HIPCHK(c, hipGetLastError());
   return copy_to_host(c, host_out, c->otf_cuts, bytes);
 }

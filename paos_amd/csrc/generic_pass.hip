@@ -30,5 +30,5 @@ int pass_t(paos_ctx* c, int axis, const PassArgs& a, int feat) {
 }  // namespace
 
 int generic_pass(paos_ctx* c, int axis, const PassArgs& a, int feat) {
-  return c->precision == PAOS_F64 ? pass_t<double>(c, axis, a, feat) : pass_t<float>(c, axis, a, feat);
+  return dispatch_layout(c, [&](auto t, auto) { return pass_t<decltype(t)>(c, axis, a, feat); });
 }

@@ -3,8 +3,11 @@
 // The host side of the library is split by what it launches: context.hip (contexts, the parameter arena, errors,
 // the launch timer), pass_plan.hip and passes.hip (pass programs), generic_pass.hip and frugal_<family>.hip (the pass
 // kernels), paos_hip.hip (the pointwise entry points: every kernel of pointwise.h) and the products: focus_otf.hip, zoom.hip,
-// detector.hip.  Here: the build-time layout, the context, the error and launch helpers, and the declarations of the
-// functions that cross unit boundaries.  Whatever is not declared here lives in an anonymous namespace of its unit.
+// detector.hip.  Here: the build-time layout, the context, the error and launch helpers, the dispatchers that turn what a
+// context is at run time into template arguments (dispatch_n: the grid size; dispatch_layout / dispatch_block_rows: element
+// type and block height -- every launch is written once, inside a generic lambda), and the declarations of the functions
+// that cross unit boundaries.  Whatever is not declared here lives in an anonymous namespace of its unit.  Which items of a
+// batch share what is plain C++ in item_groups.h.
 #pragma once
 #include "../../include/paos_hip.h"
 
@@ -40,12 +43,6 @@ inline constexpr int BR = PAOS_BR;  // complex128 and the base case of complex64
 #endif
 template <typename T, int N>
 constexpr int block_rows() { return (sizeof(T) == 4 && N >= 2048) ? PAOS_F32_BR : PAOS_BR; }
-// one float launch for either block height: FBR is the compile-time block height inside the statement
-#define F32_BR_SWITCH(c, ...)                                                            \
-  do {                                                                                   \
-    if ((c)->br == PAOS_F32_BR) { constexpr int FBR = PAOS_F32_BR; __VA_ARGS__; }        \
-    else { constexpr int FBR = PAOS_BR; __VA_ARGS__; }                                   \
-  } while (0)
 inline constexpr int kNormSlots = PAOS_NORM_SLOTS;  // outstanding paos_norm2_enqueue results
 template <typename T>
 struct Lay {
@@ -314,6 +311,29 @@ int dispatch_n(paos_ctx* c, F&& f) {
   return fail(c, PAOS_EUNSUPPORTED, "grid size must be a power of two in 64..4096");
 }
 
+// f(std::integral_constant<int, BRV>) for the context's block height BRV (PAOS_F32_BR or PAOS_BR): the launches whose
+// element type does not matter (pupil weights, Gram sums)
+template <typename F>
+auto dispatch_block_rows(const paos_ctx* c, F&& f) {
+  if (c->br == PAOS_F32_BR) return f(std::integral_constant<int, PAOS_F32_BR>{});
+  return f(std::integral_constant<int, PAOS_BR>{});
+}
+// f(T{}, std::integral_constant<int, BRV>) for the context's element type and block height: the one place that knows the
+// layouts -- (double, PAOS_BR), (float, PAOS_F32_BR) and (float, PAOS_BR), no other pair is ever instantiated.  Returns what
+// f returns; a HIPCHK inside f returns from f, so a caller that uses one hands the value on.
+template <typename F>
+auto dispatch_layout(const paos_ctx* c, F&& f) {
+  if (c->precision == PAOS_F64) return f(double{}, std::integral_constant<int, PAOS_BR>{});
+  return dispatch_block_rows(c, [&](auto br) { return f(float{}, br); });
+}
+// f(std::integral_constant<int, A>) if `first`, else f(std::integral_constant<int, B>): a two-way template argument
+// (aperture shape 0 / 1, the unrolled Zernike build 8 / 0)
+template <int A, int B, typename F>
+auto dispatch_either(bool first, F&& f) {
+  if (first) return f(std::integral_constant<int, A>{});
+  return f(std::integral_constant<int, B>{});
+}
+
 // ---- pass_plan.hip: a pass of a program lowered for the frugal kernels, and the pruning of dead lines across a program ----
 // One pass of a program, lowered for the frugal kernels before anything is launched, so that the
 // planner can look ahead.
@@ -374,7 +394,10 @@ int settle_scale(paos_ctx* c, bool field_is_overwritten = false);
 int dyn_scale_reset(paos_ctx* c);
 int zero_outside_rows(paos_ctx* c, const double* live_rows);
 int zero_outside_box(paos_ctx* c, const double* live_rows, const double* live_cols);
-int psf_power_ticket(paos_ctx* c, const double* partial, int nparts, int* ticket, const double* source = nullptr);
+// the ring of power tickets: refuse while its next slot is still out (before anything is launched) / partial sums -> c->norm2
+// (item i: the sums of item source[i], if given) -> the pinned slot of a new ticket
+int power_ring_full(paos_ctx* c);
+int take_power_ticket(paos_ctx* c, const double* partial, int nparts, const double* source, int* ticket);
 int psf_keep_power_impl(paos_ctx* c, int* ticket);
 // aperture line records (pointwise.h: MaskJob): render the lines [line0, line_end) along `axis` of the aperture whose two
 // parameter block sets start at `params` into record set `set`; at most kMaskRenders of them, in one launch per shape

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "item_groups.h"
 #include "pointwise.h"
 
 namespace {
@@ -53,10 +54,10 @@ int settle_scale(paos_ctx* c, bool field_is_overwritten) {
   ++c->deferred_settled;
   if (!field_is_overwritten) {
     const dim3 grid(pw_blocks(c), c->batch), block(kPwThreads);
-    if (c->precision == PAOS_F64)
-      hipLaunchKernelGGL(scale_by_kernel<double>, grid, block, 0, c->stream, (cx<double>*)c->field, c->dyn_scale, c->item_stride);
-    else
-      hipLaunchKernelGGL(scale_by_kernel<float>, grid, block, 0, c->stream, (cx<float>*)c->field, c->dyn_scale, c->item_stride);
+    dispatch_layout(c, [&](auto t, auto) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(scale_by_kernel<T>, grid, block, 0, c->stream, (cx<T>*)c->field, c->dyn_scale, c->item_stride);
+    });
   }
   return dyn_scale_reset(c);
 }
@@ -98,13 +99,12 @@ int render_mask_weights(paos_ctx* c, const double* ap) {
   if (!c->mask) HIPCHK(c, hipMalloc(&c->mask, (size_t)c->batch * c->item_stride * sizeof(double)));
   const dim3 grid(pw_blocks(c), c->batch), block(kPwThreads);
   const double* ap2 = ap + (size_t)c->batch * FP_STRIDE;  // the next block set
-  if (c->precision == PAOS_F64) {
-    hipLaunchKernelGGL((aperture_kernel<double, BR, Lay<double>::BC, 0>), grid, block, 0, c->stream, (cx<double>*)nullptr, ap, ap2, FP_STRIDE, c->n, c->pitch, c->item_stride, c->mask, 1);
-    hipLaunchKernelGGL((aperture_kernel<double, BR, Lay<double>::BC, 1>), grid, block, 0, c->stream, (cx<double>*)nullptr, ap, ap2, FP_STRIDE, c->n, c->pitch, c->item_stride, c->mask, 1);
-  } else {
-    F32_BR_SWITCH(c, hipLaunchKernelGGL((aperture_kernel<float, FBR, Lay<float>::BC, 0>), grid, block, 0, c->stream, (cx<float>*)nullptr, ap, ap2, FP_STRIDE, c->n, c->pitch, c->item_stride, c->mask, 1));
-    F32_BR_SWITCH(c, hipLaunchKernelGGL((aperture_kernel<float, FBR, Lay<float>::BC, 1>), grid, block, 0, c->stream, (cx<float>*)nullptr, ap, ap2, FP_STRIDE, c->n, c->pitch, c->item_stride, c->mask, 1));
-  }
+  dispatch_layout(c, [&](auto t, auto br) {  // both shapes: each takes the items that have it
+    using T = decltype(t);
+    constexpr int BRV = decltype(br)::value;
+    hipLaunchKernelGGL((aperture_kernel<T, BRV, Lay<T>::BC, 0>), grid, block, 0, c->stream, (cx<T>*)nullptr, ap, ap2, FP_STRIDE, c->n, c->pitch, c->item_stride, c->mask, 1);
+    hipLaunchKernelGGL((aperture_kernel<T, BRV, Lay<T>::BC, 1>), grid, block, 0, c->stream, (cx<T>*)nullptr, ap, ap2, FP_STRIDE, c->n, c->pitch, c->item_stride, c->mask, 1);
+  });
   HIPCHK(c, hipGetLastError());
   return PAOS_OK;
 }
@@ -112,10 +112,9 @@ int render_mask_weights(paos_ctx* c, const double* ap) {
 // a transform-free pass: its operators, pixel by pixel
 int pointwise_pass(paos_ctx* c, const PassArgs& a) {
   const dim3 grid(pw_blocks(c), c->batch), block(kPwThreads);
-  if (c->precision == PAOS_F64)
-    hipLaunchKernelGGL((pointwise_kernel<double, BR, Lay<double>::BC>), grid, block, 0, c->stream, a, c->n);
-  else
-    F32_BR_SWITCH(c, hipLaunchKernelGGL((pointwise_kernel<float, FBR, Lay<float>::BC>), grid, block, 0, c->stream, a, c->n));
+  dispatch_layout(c, [&](auto t, auto br) {
+    hipLaunchKernelGGL((pointwise_kernel<decltype(t), decltype(br)::value, Lay<decltype(t)>::BC>), grid, block, 0, c->stream, a, c->n);
+  });
   HIPCHK(c, hipGetLastError());
   return PAOS_OK;
 }
@@ -134,7 +133,47 @@ bool share_wfe_maps() {
   return on;
 }
 
+// stage 1 of a power reduction: per-workgroup sums of |u|^2 of the field (inside the windows, of the enabled items) into c->partial
+void norm2_partial_launch(paos_ctx* c, const double* enable, const double* rows = nullptr, const double* cols = nullptr) {
+  dispatch_layout(c, [&](auto t, auto br) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((norm2_partial_kernel<T, decltype(br)::value, Lay<T>::BC>), dim3(c->nparts, c->batch), dim3(kPwThreads), 0, c->stream,
+                       (const cx<T>*)c->field, c->partial, c->n, c->pitch, c->item_stride, enable, 1, rows, cols);
+  });
+}
+
+// field *= 1 / sqrt(c->norm2) for the enabled items
+void stop_scale_launch(paos_ctx* c, const double* enable) {
+  dispatch_layout(c, [&](auto t, auto) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(stop_scale_kernel<T>, dim3(pw_blocks(c), c->batch), dim3(kPwThreads), 0, c->stream, (cx<T>*)c->field, c->norm2,
+                       c->item_stride, enable, 1);
+  });
+}
+
 }  // namespace
+
+// ---- the ring of power tickets ----------------------------------------------------------------------------------------
+// refuses while the slot the next ticket would take is still out (for the entry points that must refuse before they launch)
+int power_ring_full(paos_ctx* c) {
+  if (c->norm_busy[next_norm_slot(c)])  // the oldest ticket has not been fetched
+    return fail(c, PAOS_EINVAL, "64 power reductions outstanding: fetch earlier tickets (paos_norm2_fetch) first");
+  return PAOS_OK;
+}
+
+// partial sums -> c->norm2 (item i: the sums of item source[i], if given) -> the pinned slot of a new ticket
+int take_power_ticket(paos_ctx* c, const double* partial, int nparts, const double* source, int* ticket) {
+  if (int rc = power_ring_full(c)) return rc;
+  const int slot = next_norm_slot(c);
+  hipLaunchKernelGGL(norm2_final_kernel, dim3(c->batch), dim3(kPwThreads), 0, c->stream, partial, c->norm2, nparts, (const double*)nullptr, 1, source);
+  HIPCHK(c, hipGetLastError());
+  c->norm_busy[slot] = true;
+  c->norm_slot = (slot + 1) % kNormSlots;
+  HIPCHK(c, hipMemcpyAsync(c->norm2_host + (size_t)slot * c->batch, c->norm2, (size_t)c->batch * sizeof(double),
+                           hipMemcpyDeviceToHost, c->stream));
+  *ticket = slot;
+  return PAOS_OK;
+}
 
 extern "C" {
 
@@ -144,12 +183,10 @@ int paos_fill(paos_ctx* c, double re, double im) {
   if (!c) return fail(c, PAOS_EINVAL, "null context");
   const size_t total = (size_t)c->item_stride * c->batch;
   // padding blocks are filled too; they are never read by any operator
-  if (c->precision == PAOS_F64)
-    hipLaunchKernelGGL(fill_kernel<double>, dim3(2048), dim3(kPwThreads), 0, c->stream,
-                       (cx<double>*)c->field, total, re, im);
-  else
-    hipLaunchKernelGGL(fill_kernel<float>, dim3(2048), dim3(kPwThreads), 0, c->stream,
-                       (cx<float>*)c->field, total, (float)re, (float)im);
+  dispatch_layout(c, [&](auto t, auto) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(fill_kernel<T>, dim3(2048), dim3(kPwThreads), 0, c->stream, (cx<T>*)c->field, total, (T)re, (T)im);
+  });
   HIPCHK(c, hipGetLastError());
   return PAOS_OK;
 }
@@ -162,41 +199,62 @@ struct StartZernike {
 };
 static int zernike_check(paos_ctx* c, int nmax, int kdim, const double* table, const double* params, int param_stride);
 
+// The power sums of a start with stops, into c->norm2: those of the last start if that had the same shape, constant,
+// aperture records and stop flags (paos_ctx::start_key; *found), else the launch evaluates them and start_power_keep keeps them.
+static int start_power_find(paos_ctx* c, int shape, double re, double im, const double* aperture, const std::vector<double>& flags, bool* found) {
+  static const bool memo = !env_is("PAOS_START_POWER_MEMO", '0');
+  std::vector<double> key;
+  key.reserve(3 + (size_t)c->batch * (AP_STRIDE + 1));
+  key.push_back((double)shape); key.push_back(re); key.push_back(im);
+  key.insert(key.end(), aperture, aperture + (size_t)c->batch * AP_STRIDE);
+  key.insert(key.end(), flags.begin(), flags.end());
+  *found = memo && c->start_norm2 && key.size() == c->start_key.size() &&
+           !std::memcmp(key.data(), c->start_key.data(), key.size() * sizeof(double));
+  if (*found) {
+    HIPCHK(c, hipMemcpyAsync(c->norm2, c->start_norm2, (size_t)c->batch * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  } else {
+    c->start_key.clear();  // (set again behind the launches of the start)
+    if (memo) c->start_key = std::move(key);
+  }
+  return PAOS_OK;
+}
+// keep the sums just evaluated (c->norm2 is rewritten by every reduction)
+static int start_power_keep(paos_ctx* c) {
+  if (c->start_key.empty()) return PAOS_OK;
+  if (!c->start_norm2) HIPCHK(c, hipMalloc(&c->start_norm2, (size_t)c->batch * sizeof(double)));
+  HIPCHK(c, hipMemcpyAsync(c->start_norm2, c->norm2, (size_t)c->batch * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  return PAOS_OK;
+}
+
+// check, group, push, find or evaluate the power sums, launch, keep the sums
 static int start_impl(paos_ctx* c, double re, double im, int shape, const double* aperture, const double* stop,
                       const double* write_rows, const double* write_cols = nullptr, const StartZernike* zk = nullptr) {
   if (c) (void)hipSetDevice(c->device);
   if (!c || !aperture) return fail(c, PAOS_EINVAL, "null argument");
   if (shape != PAOS_SHAPE_ELLIPSE && shape != PAOS_SHAPE_RECT) return fail(c, PAOS_EINVAL, "unknown aperture shape");
+  int rc;
   if (zk) {
-    int rcz = zernike_check(c, zk->nmax, zk->kdim, zk->table, zk->params, zk->param_stride);
-    if (rcz) return rcz;
-    if (zk->power_ticket && c->norm_busy[next_norm_slot(c)])
-      return fail(c, PAOS_EINVAL, "64 power reductions outstanding: fetch earlier tickets (paos_norm2_fetch) first");
+    if ((rc = zernike_check(c, zk->nmax, zk->kdim, zk->table, zk->params, zk->param_stride))) return rc;
+    if (zk->power_ticket && (rc = power_ring_full(c))) return rc;
   }
-  std::vector<double> flags(c->batch, 0.0);
+  const int batch = c->batch;
+  std::vector<double> flags(batch, 0.0);
   bool any_stop = false;
   if (stop)
-    for (int i = 0; i < c->batch; ++i) { flags[i] = stop[i] != 0.0 ? 1.0 : 0.0; any_stop |= flags[i] != 0.0; }
+    for (int i = 0; i < batch; ++i) { flags[i] = stop[i] != 0.0 ? 1.0 : 0.0; any_stop |= flags[i] != 0.0; }
   // items with identical aperture records (a wavelength sweep at the entrance pupil, a Monte-Carlo batch)
   // have identical power sums: stage 1 runs for the first of them, stage 2 sums ITS partials for all
-  std::vector<double> power_of(c->batch), compute(c->batch);
-  for (int i = 0; i < c->batch; ++i) {
-    int rep = i;
-    for (int j = 0; j < i; ++j)
-      if (flags[j] != 0.0 && !std::memcmp(aperture + (size_t)j * AP_STRIDE, aperture + (size_t)i * AP_STRIDE, AP_STRIDE * sizeof(double))) { rep = j; break; }
-    power_of[i] = (double)rep;
-    compute[i] = (flags[i] != 0.0 && rep == i) ? 1.0 : 0.0;
-  }
+  std::vector<double> power_of, compute;
+  power_representatives(batch, aperture, AP_STRIDE, flags.data(), power_of, compute);
   const double *dp = nullptr, *ds = nullptr, *dcompute = nullptr, *dpower_of = nullptr;
-  int rc;
-  if ((rc = arena_push(c, aperture, (size_t)c->batch * AP_STRIDE, &dp))) return rc;
+  if ((rc = arena_push(c, aperture, (size_t)batch * AP_STRIDE, &dp))) return rc;
   if ((rc = arena_push(c, flags.data(), flags.size(), &ds))) return rc;
   if ((rc = arena_push(c, compute.data(), compute.size(), &dcompute))) return rc;
   if ((rc = arena_push(c, power_of.data(), power_of.size(), &dpower_of))) return rc;
   const double* drows = nullptr;
   if (write_rows) {
     if ((rc = check_rows(c, write_rows))) return rc;
-    if ((rc = arena_push(c, write_rows, (size_t)2 * c->batch, &drows))) return rc;
+    if ((rc = arena_push(c, write_rows, (size_t)2 * batch, &drows))) return rc;
   }
   const double* dcols = nullptr;
   if (write_cols) {
@@ -205,73 +263,25 @@ static int start_impl(paos_ctx* c, double re, double im, int shape, const double
     const std::vector<double> wc = rounded_cols(c, write_cols);
     if ((rc = arena_push(c, wc.data(), wc.size(), &dcols))) return rc;
   }
-  // groups of items that start from the same field (start_write_kernel)
+  // groups of items that start from the same field (start_write_kernel): PAOS_SHARE_START=0: never
   static const bool share_start = !env_is("PAOS_SHARE_START", '0');
-  std::vector<double> goff(c->batch, 0.0), glen(c->batch, 0.0), members;
-  {
-    std::vector<int> lead(c->batch);
-    for (int i = 0; i < c->batch; ++i) {
-      lead[i] = i;
-      if (!share_start) continue;
-      for (int j = 0; j < i; ++j)
-        if (lead[j] == j && flags[j] == flags[i] &&
-            !std::memcmp(aperture + (size_t)j * AP_STRIDE, aperture + (size_t)i * AP_STRIDE, AP_STRIDE * sizeof(double)) &&
-            (!write_rows || !std::memcmp(write_rows + 2 * j, write_rows + 2 * i, 2 * sizeof(double))) &&
-            (!write_cols || !std::memcmp(write_cols + 2 * j, write_cols + 2 * i, 2 * sizeof(double)))) { lead[i] = j; break; }
-    }
-    for (int i = 0; i < c->batch; ++i) {
-      if (lead[i] != i) continue;
-      goff[i] = (double)members.size();
-      for (int j = i; j < c->batch; ++j)
-        if (lead[j] == i) members.push_back((double)j);
-      glen[i] = (double)members.size() - goff[i];
-    }
-  }
+  ItemGroups groups = group_items(
+      batch,
+      [&](int j, int i) {
+        return share_start && flags[j] == flags[i] && same_record(aperture + (size_t)j * AP_STRIDE, aperture + (size_t)i * AP_STRIDE, AP_STRIDE) &&
+               (!write_rows || same_record(write_rows + 2 * j, write_rows + 2 * i, 2)) &&
+               (!write_cols || same_record(write_cols + 2 * j, write_cols + 2 * i, 2));
+      },
+      [](int) { return true; });
   // ... and, with a Zernike surface riding on the write, inside each of them the groups of items with one wfe map: records equal
   // in everything but the wavelength (zernike_apply's rule, PAOS_SHARE_WFE); items without a Zernike record form one more
   const double *dzt = nullptr, *dzp = nullptr, *dsubs = nullptr, *dlead = nullptr, *dsame = nullptr;
   if (zk) {
-    const bool share_wfe = share_wfe_maps();
-    const int ps = zk->param_stride;
-    auto same_map = [&](int a, int b) {
-      const double *qa = zk->params + (size_t)a * ps, *qb = zk->params + (size_t)b * ps;
-      for (int k = 0; k < ps; ++k)
-        if (k != ZP_INV_WL && std::memcmp(qa + k, qb + k, sizeof(double))) return false;
-      return true;
-    };
-    std::vector<double> subs, sub_members, lead(c->batch, 0.0), same(c->batch, 0.0);
-    for (int i = 0; i < c->batch; ++i) {
-      const int g0 = (int)goff[i], gl = (int)glen[i];
-      for (int g = 0; g < gl; ++g) { same[(int)members[g0 + g]] = (double)i; }
-      if (gl == 0) continue;
-      lead[i] = 1.0;
-      const size_t first_sub = subs.size() / 3;
-      std::vector<char> placed(gl, 0);
-      for (int g = 0; g < gl; ++g) {
-        if (placed[g]) continue;
-        const int a = (int)members[g0 + g];
-        const bool off = zk->params[(size_t)a * ps + ZP_ENABLE] == 0.0;
-        subs.push_back(off ? -1.0 : (double)a);
-        subs.push_back((double)sub_members.size());
-        size_t count = 0;
-        for (int h = g; h < gl; ++h) {
-          const int b = (int)members[g0 + h];
-          if (placed[h]) continue;
-          const bool b_off = zk->params[(size_t)b * ps + ZP_ENABLE] == 0.0;
-          if (h == g || (off && b_off) || (!off && !b_off && share_wfe && same_map(a, b))) {
-            placed[h] = 1;
-            sub_members.push_back((double)b);
-            ++count;
-          }
-        }
-        subs.push_back((double)count);
-      }
-      goff[i] = (double)first_sub;               // the leader's run of sub-group records ...
-      glen[i] = (double)(subs.size() / 3 - first_sub);  // ... and their number
-    }
-    members = sub_members;
+    std::vector<double> lead, same;
+    group_leaders(groups, lead, same);  // (of the groups of identical start fields, before they are split)
+    const std::vector<double> subs = split_by_map(groups, zk->params, zk->param_stride, ZP_ENABLE, ZP_INV_WL, share_wfe_maps());
     if ((rc = arena_push(c, zk->table, (size_t)(zk->nmax + 1) * zk->kdim * 3, &dzt))) return rc;
-    if ((rc = arena_push(c, zk->params, (size_t)c->batch * ps, &dzp))) return rc;
+    if ((rc = arena_push(c, zk->params, (size_t)batch * zk->param_stride, &dzp))) return rc;
     if ((rc = arena_push(c, subs.data(), subs.size(), &dsubs))) return rc;
     if (zk->power_ticket) {  // one sum per group of identical start fields (paos_norm2_enqueue_box: same_as)
       if ((rc = arena_push(c, lead.data(), lead.size(), &dlead))) return rc;
@@ -279,83 +289,52 @@ static int start_impl(paos_ctx* c, double re, double im, int shape, const double
     }
   }
   const double *dgoff = nullptr, *dglen = nullptr, *dmembers = nullptr;
-  if ((rc = arena_push(c, goff.data(), goff.size(), &dgoff))) return rc;
-  if ((rc = arena_push(c, glen.data(), glen.size(), &dglen))) return rc;
-  if ((rc = arena_push(c, members.data(), members.size(), &dmembers))) return rc;
-  const dim3 block(kPwThreads);
-  // the power sums: found (same shape, constant, aperture records and stop flags as the last start) or evaluated and kept
+  if ((rc = arena_push(c, groups.goff.data(), groups.goff.size(), &dgoff))) return rc;
+  if ((rc = arena_push(c, groups.glen.data(), groups.glen.size(), &dglen))) return rc;
+  if ((rc = arena_push(c, groups.members.data(), groups.members.size(), &dmembers))) return rc;
   bool power_found = false;
-  if (any_stop) {
-    static const bool memo = !env_is("PAOS_START_POWER_MEMO", '0');
-    std::vector<double> key;
-    key.reserve(3 + (size_t)c->batch * (AP_STRIDE + 1));
-    key.push_back((double)shape); key.push_back(re); key.push_back(im);
-    key.insert(key.end(), aperture, aperture + (size_t)c->batch * AP_STRIDE);
-    key.insert(key.end(), flags.begin(), flags.end());
-    power_found = memo && c->start_norm2 && key.size() == c->start_key.size() &&
-                  !std::memcmp(key.data(), c->start_key.data(), key.size() * sizeof(double));
-    if (power_found) {
-      HIPCHK(c, hipMemcpyAsync(c->norm2, c->start_norm2, (size_t)c->batch * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    } else {
-      c->start_key.clear();  // (set again behind the launches below)
-      if (memo) c->start_key = std::move(key);
-    }
-  }
-#define START_LAUNCH(T, BRV, S)                                                                         \
-  do {                                                                                                  \
-    if (any_stop && !power_found) {                                                                     \
-      hipLaunchKernelGGL((start_power_kernel<T, BRV, Lay<T>::BC, S>), dim3(c->nparts, c->batch), block, 0, \
-                         c->stream, dp, c->n, c->pitch, c->item_stride, re, im, c->partial, dcompute);  \
-      hipLaunchKernelGGL(norm2_final_kernel, dim3(c->batch), block, 0, c->stream, c->partial, c->norm2,   \
-                         c->nparts, ds, 1, dpower_of);                                                  \
-    }                                                                                                   \
-    if (!zk)                                                                                            \
-      hipLaunchKernelGGL((start_write_kernel<T, BRV, Lay<T>::BC, S>), dim3(pw_blocks(c), c->batch), block, 0, \
-                         c->stream, (cx<T>*)c->field, dp, c->n, c->pitch, c->item_stride, re, im,        \
-                         (const double*)c->norm2, ds, drows, dgoff, dglen, dmembers, dcols);            \
-    else if (zk->nmax <= 8)                                                                             \
-      START_ZERNIKE_LAUNCH(T, BRV, S, 8);                                                               \
-    else                                                                                                \
-      START_ZERNIKE_LAUNCH(T, BRV, S, 0);                                                               \
-  } while (0)
-  // (orders up to 8 run on the unrolled build, like zernike_kernel) ... and the power of the start field from the weights,
-  // before the reduction behind it rewrites c->norm2
-#define START_ZERNIKE_LAUNCH(T, BRV, S, NC)                                                             \
-  do {                                                                                                  \
-    hipLaunchKernelGGL((zernike_start_write_kernel<T, BRV, Lay<T>::BC, S, NC>), dim3(pw_blocks(c), c->batch), block, 0, \
-                       c->stream, (cx<T>*)c->field, dp, c->n, c->pitch, c->item_stride, re, im,          \
-                       (const double*)c->norm2, ds, drows, dcols, dgoff, dglen, dsubs, dmembers, dzt, dzp, \
-                       zk->param_stride, zk->nmax, zk->kdim);                                           \
-    if (zk->power_ticket)                                                                               \
-      hipLaunchKernelGGL((start_norm2_partial_kernel<T, BRV, Lay<T>::BC, S>), dim3(c->nparts, c->batch), block, 0, \
-                         c->stream, c->partial, dp, c->n, c->pitch, c->item_stride, re, im,              \
-                         (const double*)c->norm2, ds, dlead, drows, dcols);                             \
-  } while (0)
-  if (c->precision == PAOS_F64) {
-    if (shape == PAOS_SHAPE_ELLIPSE) START_LAUNCH(double, BR, 0); else START_LAUNCH(double, BR, 1);
-  } else {
-    if (shape == PAOS_SHAPE_ELLIPSE) F32_BR_SWITCH(c, START_LAUNCH(float, FBR, 0)); else F32_BR_SWITCH(c, START_LAUNCH(float, FBR, 1));
-  }
-#undef START_LAUNCH
-#undef START_ZERNIKE_LAUNCH
+  if (any_stop && (rc = start_power_find(c, shape, re, im, aperture, flags, &power_found))) return rc;
+  const dim3 block(kPwThreads), sweep(pw_blocks(c), batch), parts(c->nparts, batch);
+  dispatch_layout(c, [&](auto t, auto br) {
+    using T = decltype(t);
+    constexpr int BRV = decltype(br)::value, BC = Lay<T>::BC;
+    dispatch_either<0, 1>(shape == PAOS_SHAPE_ELLIPSE, [&](auto s) {
+      constexpr int S = decltype(s)::value;
+      if (any_stop && !power_found) {
+        hipLaunchKernelGGL((start_power_kernel<T, BRV, BC, S>), parts, block, 0, c->stream, dp, c->n, c->pitch, c->item_stride, re, im,
+                           c->partial, dcompute);
+        hipLaunchKernelGGL(norm2_final_kernel, dim3(batch), block, 0, c->stream, c->partial, c->norm2, c->nparts, ds, 1, dpower_of);
+      }
+      if (!zk) {
+        hipLaunchKernelGGL((start_write_kernel<T, BRV, BC, S>), sweep, block, 0, c->stream, (cx<T>*)c->field, dp, c->n, c->pitch,
+                           c->item_stride, re, im, (const double*)c->norm2, ds, drows, dgoff, dglen, dmembers, dcols);
+        return;
+      }
+      // (orders up to 8 run on the unrolled build, like zernike_kernel) ... and the power of the start field from the
+      // weights, before the reduction behind it rewrites c->norm2
+      dispatch_either<8, 0>(zk->nmax <= 8, [&](auto nc) {
+        hipLaunchKernelGGL((zernike_start_write_kernel<T, BRV, BC, S, decltype(nc)::value>), sweep, block, 0, c->stream, (cx<T>*)c->field,
+                           dp, c->n, c->pitch, c->item_stride, re, im, (const double*)c->norm2, ds, drows, dcols, dgoff, dglen, dsubs,
+                           dmembers, dzt, dzp, zk->param_stride, zk->nmax, zk->kdim);
+      });
+      if (zk->power_ticket)
+        hipLaunchKernelGGL((start_norm2_partial_kernel<T, BRV, BC, S>), parts, block, 0, c->stream, c->partial, dp, c->n, c->pitch,
+                           c->item_stride, re, im, (const double*)c->norm2, ds, dlead, drows, dcols);
+    });
+  });
   HIPCHK(c, hipGetLastError());
-  if (any_stop && !power_found && !c->start_key.empty()) {  // keep the sums just evaluated (c->norm2 is rewritten by every reduction)
-    if (!c->start_norm2) HIPCHK(c, hipMalloc(&c->start_norm2, (size_t)c->batch * sizeof(double)));
-    HIPCHK(c, hipMemcpyAsync(c->start_norm2, c->norm2, (size_t)c->batch * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  }
-  if (zk && zk->power_ticket) return psf_power_ticket(c, c->partial, c->nparts, zk->power_ticket, dsame);
+  if (any_stop && !power_found && (rc = start_power_keep(c))) return rc;
+  if (zk && zk->power_ticket) return take_power_ticket(c, c->partial, c->nparts, dsame, zk->power_ticket);
   return PAOS_OK;
 }
 
 int paos_start(paos_ctx* c, double re, double im, int shape, const double* aperture, const double* stop) {
-  DROP_SCALE(c);
-  return start_impl(c, re, im, shape, aperture, stop, nullptr);
+  return paos_start_box(c, re, im, shape, aperture, stop, nullptr, nullptr);
 }
 
 int paos_start_rows(paos_ctx* c, double re, double im, int shape, const double* aperture, const double* stop,
                     const double* write_rows) {
-  DROP_SCALE(c);
-  return start_impl(c, re, im, shape, aperture, stop, write_rows);
+  return paos_start_box(c, re, im, shape, aperture, stop, write_rows, nullptr);
 }
 
 int paos_start_box(paos_ctx* c, double re, double im, int shape, const double* aperture, const double* stop,
@@ -383,14 +362,7 @@ int paos_zero_outside_box(paos_ctx* c, const double* live_rows, const double* li
   return zero_outside_box(c, live_rows, live_cols);
 }
 
-int paos_zero_outside_rows(paos_ctx* c, const double* live_rows) {
-  SETTLE_SCALE(c);
-  if (c) (void)hipSetDevice(c->device);
-  if (!c || !live_rows) return fail(c, PAOS_EINVAL, "null argument");
-  int rc = check_rows(c, live_rows);
-  if (rc) return rc;
-  return zero_outside_rows(c, live_rows);
-}
+int paos_zero_outside_rows(paos_ctx* c, const double* live_rows) { return paos_zero_outside_box(c, live_rows, nullptr); }
 
 int paos_import(paos_ctx* c, int item, const void* host) {
   SETTLE_SCALE(c);
@@ -398,14 +370,11 @@ int paos_import(paos_ctx* c, int item, const void* host) {
   if (!c || !host || item < 0 || item >= c->batch) return fail(c, PAOS_EINVAL, "bad item or null buffer");
   const size_t bytes = (size_t)c->n * c->n * 16;
   HIPCHK(c, hipMemcpyAsync(c->staging, host, bytes, hipMemcpyHostToDevice, c->stream));
-  if (c->precision == PAOS_F64)
-    hipLaunchKernelGGL((import_kernel<double, BR, Lay<double>::BC>), dim3(pw_blocks(c)), dim3(kPwThreads), 0, c->stream,
-                       (cx<double>*)c->field + (size_t)item * c->item_stride, (const cx<double>*)c->staging,
-                       c->n, c->pitch);
-  else
-    F32_BR_SWITCH(c, hipLaunchKernelGGL((import_kernel<float, FBR, Lay<float>::BC>), dim3(pw_blocks(c)), dim3(kPwThreads), 0, c->stream,
-                       (cx<float>*)c->field + (size_t)item * c->item_stride, (const cx<double>*)c->staging,
-                       c->n, c->pitch));
+  dispatch_layout(c, [&](auto t, auto br) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((import_kernel<T, decltype(br)::value, Lay<T>::BC>), dim3(pw_blocks(c)), dim3(kPwThreads), 0, c->stream,
+                       (cx<T>*)c->field + (size_t)item * c->item_stride, (const cx<double>*)c->staging, c->n, c->pitch);
+  });
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));  // the host buffer is only borrowed
   return PAOS_OK;
@@ -414,14 +383,11 @@ int paos_import(paos_ctx* c, int item, const void* host) {
 static int export_impl(paos_ctx* c, int item, int what, void* host_out, bool pinned) {
   if (!c || !host_out || item < 0 || item >= c->batch || what < 0 || what > 3)
     return fail(c, PAOS_EINVAL, "bad item/what or null buffer");
-  if (c->precision == PAOS_F64)
-    hipLaunchKernelGGL((export_kernel<double, BR, Lay<double>::BC>), dim3(pw_blocks(c)), dim3(kPwThreads), 0, c->stream,
-                       (const cx<double>*)c->field + (size_t)item * c->item_stride, (double*)c->staging,
-                       c->n, c->pitch, what);
-  else
-    F32_BR_SWITCH(c, hipLaunchKernelGGL((export_kernel<float, FBR, Lay<float>::BC>), dim3(pw_blocks(c)), dim3(kPwThreads), 0, c->stream,
-                       (const cx<float>*)c->field + (size_t)item * c->item_stride, (double*)c->staging,
-                       c->n, c->pitch, what));
+  dispatch_layout(c, [&](auto t, auto br) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((export_kernel<T, decltype(br)::value, Lay<T>::BC>), dim3(pw_blocks(c)), dim3(kPwThreads), 0, c->stream,
+                       (const cx<T>*)c->field + (size_t)item * c->item_stride, (double*)c->staging, c->n, c->pitch, what);
+  });
   HIPCHK(c, hipGetLastError());
   const size_t bytes = (size_t)c->n * c->n * (what == PAOS_WHAT_FIELD ? 16 : 8);
   if (pinned) {  // one DMA into page-locked memory
@@ -454,12 +420,11 @@ int paos_psf_keep(paos_ctx* c) {
   c->psf_zero_axis = -1;  // the whole buffer is rewritten
   c->otf_valid = false;   // ... and the transfer functions computed from the previous PSFs are stale
   const dim3 grid(pw_blocks(c), c->batch), block(kPwThreads);
-  if (c->precision == PAOS_F64)
-    hipLaunchKernelGGL((intensity_kernel<double, BR, Lay<double>::BC>), grid, block, 0, c->stream,
-                       (const cx<double>*)c->field, c->psf, c->n, c->pitch, c->item_stride);
-  else
-    F32_BR_SWITCH(c, hipLaunchKernelGGL((intensity_kernel<float, FBR, Lay<float>::BC>), grid, block, 0, c->stream,
-                       (const cx<float>*)c->field, c->psf, c->n, c->pitch, c->item_stride));
+  dispatch_layout(c, [&](auto t, auto br) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((intensity_kernel<T, decltype(br)::value, Lay<T>::BC>), grid, block, 0, c->stream, (const cx<T>*)c->field,
+                       c->psf, c->n, c->pitch, c->item_stride);
+  });
   HIPCHK(c, hipGetLastError());
   return PAOS_OK;
 }
@@ -469,28 +434,24 @@ int paos_psf_fetch(paos_ctx* c, int item, double* host_out) {
   if (!c || !host_out || item < 0 || item >= c->batch) return fail(c, PAOS_EINVAL, "bad item or null buffer");
   if (!c->psf) return fail(c, PAOS_EINVAL, "no PSF kept (paos_psf_keep)");
   // the PSF buffer is blocked like the field: row-major through the staging buffer
-  if (c->precision == PAOS_F64)
-    hipLaunchKernelGGL((psf_unblock_kernel<BR, Lay<double>::BC>), dim3(pw_blocks(c)), dim3(kPwThreads), 0, c->stream,
+  dispatch_layout(c, [&](auto t, auto br) {
+    hipLaunchKernelGGL((psf_unblock_kernel<decltype(br)::value, Lay<decltype(t)>::BC>), dim3(pw_blocks(c)), dim3(kPwThreads), 0, c->stream,
                        (const double*)c->psf + (size_t)item * c->item_stride, (double*)c->staging, c->n, c->pitch);
-  else
-    F32_BR_SWITCH(c, hipLaunchKernelGGL((psf_unblock_kernel<FBR, Lay<float>::BC>), dim3(pw_blocks(c)), dim3(kPwThreads), 0, c->stream,
-                       (const double*)c->psf + (size_t)item * c->item_stride, (double*)c->staging, c->n, c->pitch));
+  });
   HIPCHK(c, hipGetLastError());
   return copy_to_host(c, host_out, c->staging, (size_t)c->n * c->n * sizeof(double));
 }
 
 static int aperture_launch(paos_ctx* c, int shape, const double* dp, int nitems, double* mask_out) {
   const dim3 grid(pw_blocks(c), nitems), block(kPwThreads);
-#define AP_LAUNCH(T, BRV, S)                                                                     \
-  hipLaunchKernelGGL((aperture_kernel<T, BRV, Lay<T>::BC, S>), grid, block, 0, c->stream,                \
-                     mask_out ? (cx<T>*)nullptr : (cx<T>*)c->field, dp, (const double*)nullptr,    \
-                     AP_STRIDE, c->n, c->pitch, c->item_stride, mask_out, 0)
-  if (c->precision == PAOS_F64) {
-    if (shape == PAOS_SHAPE_ELLIPSE) AP_LAUNCH(double, BR, 0); else AP_LAUNCH(double, BR, 1);
-  } else {
-    if (shape == PAOS_SHAPE_ELLIPSE) F32_BR_SWITCH(c, AP_LAUNCH(float, FBR, 0)); else F32_BR_SWITCH(c, AP_LAUNCH(float, FBR, 1));
-  }
-#undef AP_LAUNCH
+  dispatch_layout(c, [&](auto t, auto br) {
+    using T = decltype(t);
+    dispatch_either<0, 1>(shape == PAOS_SHAPE_ELLIPSE, [&](auto s) {
+      hipLaunchKernelGGL((aperture_kernel<T, decltype(br)::value, Lay<T>::BC, decltype(s)::value>), grid, block, 0, c->stream,
+                         mask_out ? (cx<T>*)nullptr : (cx<T>*)c->field, dp, (const double*)nullptr, AP_STRIDE, c->n, c->pitch,
+                         c->item_stride, mask_out, 0);
+    });
+  });
   HIPCHK(c, hipGetLastError());
   return PAOS_OK;
 }
@@ -518,17 +479,16 @@ int paos_aperture_render(paos_ctx* c, int shape, const double* params1, double* 
   return copy_to_host(c, host_mask, c->staging, (size_t)c->n * c->n * 8);
 }
 
+// a stop's optional [batch] enable flags, on the device (null: every item)
+static int push_enable(paos_ctx* c, const double* enable, const double** den) {
+  *den = nullptr;
+  return enable ? arena_push(c, enable, (size_t)c->batch, den) : PAOS_OK;
+}
+
 static int norm2_launch(paos_ctx* c, const double* den) {
-  const dim3 grid(c->nparts, c->batch), block(kPwThreads);
-  if (c->precision == PAOS_F64)
-    hipLaunchKernelGGL((norm2_partial_kernel<double, BR, Lay<double>::BC>), grid, block, 0, c->stream,
-                       (const cx<double>*)c->field, c->partial, c->n, c->pitch, c->item_stride, den, 1);
-  else
-    F32_BR_SWITCH(c, hipLaunchKernelGGL((norm2_partial_kernel<float, FBR, Lay<float>::BC>), grid, block, 0, c->stream,
-                       (const cx<float>*)c->field, c->partial, c->n, c->pitch, c->item_stride, den, 1));
+  norm2_partial_launch(c, den);
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(norm2_final_kernel, dim3(c->batch), block, 0, c->stream, c->partial, c->norm2,
-                     c->nparts, den, 1);
+  hipLaunchKernelGGL(norm2_final_kernel, dim3(c->batch), dim3(kPwThreads), 0, c->stream, c->partial, c->norm2, c->nparts, den, 1);
   HIPCHK(c, hipGetLastError());
   return PAOS_OK;
 }
@@ -537,20 +497,10 @@ int paos_make_stop(paos_ctx* c, const double* enable) {
   SETTLE_SCALE(c);
   if (c) (void)hipSetDevice(c->device);  // one process may drive several GPUs
   if (!c) return fail(c, PAOS_EINVAL, "null context");
-  const double* den = nullptr;
-  if (enable) {
-    int rc = arena_push(c, enable, (size_t)c->batch, &den);
-    if (rc) return rc;
-  }
-  int rc = norm2_launch(c, den);
-  if (rc) return rc;
-  const dim3 grid(pw_blocks(c), c->batch), block(kPwThreads);
-  if (c->precision == PAOS_F64)
-    hipLaunchKernelGGL(stop_scale_kernel<double>, grid, block, 0, c->stream, (cx<double>*)c->field,
-                       c->norm2, c->item_stride, den, 1);
-  else
-    hipLaunchKernelGGL(stop_scale_kernel<float>, grid, block, 0, c->stream, (cx<float>*)c->field,
-                       c->norm2, c->item_stride, den, 1);
+  const double* den;
+  int rc = push_enable(c, enable, &den);
+  if (rc || (rc = norm2_launch(c, den))) return rc;
+  stop_scale_launch(c, den);
   HIPCHK(c, hipGetLastError());
   return PAOS_OK;
 }
@@ -561,16 +511,9 @@ int paos_stop_scale_last_power(paos_ctx* c, const double* enable) {
   if (!c->norm2_of_field) return paos_make_stop(c, enable);
   SETTLE_SCALE(c);  // (clears norm2_of_field: behind the stop c->norm2 no longer is the field's power)
   (void)hipSetDevice(c->device);
-  const double* den = nullptr;
-  if (enable) {
-    int rc = arena_push(c, enable, (size_t)c->batch, &den);
-    if (rc) return rc;
-  }
-  const dim3 grid(pw_blocks(c), c->batch), block(kPwThreads);
-  if (c->precision == PAOS_F64)
-    hipLaunchKernelGGL(stop_scale_kernel<double>, grid, block, 0, c->stream, (cx<double>*)c->field, c->norm2, c->item_stride, den, 1);
-  else
-    hipLaunchKernelGGL(stop_scale_kernel<float>, grid, block, 0, c->stream, (cx<float>*)c->field, c->norm2, c->item_stride, den, 1);
+  const double* den;
+  if (int rc = push_enable(c, enable, &den)) return rc;
+  stop_scale_launch(c, den);
   HIPCHK(c, hipGetLastError());
   return PAOS_OK;
 }
@@ -582,11 +525,8 @@ int paos_stop_defer_last_power(paos_ctx* c, const double* enable) {
   if (!c->norm2_of_field) return paos_make_stop(c, enable);
   (void)hipSetDevice(c->device);
   SETTLE_SCALE(c);  // (clears norm2_of_field)
-  const double* den = nullptr;
-  if (enable) {
-    int rc = arena_push(c, enable, (size_t)c->batch, &den);
-    if (rc) return rc;
-  }
+  const double* den;
+  if (int rc = push_enable(c, enable, &den)) return rc;
   hipLaunchKernelGGL(dyn_scale_set_kernel, dim3((c->batch + 255) / 256), dim3(256), 0, c->stream, c->dyn_scale, c->norm2, den, c->batch);
   HIPCHK(c, hipGetLastError());
   c->dyn_pending = true;
@@ -612,8 +552,9 @@ int paos_psf_metrics(paos_ctx* c, int nr, const double* radii_px, double cx_px, 
   a.item_stride = c->item_stride; a.cx = cx_px; a.cy = cy_px;
   for (int k = 0; k < nr; ++k) a.r2[k] = radii_px[k] * radii_px[k];
   const dim3 grid(nblocks, c->batch), block(kPwThreads);
-  if (c->precision == PAOS_F64) hipLaunchKernelGGL((psf_metrics_kernel<double, BR, Lay<double>::BC>), grid, block, 0, c->stream, a);
-  else F32_BR_SWITCH(c, hipLaunchKernelGGL((psf_metrics_kernel<float, FBR, Lay<float>::BC>), grid, block, 0, c->stream, a));
+  dispatch_layout(c, [&](auto t, auto br) {
+    hipLaunchKernelGGL((psf_metrics_kernel<decltype(t), decltype(br)::value, Lay<decltype(t)>::BC>), grid, block, 0, c->stream, a);
+  });
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(psf_metrics_final_kernel, dim3(c->batch), dim3(64), 0, c->stream, c->metric_partial, c->metric_out, nblocks, nvals);
   HIPCHK(c, hipGetLastError());
@@ -627,52 +568,27 @@ int paos_norm2_enqueue(paos_ctx* c, int* ticket) {
   SETTLE_SCALE(c);
   if (c) (void)hipSetDevice(c->device);  // one process may drive several GPUs
   if (!c || !ticket) return fail(c, PAOS_EINVAL, "null argument");
-  const int slot = next_norm_slot(c);
-  if (c->norm_busy[slot])  // the ring is full: the oldest ticket has not been fetched
-    return fail(c, PAOS_EINVAL, "64 power reductions outstanding: fetch earlier tickets (paos_norm2_fetch) first");
-  int rc = norm2_launch(c, nullptr);
-  if (rc) return rc;
-  c->norm_busy[slot] = true;
-  c->norm_slot = (slot + 1) % kNormSlots;
-  HIPCHK(c, hipMemcpyAsync(c->norm2_host + (size_t)slot * c->batch, c->norm2, (size_t)c->batch * sizeof(double),
-                           hipMemcpyDeviceToHost, c->stream));
-  *ticket = slot;
-  return PAOS_OK;
+  if (int rc = power_ring_full(c)) return rc;
+  norm2_partial_launch(c, nullptr);
+  HIPCHK(c, hipGetLastError());
+  return take_power_ticket(c, c->partial, c->nparts, nullptr, ticket);
 }
 
 }  // extern "C"
 
-// partial sums -> norm2 -> a ticket of the power ring
-int psf_power_ticket(paos_ctx* c, const double* partial, int nparts, int* ticket, const double* source) {
-  const int slot = next_norm_slot(c);
-  if (c->norm_busy[slot])
-    return fail(c, PAOS_EINVAL, "64 power reductions outstanding: fetch earlier tickets (paos_norm2_fetch) first");
-  hipLaunchKernelGGL(norm2_final_kernel, dim3(c->batch), dim3(kPwThreads), 0, c->stream, partial, c->norm2, nparts,
-                     (const double*)nullptr, 1, source);
-  HIPCHK(c, hipGetLastError());
-  c->norm_busy[slot] = true;
-  c->norm_slot = (slot + 1) % kNormSlots;
-  HIPCHK(c, hipMemcpyAsync(c->norm2_host + (size_t)slot * c->batch, c->norm2, (size_t)c->batch * sizeof(double),
-                           hipMemcpyDeviceToHost, c->stream));
-  *ticket = slot;
-  return PAOS_OK;
-}
-
 int psf_keep_power_impl(paos_ctx* c, int* ticket) {
-  if (c->norm_busy[next_norm_slot(c)])
-    return fail(c, PAOS_EINVAL, "64 power reductions outstanding: fetch earlier tickets (paos_norm2_fetch) first");
+  if (int rc = power_ring_full(c)) return rc;
   if (!c->psf) HIPCHK(c, hipMalloc(&c->psf, (size_t)c->batch * c->item_stride * sizeof(double)));
   c->psf_zero_axis = -1;  // the whole buffer is rewritten
   c->otf_valid = false;   // ... and the transfer functions computed from the previous PSFs are stale
   const dim3 grid(c->nparts, c->batch), block(kPwThreads);
-  if (c->precision == PAOS_F64)
-    hipLaunchKernelGGL((intensity_power_kernel<double, BR, Lay<double>::BC>), grid, block, 0, c->stream,
-                       (const cx<double>*)c->field, c->psf, c->partial, c->n, c->pitch, c->item_stride);
-  else
-    F32_BR_SWITCH(c, hipLaunchKernelGGL((intensity_power_kernel<float, FBR, Lay<float>::BC>), grid, block, 0, c->stream,
-                       (const cx<float>*)c->field, c->psf, c->partial, c->n, c->pitch, c->item_stride));
+  dispatch_layout(c, [&](auto t, auto br) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((intensity_power_kernel<T, decltype(br)::value, Lay<T>::BC>), grid, block, 0, c->stream, (const cx<T>*)c->field,
+                       c->psf, c->partial, c->n, c->pitch, c->item_stride);
+  });
   HIPCHK(c, hipGetLastError());
-  return psf_power_ticket(c, c->partial, c->nparts, ticket);
+  return take_power_ticket(c, c->partial, c->nparts, nullptr, ticket);
 }
 
 // rows outside [lo, hi) of every item := 0 (whole block rows, which are contiguous in memory)
@@ -701,12 +617,11 @@ int zero_outside_box(paos_ctx* c, const double* live_rows, const double* live_co
   const std::vector<double> lc = rounded_cols(c, live_cols);
   if ((rc = arena_push(c, lc.data(), lc.size(), &dcols))) return rc;
   const dim3 grid(pw_blocks(c), c->batch), block(kPwThreads);
-  if (c->precision == PAOS_F64)
-    hipLaunchKernelGGL((zero_outside_box_kernel<double, BR, Lay<double>::BC>), grid, block, 0, c->stream, (cx<double>*)c->field, c->n,
+  dispatch_layout(c, [&](auto t, auto br) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((zero_outside_box_kernel<T, decltype(br)::value, Lay<T>::BC>), grid, block, 0, c->stream, (cx<T>*)c->field, c->n,
                        c->pitch, c->item_stride, drows, dcols);
-  else
-    F32_BR_SWITCH(c, hipLaunchKernelGGL((zero_outside_box_kernel<float, FBR, Lay<float>::BC>), grid, block, 0, c->stream,
-                                        (cx<float>*)c->field, c->n, c->pitch, c->item_stride, drows, dcols));
+  });
   HIPCHK(c, hipGetLastError());
   return PAOS_OK;
 }
@@ -726,9 +641,7 @@ static int norm2_enqueue_rows_impl(paos_ctx* c, const double* live_rows, const d
   if (!c || !ticket || !live_rows) return fail(c, PAOS_EINVAL, "null argument");
   int rc = check_rows(c, live_rows);
   if (rc) return rc;
-  const int slot = next_norm_slot(c);
-  if (c->norm_busy[slot])
-    return fail(c, PAOS_EINVAL, "64 power reductions outstanding: fetch earlier tickets (paos_norm2_fetch) first");
+  if ((rc = power_ring_full(c))) return rc;
   const double *drows = nullptr, *dlead = nullptr, *dsame = nullptr, *dcols = nullptr;
   if ((rc = arena_push(c, live_rows, (size_t)2 * c->batch, &drows))) return rc;
   if (live_cols) {
@@ -736,11 +649,10 @@ static int norm2_enqueue_rows_impl(paos_ctx* c, const double* live_rows, const d
     if ((rc = arena_push(c, lc.data(), lc.size(), &dcols))) return rc;
   }
   if (same_as) {  // items whose fields the caller knows to be copies of another item's: summed once
+    if (!same_as_valid(same_as, c->batch, true)) return fail(c, PAOS_EINVAL, "same_as must name an item that stands for itself");
     std::vector<double> lead(c->batch);
     for (int i = 0; i < c->batch; ++i) {
       const int j = (int)same_as[i];
-      if (!(same_as[i] >= 0.0) || j >= c->batch || (double)j != same_as[i] || (int)same_as[j] != j)
-        return fail(c, PAOS_EINVAL, "same_as must name an item that stands for itself");
       if (live_rows[2 * i] != live_rows[2 * j] || live_rows[2 * i + 1] != live_rows[2 * j + 1] ||
           (live_cols && (live_cols[2 * i] != live_cols[2 * j] || live_cols[2 * i + 1] != live_cols[2 * j + 1])))
         return fail(c, PAOS_EINVAL, "items that share a sum must share their row (and column) window");
@@ -749,15 +661,9 @@ static int norm2_enqueue_rows_impl(paos_ctx* c, const double* live_rows, const d
     if ((rc = arena_push(c, lead.data(), lead.size(), &dlead))) return rc;
     if ((rc = arena_push(c, same_as, (size_t)c->batch, &dsame))) return rc;
   }
-  const dim3 grid(c->nparts, c->batch), block(kPwThreads);
-  if (c->precision == PAOS_F64)
-    hipLaunchKernelGGL((norm2_partial_kernel<double, BR, Lay<double>::BC>), grid, block, 0, c->stream,
-                       (const cx<double>*)c->field, c->partial, c->n, c->pitch, c->item_stride, dlead, 1, drows, dcols);
-  else
-    F32_BR_SWITCH(c, hipLaunchKernelGGL((norm2_partial_kernel<float, FBR, Lay<float>::BC>), grid, block, 0, c->stream,
-                       (const cx<float>*)c->field, c->partial, c->n, c->pitch, c->item_stride, dlead, 1, drows, dcols));
+  norm2_partial_launch(c, dlead, drows, dcols);
   HIPCHK(c, hipGetLastError());
-  return psf_power_ticket(c, c->partial, c->nparts, ticket, dsame);
+  return take_power_ticket(c, c->partial, c->nparts, dsame, ticket);
 }
 
 int paos_norm2_enqueue_box(paos_ctx* c, const double* live_rows, const double* live_cols, const double* same_as, int* ticket) {
@@ -805,12 +711,11 @@ int paos_phase_map(paos_ctx* c, int item, const double* host_wfe, double wl) {
   }
   if (!phase_map_argument_finite(wmax, wl)) return fail(c, PAOS_EINVAL, kPhaseMapOverflow);
   HIPCHK(c, hipMemcpyAsync(c->staging, host_wfe, count * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (c->precision == PAOS_F64)
-    hipLaunchKernelGGL((phase_map_kernel<double, BR, Lay<double>::BC>), dim3(pw_blocks(c)), dim3(kPwThreads), 0, c->stream,
-                       (cx<double>*)c->field + (size_t)item * c->item_stride, (const double*)c->staging, c->n, c->pitch, wl);
-  else
-    F32_BR_SWITCH(c, hipLaunchKernelGGL((phase_map_kernel<float, FBR, Lay<float>::BC>), dim3(pw_blocks(c)), dim3(kPwThreads), 0, c->stream,
-                       (cx<float>*)c->field + (size_t)item * c->item_stride, (const double*)c->staging, c->n, c->pitch, wl));
+  dispatch_layout(c, [&](auto t, auto br) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((phase_map_kernel<T, decltype(br)::value, Lay<T>::BC>), dim3(pw_blocks(c)), dim3(kPwThreads), 0, c->stream,
+                       (cx<T>*)c->field + (size_t)item * c->item_stride, (const double*)c->staging, c->n, c->pitch, wl);
+  });
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));  // the host buffer is only borrowed
   return PAOS_OK;
@@ -851,12 +756,11 @@ int paos_phase_map_items(paos_ctx* c, const double* host_wfe, unsigned long long
   if ((rc = arena_push(c, items, (size_t)n_items, &ditems))) return rc;
   if ((rc = arena_push(c, wl, (size_t)n_items, &dwl))) return rc;
   const dim3 grid(pw_blocks(c), n_items), block(kPwThreads);
-  if (c->precision == PAOS_F64)
-    hipLaunchKernelGGL((phase_map_items_kernel<double, BR, Lay<double>::BC>), grid, block, 0, c->stream, (cx<double>*)c->field,
+  dispatch_layout(c, [&](auto t, auto br) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((phase_map_items_kernel<T, decltype(br)::value, Lay<T>::BC>), grid, block, 0, c->stream, (cx<T>*)c->field,
                        c->item_stride, (const double*)c->map_dev, c->n, c->pitch, ditems, dwl);
-  else
-    F32_BR_SWITCH(c, hipLaunchKernelGGL((phase_map_items_kernel<float, FBR, Lay<float>::BC>), grid, block, 0, c->stream,
-                                        (cx<float>*)c->field, c->item_stride, (const double*)c->map_dev, c->n, c->pitch, ditems, dwl));
+  });
   HIPCHK(c, hipGetLastError());
   return PAOS_OK;
 }
@@ -929,10 +833,10 @@ int paos_copy_yardstick(paos_ctx* c, int reps, double* ms_per_launch, double* by
   HIPCHK(c, hipEventCreate(&e0));
   HIPCHK(c, hipEventCreate(&e1));
   auto launch = [&] {
-    if (c->precision == PAOS_F64)
-      hipLaunchKernelGGL(rmw_copy_kernel<double>, dim3(blocks), dim3(kPwThreads), 0, c->stream, (cx<double>*)c->field, total);
-    else
-      hipLaunchKernelGGL(rmw_copy_kernel<float>, dim3(blocks), dim3(kPwThreads), 0, c->stream, (cx<float>*)c->field, total);
+    dispatch_layout(c, [&](auto t, auto) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(rmw_copy_kernel<T>, dim3(blocks), dim3(kPwThreads), 0, c->stream, (cx<T>*)c->field, total);
+    });
   };
   launch();  // warm
   HIPCHK(c, hipEventRecord(e0, c->stream));
@@ -975,45 +879,19 @@ static int zernike_apply(paos_ctx* c, int nmax, int kdim, const double* table, c
   rc = arena_push(c, params, (size_t)c->batch * param_stride, &dp);
   if (rc) return rc;
   // groups of items with one wfe map: records equal in everything but the wavelength (and no per-item pupil)
-  const bool share_wfe = share_wfe_maps();
-  std::vector<double> goff(c->batch, 0.0), glen(c->batch, 0.0), members;
-  {
-    std::vector<int> lead(c->batch, -1);
-    auto same_map = [&](int a, int b) {
-      const double *qa = params + (size_t)a * param_stride, *qb = params + (size_t)b * param_stride;
-      for (int k = 0; k < param_stride; ++k)
-        if (k != ZP_INV_WL && std::memcmp(qa + k, qb + k, sizeof(double))) return false;
-      return true;
-    };
-    for (int i = 0; i < c->batch; ++i) {
-      if (params[(size_t)i * param_stride + ZP_ENABLE] == 0.0) continue;
-      lead[i] = i;
-      if (share_wfe && !use_pupil)
-        for (int j = 0; j < i; ++j)
-          if (lead[j] == j && same_map(j, i)) { lead[i] = j; break; }
-    }
-    for (int i = 0; i < c->batch; ++i) {
-      if (lead[i] != i) continue;
-      goff[i] = (double)members.size();
-      for (int j = i; j < c->batch; ++j)
-        if (lead[j] == i) members.push_back((double)j);
-      glen[i] = (double)members.size() - goff[i];
-    }
-    if (members.empty()) members.push_back(0.0);
-  }
+  const ItemGroups g = map_groups(c->batch, params, param_stride, ZP_ENABLE, ZP_INV_WL, share_wfe_maps() && !use_pupil);
   const double *dgoff = nullptr, *dglen = nullptr, *dmembers = nullptr, *dtwins = nullptr;
-  if ((rc = arena_push(c, goff.data(), goff.size(), &dgoff))) return rc;
-  if ((rc = arena_push(c, glen.data(), glen.size(), &dglen))) return rc;
-  if ((rc = arena_push(c, members.data(), members.size(), &dmembers))) return rc;
+  if ((rc = arena_push(c, g.goff.data(), g.goff.size(), &dgoff))) return rc;
+  if ((rc = arena_push(c, g.glen.data(), g.glen.size(), &dglen))) return rc;
+  if ((rc = arena_push(c, g.members.data(), g.members.size(), &dmembers))) return rc;
   if (same_as) {  // a group whose members all hold copies of one field reads the leader's (paos_zernike_like)
+    if (!same_as_valid(same_as, c->batch, false)) return fail(c, PAOS_EINVAL, "same_as must hold item indices");
     std::vector<double> twins(c->batch, 0.0);
     bool any = false;
     for (int i = 0; i < c->batch; ++i) {
-      if (!(same_as[i] >= 0.0) || same_as[i] >= (double)c->batch || same_as[i] != (double)(int)same_as[i])
-        return fail(c, PAOS_EINVAL, "same_as must hold item indices");
-      if (glen[i] < 2.0) continue;
+      if (g.glen[i] < 2.0) continue;
       bool all = true;
-      for (int g = 0; g < (int)glen[i]; ++g) all = all && same_as[(int)members[(size_t)goff[i] + g]] == same_as[i];
+      for (int k = 0; k < (int)g.glen[i]; ++k) all = all && same_as[(int)g.members[(size_t)g.goff[i] + k]] == same_as[i];
       twins[i] = all ? 1.0 : 0.0;
       any = any || all;
     }
@@ -1046,16 +924,14 @@ static int zernike_apply(paos_ctx* c, int nmax, int kdim, const double* table, c
     }
   }
   // orders up to 8 (45 polynomials) run on the unrolled build
-#define ZK_LAUNCH(T, BRV, NC)                                                                                          \
-  hipLaunchKernelGGL((zernike_kernel<T, BRV, Lay<T>::BC, NC>), grid, block, 0, c->stream, (cx<T>*)c->field, dt, dp,   \
-                     param_stride, c->n, c->pitch, c->item_stride, nmax, kdim, wfe, pupil, m_first, m_end, dgoff, dglen, \
-                     dmembers, dtwins)
-  if (c->precision == PAOS_F64) {
-    if (nmax <= 8) ZK_LAUNCH(double, BR, 8); else ZK_LAUNCH(double, BR, 0);
-  } else {
-    if (nmax <= 8) F32_BR_SWITCH(c, ZK_LAUNCH(float, FBR, 8)); else F32_BR_SWITCH(c, ZK_LAUNCH(float, FBR, 0));
-  }
-#undef ZK_LAUNCH
+  dispatch_layout(c, [&](auto t, auto br) {
+    using T = decltype(t);
+    dispatch_either<8, 0>(nmax <= 8, [&](auto nc) {
+      hipLaunchKernelGGL((zernike_kernel<T, decltype(br)::value, Lay<T>::BC, decltype(nc)::value>), grid, block, 0, c->stream, (cx<T>*)c->field,
+                         dt, dp, param_stride, c->n, c->pitch, c->item_stride, nmax, kdim, wfe, pupil, m_first, m_end, dgoff, dglen, dmembers,
+                         dtwins);
+    });
+  });
   HIPCHK(c, hipGetLastError());
   if (host_wfe) return copy_to_host(c, host_wfe, c->staging, (size_t)c->n * c->n * 8);
   return PAOS_OK;
@@ -1099,12 +975,12 @@ int paos_pupil_aperture(paos_ctx* c, int shape, const double* params) {
   const dim3 grid(pw_blocks(c), c->batch), block(kPwThreads);
   // the mask values of the aperture OBJECT, whatever its obscuration flag says (run.py:136-141)
   // (the element type is irrelevant without a field; the block height is the context's)
-  if (shape == PAOS_SHAPE_ELLIPSE)
-    F32_BR_SWITCH(c, hipLaunchKernelGGL((aperture_kernel<double, FBR, Lay<double>::BC, 0>), grid, block, 0, c->stream, (cx<double>*)nullptr,
-                       dp, (const double*)nullptr, AP_STRIDE, c->n, c->pitch, c->item_stride, c->mask, 2));
-  else
-    F32_BR_SWITCH(c, hipLaunchKernelGGL((aperture_kernel<double, FBR, Lay<double>::BC, 1>), grid, block, 0, c->stream, (cx<double>*)nullptr,
-                       dp, (const double*)nullptr, AP_STRIDE, c->n, c->pitch, c->item_stride, c->mask, 2));
+  dispatch_block_rows(c, [&](auto br) {
+    dispatch_either<0, 1>(shape == PAOS_SHAPE_ELLIPSE, [&](auto s) {
+      hipLaunchKernelGGL((aperture_kernel<double, decltype(br)::value, Lay<double>::BC, decltype(s)::value>), grid, block, 0, c->stream,
+                         (cx<double>*)nullptr, dp, (const double*)nullptr, AP_STRIDE, c->n, c->pitch, c->item_stride, c->mask, 2);
+    });
+  });
   HIPCHK(c, hipGetLastError());
   return PAOS_OK;
 }
@@ -1116,8 +992,10 @@ int paos_pupil_upload(paos_ctx* c, int item, const double* host_weights) {
   int rc = ensure_pupil(c);
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(c->staging, host_weights, (size_t)c->n * c->n * 8, hipMemcpyHostToDevice, c->stream));
-  F32_BR_SWITCH(c, hipLaunchKernelGGL((import_weights_kernel<FBR, Lay<double>::BC>), dim3(pw_blocks(c)), dim3(kPwThreads), 0, c->stream,
-                     (const double*)c->staging, c->mask + (size_t)item * c->item_stride, c->n, c->pitch, c->item_stride));
+  dispatch_block_rows(c, [&](auto br) {
+    hipLaunchKernelGGL((import_weights_kernel<decltype(br)::value, Lay<double>::BC>), dim3(pw_blocks(c)), dim3(kPwThreads), 0, c->stream,
+                       (const double*)c->staging, c->mask + (size_t)item * c->item_stride, c->n, c->pitch, c->item_stride);
+  });
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));  // host_weights is borrowed
   return PAOS_OK;
@@ -1167,7 +1045,7 @@ int paos_zernike_gram(paos_ctx* c, int nmax, int kdim, const double* table, cons
     return fail(c, PAOS_EHIP, "hipMalloc(gram sums)");
   }
   const size_t lds = (size_t)K * kGramRow * sizeof(double);
-  auto kern = c->br == PAOS_F32_BR ? zernike_gram_kernel<PAOS_F32_BR, Lay<double>::BC> : zernike_gram_kernel<BR, Lay<double>::BC>;
+  auto kern = dispatch_block_rows(c, [](auto br) { return zernike_gram_kernel<decltype(br)::value, Lay<double>::BC>; });
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(kern, dim3(nblocks, c->batch), dim3(kGramThreads), lds, c->stream, dt, dp, param_stride, c->n,

@@ -424,8 +424,7 @@ int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const do
   c->norm2_of_field = false;  // (set again at the end when the last pass sums the power of what it stores)
   // A program that ends on the PSF gives the field up for it: the free power-ticket slot it will need is checked
   // BEFORE anything is launched (found full afterwards, the context held neither field nor ticket).
-  if (final_ticket && c->norm_busy[next_norm_slot(c)])
-    return fail(c, PAOS_EINVAL, "64 power reductions outstanding: fetch earlier tickets (paos_norm2_fetch) first");
+  if (int rcr = final_ticket ? power_ring_full(c) : PAOS_OK) return rcr;
   // The device sincos has no huge-argument path: bound every enabled phase operator here.
   for (int i = 0; i < n_passes; ++i) {
     const paos_pw_op* lists[3] = {passes[i].pre, passes[i].mid, passes[i].post};
@@ -711,14 +710,14 @@ int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const do
   }
   if (final_ticket && final_mode == 2) {
     // (the fallback: a generic-kernel pass, or an item that sat the last pass out)
-    const int rcp = fused_power ? psf_power_ticket(c, c->pow_partial, power_groups, final_ticket) : paos_norm2_enqueue(c, final_ticket);
+    const int rcp = fused_power ? take_power_ticket(c, c->pow_partial, power_groups, nullptr, final_ticket) : paos_norm2_enqueue(c, final_ticket);
     if (rcp == PAOS_OK) c->norm2_of_field = true;  // c->norm2 = the power of every item's field as stored
     return rcp;
   }
   if (final_ticket) {
     if (fused_store) {
       c->psf_zero_axis = passes[n_passes - 1].axis;  // every launch of the program went through
-      return psf_power_ticket(c, c->psf_partial, c->n / frugal_tile_lines(c, passes[n_passes - 1].axis), final_ticket);
+      return take_power_ticket(c, c->psf_partial, c->n / frugal_tile_lines(c, passes[n_passes - 1].axis), nullptr, final_ticket);
     }
     return psf_keep_power_impl(c, final_ticket);
   }

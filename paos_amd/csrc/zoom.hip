@@ -249,8 +249,7 @@ int paos_zoom_compute(paos_ctx* c, int m, int s, const double* centres, int want
   int pty = 1, ptx = 1;
   rc = paos_zoom_tiles(n, nb, m, &pty, &ptx);  // the one rule of the launch plan, as the host-side query reports it
   if (rc) return rc;
-  if (c->precision == PAOS_F64) zoom_launch<double, 0>(c, a, pty);
-  else zoom_launch<float, 0>(c, a, pty);
+  dispatch_layout(c, [&](auto t, auto) { zoom_launch<decltype(t), 0>(c, a, pty); });
   HIPCHK(c, hipGetLastError());
   // stage X: T -> the windows
   a.src = c->zoom_t;

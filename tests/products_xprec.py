@@ -163,7 +163,7 @@ def zoom_check(got, ref, yard, rigorous, what):
 
 
 # ---- transfer functions -------------------------------------------------------------------------------------------------
-OTF_COLS_PER_WORKGROUP = 2  # csrc/focus_otf.hip: otf_launch<T, 4096, 1> runs COL_LINES x COL_TILES = 2 x 1 columns per workgroup
+OTF_COLS_PER_WORKGROUP = 2  # csrc/focus_otf.hip: the OTF column pass at 4096 (tile_pass) runs COL_LINES x COL_TILES = 2 x 1 columns per workgroup
 
 
 def otf_random_field(n):
