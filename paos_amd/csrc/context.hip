@@ -4,6 +4,7 @@
 
 #include <cmath>
 #include <complex>
+#include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <set>
@@ -24,9 +25,27 @@ int fail(paos_ctx* c, int code, const std::string& msg) {
 
 namespace {
 
+// PAOS_DUMP_PASSES=1 (passes.hip: the build of every launch) also says, on stderr, when the arena goes to its next slab or grows
+bool dump_arena() {
+  static const bool dump = env_is("PAOS_DUMP_PASSES", '1');
+  return dump;
+}
+
+// copy what has been added and not copied yet, [sent, head) of the slab being filled, in ONE transfer
+int arena_commit(paos_ctx* c) {
+  Arena& a = c->arena;
+  size_t first = 0, count = 0;
+  if (!a.lay.take(&first, &count)) return PAOS_OK;
+  const size_t at = (size_t)a.cur * a.lay.cap + first;
+  HIPCHK(c, hipMemcpyAsync(a.dev + at, a.host + at, count * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  return PAOS_OK;
+}
+
 // next slab: record the fence of the slab left one switch ago, wait for the readers of the slab about to be refilled
+// (blocks still pending in the slab being left are copied first)
 int arena_switch(paos_ctx* c) {
   Arena& a = c->arena;
+  if (int rc = arena_commit(c)) return rc;
   if (a.left >= 0) {
     HIPCHK(c, hipEventRecord(a.fence[a.left], c->stream));
     a.fenced[a.left] = true;
@@ -40,7 +59,8 @@ int arena_switch(paos_ctx* c) {
   a.fenced[next] = false;
   a.used[next] = true;
   a.cur = next;
-  a.head = 0;
+  a.lay.rewind();
+  if (dump_arena()) std::fprintf(stderr, "arena switch to slab %d\n", next);
   return PAOS_OK;
 }
 
@@ -56,43 +76,71 @@ int launch_failed(paos_ctx* c, const char* call, hipError_t e, const char* file,
 // wrap (one stream synchronisation) or a growth of the arena happens here, before the first push.
 int arena_reserve(paos_ctx* c, size_t total) {
   Arena& a = c->arena;
-  total += 64;  // rounding of the individual pushes
-  if (total > a.cap) {  // (grow every slab: one synchronisation, once)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    size_t cap = a.cap;
-    while (cap < total) cap *= 2;
-    double *h = nullptr, *d = nullptr;
-    HIPCHK(c, hipHostMalloc(&h, kArenaSlabs * cap * sizeof(double)));
-    if (hipMalloc(&d, kArenaSlabs * cap * sizeof(double)) != hipSuccess) {
-      (void)hipHostFree(h);
-      return fail(c, PAOS_EHIP, "hipMalloc(arena growth)");
-    }
-    (void)hipHostFree(a.host);
-    (void)hipFree(a.dev);
-    a.host = h; a.dev = d; a.cap = cap; a.head = 0; a.cur = 0; a.left = -1;
-    for (int k = 0; k < kArenaSlabs; ++k) a.fenced[k] = a.used[k] = false;
-    a.used[0] = true;
-    return PAOS_OK;
+  switch (a.lay.room(total)) {  // (kArenaSlack on top: the rounding of the individual pushes)
+    case ARENA_FITS: return PAOS_OK;
+    case ARENA_SWITCH: return arena_switch(c);
+    case ARENA_GROW: break;
   }
-  if (a.head + total > a.cap) return arena_switch(c);
+  // grow every slab: one synchronisation, once (behind the copy of what is still pending: its readers may follow)
+  if (int rc = arena_commit(c)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t cap = a.lay.grown(total);
+  double *h = nullptr, *d = nullptr;
+  HIPCHK(c, hipHostMalloc(&h, kArenaSlabs * cap * sizeof(double)));
+  if (hipMalloc(&d, kArenaSlabs * cap * sizeof(double)) != hipSuccess) {
+    (void)hipHostFree(h);
+    return fail(c, PAOS_EHIP, "hipMalloc(arena growth)");
+  }
+  (void)hipHostFree(a.host);
+  (void)hipFree(a.dev);
+  if (dump_arena()) std::fprintf(stderr, "arena grow to %zu doubles per slab\n", cap);
+  a.host = h; a.dev = d; a.lay.cap = cap; a.lay.rewind(); a.cur = 0; a.left = -1;
+  for (int k = 0; k < kArenaSlabs; ++k) a.fenced[k] = a.used[k] = false;
+  a.used[0] = true;
   return PAOS_OK;
 }
 
-// copy `count` doubles into the arena; returns the device pointer through *dev
-int arena_push(paos_ctx* c, const double* src, size_t count, const double** dev) {
-  Arena& a = c->arena;
-  if (count > a.cap) return fail(c, PAOS_EINVAL, "parameter block larger than the arena");
-  if (a.head + count > a.cap) {
-    int rc = arena_switch(c);
-    if (rc) return rc;
+int ArenaBatch::begin(size_t total) {
+  if (st_.closed || st_.reserved) return fail(c_, PAOS_EINVAL, "a parameter batch is begun once, before its first block");
+  const int rc = arena_reserve(c_, total);
+  if (rc == PAOS_OK) st_.reserved = true;
+  return rc;
+}
+
+// write `count` doubles into the pinned slab at the head; *dev: where the commit will put them on the device
+int ArenaBatch::add(const double* src, size_t count, const double** dev) {
+  Arena& a = c_->arena;
+  if (!st_.may_add()) return fail(c_, PAOS_EINVAL, "parameter block added to a batch that has been committed");
+  if (count > a.lay.cap) return fail(c_, PAOS_EINVAL, "parameter block larger than the arena");
+  if (!a.lay.fits(count)) {
+    if (!st_.may_switch()) return fail(c_, PAOS_EINVAL, "a parameter batch outgrew the room it reserved");
+    if (int rc = arena_switch(c_)) return rc;
   }
-  double* h = a.host + (size_t)a.cur * a.cap + a.head;
-  double* d = a.dev + (size_t)a.cur * a.cap + a.head;
-  std::memcpy(h, src, count * sizeof(double));
-  HIPCHK(c, hipMemcpyAsync(d, h, count * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  *dev = d;
-  a.head += (count + 15) & ~size_t(15);
+  const size_t at = (size_t)a.cur * a.lay.cap + a.lay.place(count);
+  std::memcpy(a.host + at, src, count * sizeof(double));
+  *dev = a.dev + at;
   return PAOS_OK;
+}
+
+int ArenaBatch::commit() {
+  st_.closed = true;
+  return arena_commit(c_);
+}
+
+// one block, one copy (whatever else is pending goes with it)
+int arena_push(paos_ctx* c, const double* src, size_t count, const double** dev) {
+  ArenaBatch one(c);
+  if (int rc = one.add(src, count, dev)) return rc;
+  return one.commit();
+}
+
+int arena_settled(paos_ctx* c, int rc) {
+  if (!c) return rc;
+  const bool pending = c->arena.lay.pending();
+  c->arena.lay.drop();
+  if (rc == PAOS_OK && pending)
+    return fail(c, PAOS_EHIP, "parameter blocks were added but never copied to the device: the call's launches read stale parameters");
+  return rc;
 }
 
 // Device -> caller's (pageable) host buffer.  hipMemcpy into pageable memory pins the target pages
@@ -297,10 +345,13 @@ int paos_ctx_create(int device, int n, int batch, int precision, paos_ctx** out)
   if ((e = hipMalloc(&c->partial, (size_t)batch * c->nparts * sizeof(double))) != hipSuccess) return bail(e, "hipMalloc(partial)");
   if ((e = hipMalloc(&c->norm2, (size_t)batch * sizeof(double))) != hipSuccess) return bail(e, "hipMalloc(norm2)");
   if ((e = hipHostMalloc(&c->norm2_host, (size_t)kNormSlots * batch * sizeof(double))) != hipSuccess) return bail(e, "hipHostMalloc(norm2)");
-  c->arena.cap = (size_t)1 << 18;  // four slabs of 2 MiB of doubles; a large batch starts with room for one of its programs per slab
-  if (c->arena.cap < (size_t)batch * 2048) c->arena.cap = (size_t)batch * 2048;
-  if ((e = hipHostMalloc(&c->arena.host, kArenaSlabs * c->arena.cap * sizeof(double))) != hipSuccess) return bail(e, "hipHostMalloc(arena)");
-  if ((e = hipMalloc(&c->arena.dev, kArenaSlabs * c->arena.cap * sizeof(double))) != hipSuccess) return bail(e, "hipMalloc(arena)");
+  c->arena.lay.cap = (size_t)1 << 18;  // four slabs of 2 MiB of doubles; a large batch starts with room for one of its programs per slab
+  if (c->arena.lay.cap < (size_t)batch * 2048) c->arena.lay.cap = (size_t)batch * 2048;
+  // PAOS_ARENA_DOUBLES: another slab size to start with (whole blocks, at least one); a batch that reserves more grows the
+  // slabs, a single block pushed on its own has to fit
+  if (const char* cap = getenv("PAOS_ARENA_DOUBLES")) c->arena.lay.cap = arena_rounded((size_t)std::max(1LL, std::atoll(cap)));
+  if ((e = hipHostMalloc(&c->arena.host, kArenaSlabs * c->arena.lay.cap * sizeof(double))) != hipSuccess) return bail(e, "hipHostMalloc(arena)");
+  if ((e = hipMalloc(&c->arena.dev, kArenaSlabs * c->arena.lay.cap * sizeof(double))) != hipSuccess) return bail(e, "hipMalloc(arena)");
   for (int k = 0; k < kArenaSlabs; ++k)
     if ((e = hipEventCreateWithFlags(&c->arena.fence[k], hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate(arena fence)");
   c->arena.used[0] = true;
@@ -409,6 +460,7 @@ int paos_ctx_destroy(paos_ctx* c) {
   if (c->map_dev) (void)hipFree(c->map_dev);
   if (c->psd_scratch) (void)hipFree(c->psd_scratch);
   if (c->start_norm2) (void)hipFree(c->start_norm2);
+  if (c->start_partial) (void)hipFree(c->start_partial);
   if (c->psd_bad) (void)hipFree(c->psd_bad);
   if (c->pow_partial) (void)hipFree(c->pow_partial);
   if (c->dyn_scale) (void)hipFree(c->dyn_scale);

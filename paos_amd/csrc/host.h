@@ -7,7 +7,7 @@
 // context is at run time into template arguments (dispatch_n: the grid size; dispatch_layout / dispatch_block_rows: element
 // type and block height -- every launch is written once, inside a generic lambda), and the declarations of the functions
 // that cross unit boundaries.  Whatever is not declared here lives in an anonymous namespace of its unit.  Which items of a
-// batch share what is plain C++ in item_groups.h.
+// batch share what is plain C++ in item_groups.h, where the blocks of the parameter arena go in arena_layout.h.
 #pragma once
 #include "../../include/paos_hip.h"
 
@@ -18,6 +18,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "arena_layout.h"
 #include "frugal_pass.h"
 
 using namespace paos;
@@ -58,11 +59,15 @@ struct Lay {
 // two slabs) -- instead of by a hipStreamSynchronize at every wrap of one ring: at 512 wavefronts per step the ring
 // wrapped every second step, and each wrap made the host wait for the GPU to drain (1024^2: 33 ms per step where the GPU
 // needs 25 and the host 18).  With four slabs the host may run two to three steps ahead and no further.
+// Round 17: a block is written to the pinned slab when it is added and copied to the device when its batch is committed --
+// one hipMemcpyAsync for every block a call adds in front of its first launch (ArenaBatch below), instead of one per block
+// (22 copy kernels of ~4.7 us per SYN20 step, each a dispatch of its own in front of the kernel that reads it).
+// PAOS_ARENA_DOUBLES: the slab size a context starts with (tests: a small one, so that a short sweep goes round the slabs).
 constexpr int kArenaSlabs = 4;
 struct Arena {
-  double* host = nullptr;  // pinned, kArenaSlabs * cap doubles
+  double* host = nullptr;  // pinned, kArenaSlabs * lay.cap doubles
   double* dev = nullptr;
-  size_t cap = 0, head = 0;  // doubles per slab / fill of the current slab
+  ArenaLayout lay;           // doubles per slab, fill of the current slab, what of it is not copied yet (arena_layout.h)
   int cur = 0;               // slab being filled
   int left = -1;             // the slab left at the last switch: its fence is recorded at the NEXT switch
   hipEvent_t fence[kArenaSlabs] = {};
@@ -112,6 +117,13 @@ struct paos_ctx {
   // overlaps again (start_power_kernel + norm2_final_kernel: 0.08 ms of a 14.6 ms SYN20 step).  PAOS_START_POWER_MEMO=0: never.
   std::vector<double> start_key;
   double* start_norm2 = nullptr;  // [batch]
+  // (round 17) ... and the per-workgroup sums of the power of the start FIELD inside its box (start_norm2_partial_kernel:
+  // the saved first surface of a lean sweep, whose field is never stored on its own), [batch][nparts]: a pure function of
+  // the start key, the row windows, the rounded column windows and which items lead / share a sum.  The final reduction
+  // runs every time, so the power is the same bits.  Both keys are set only once the launches that fill the sums are
+  // enqueued, and a failed start clears both.
+  std::vector<double> start_partial_key;
+  double* start_partial = nullptr;
   cx<double>* psd_scratch = nullptr;  // one item in the field's layout: the spectrum of a PSD screen (paos_psd_screen)
   int* psd_bad = nullptr;
   double* psf_partial = nullptr;  // per-workgroup sums of a pass that stores the PSF (paos_run_program: final_intensity)
@@ -262,7 +274,27 @@ inline int frugal_tile_lines(const paos_ctx* c, int axis) { return axis == 0 ? (
 // ---- context.hip ---------------------------------------------------------------------------------------------
 // the parameter arena: make room for `total` doubles that must all stay live / copy `count` doubles, *dev: where they are
 int arena_reserve(paos_ctx* c, size_t total);
-int arena_push(paos_ctx* c, const double* src, size_t count, const double** dev);
+int arena_push(paos_ctx* c, const double* src, size_t count, const double** dev);  // one block: add + commit
+// Several blocks, one copy: begin(total) makes room for all of them in ONE slab (arena_reserve: grow, or switch, before the
+// first block), add() writes a block to the pinned slab and says at once where it will be on the device, commit() copies
+// everything added and not copied yet -- [first block, head) -- in one transfer.  The device pointers may go to kernels
+// launched BEHIND commit() only: a launch in front of it reads whatever the slab held four switches ago.  So a batch is
+// closed by its commit (a later add is refused), and an entry point that ends well with blocks still pending fails
+// (arena_settled).  Without begin() a block that does not fit the slab commits what is pending and switches, like arena_push.
+class ArenaBatch {
+ public:
+  explicit ArenaBatch(paos_ctx* c) : c_(c) {}
+  int begin(size_t total);
+  int add(const double* src, size_t count, const double** dev);
+  int commit();
+
+ private:
+  paos_ctx* c_;
+  ArenaBatchState st_;
+};
+// the last thing an entry point that adds blocks does with its result: an error drops what is still pending (never copied;
+// the head stays advanced), PAOS_OK with blocks pending becomes a failure
+int arena_settled(paos_ctx* c, int rc);
 int copy_to_host(paos_ctx* c, void* host, const void* dev, size_t bytes);  // device -> pageable host; synchronises
 int next_norm_slot(paos_ctx* c);                                           // the next free slot of the power-ticket ring
 int check_mask_overflow(paos_ctx* c);  // after a synchronisation: did an aperture's partial run overflow its line records?

@@ -199,36 +199,22 @@ struct StartZernike {
 };
 static int zernike_check(paos_ctx* c, int nmax, int kdim, const double* table, const double* params, int param_stride);
 
-// The power sums of a start with stops, into c->norm2: those of the last start if that had the same shape, constant,
-// aperture records and stop flags (paos_ctx::start_key; *found), else the launch evaluates them and start_power_keep keeps them.
-static int start_power_find(paos_ctx* c, int shape, double re, double im, const double* aperture, const std::vector<double>& flags, bool* found) {
+// What a start keeps from call to call (paos_ctx::start_key, start_partial_key).  PAOS_START_POWER_MEMO=0: nothing.
+static bool start_memo_on() {
   static const bool memo = !env_is("PAOS_START_POWER_MEMO", '0');
-  std::vector<double> key;
-  key.reserve(3 + (size_t)c->batch * (AP_STRIDE + 1));
-  key.push_back((double)shape); key.push_back(re); key.push_back(im);
-  key.insert(key.end(), aperture, aperture + (size_t)c->batch * AP_STRIDE);
-  key.insert(key.end(), flags.begin(), flags.end());
-  *found = memo && c->start_norm2 && key.size() == c->start_key.size() &&
-           !std::memcmp(key.data(), c->start_key.data(), key.size() * sizeof(double));
-  if (*found) {
-    HIPCHK(c, hipMemcpyAsync(c->norm2, c->start_norm2, (size_t)c->batch * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  } else {
-    c->start_key.clear();  // (set again behind the launches of the start)
-    if (memo) c->start_key = std::move(key);
-  }
-  return PAOS_OK;
+  return memo;
 }
-// keep the sums just evaluated (c->norm2 is rewritten by every reduction)
-static int start_power_keep(paos_ctx* c) {
-  if (c->start_key.empty()) return PAOS_OK;
-  if (!c->start_norm2) HIPCHK(c, hipMalloc(&c->start_norm2, (size_t)c->batch * sizeof(double)));
-  HIPCHK(c, hipMemcpyAsync(c->start_norm2, c->norm2, (size_t)c->batch * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  return PAOS_OK;
+static bool same_key(const std::vector<double>& a, const std::vector<double>& b) {
+  return a.size() == b.size() && !std::memcmp(a.data(), b.data(), a.size() * sizeof(double));
+}
+static void start_forget(paos_ctx* c) {
+  c->start_key.clear();
+  c->start_partial_key.clear();
 }
 
-// check, group, push, find or evaluate the power sums, launch, keep the sums
-static int start_impl(paos_ctx* c, double re, double im, int shape, const double* aperture, const double* stop,
-                      const double* write_rows, const double* write_cols = nullptr, const StartZernike* zk = nullptr) {
+// check, group, upload (one copy), find or evaluate the power sums, launch, keep the sums
+static int start_body(paos_ctx* c, double re, double im, int shape, const double* aperture, const double* stop,
+                      const double* write_rows, const double* write_cols, const StartZernike* zk) {
   if (c) (void)hipSetDevice(c->device);
   if (!c || !aperture) return fail(c, PAOS_EINVAL, "null argument");
   if (shape != PAOS_SHAPE_ELLIPSE && shape != PAOS_SHAPE_RECT) return fail(c, PAOS_EINVAL, "unknown aperture shape");
@@ -246,22 +232,12 @@ static int start_impl(paos_ctx* c, double re, double im, int shape, const double
   // have identical power sums: stage 1 runs for the first of them, stage 2 sums ITS partials for all
   std::vector<double> power_of, compute;
   power_representatives(batch, aperture, AP_STRIDE, flags.data(), power_of, compute);
-  const double *dp = nullptr, *ds = nullptr, *dcompute = nullptr, *dpower_of = nullptr;
-  if ((rc = arena_push(c, aperture, (size_t)batch * AP_STRIDE, &dp))) return rc;
-  if ((rc = arena_push(c, flags.data(), flags.size(), &ds))) return rc;
-  if ((rc = arena_push(c, compute.data(), compute.size(), &dcompute))) return rc;
-  if ((rc = arena_push(c, power_of.data(), power_of.size(), &dpower_of))) return rc;
-  const double* drows = nullptr;
-  if (write_rows) {
-    if ((rc = check_rows(c, write_rows))) return rc;
-    if ((rc = arena_push(c, write_rows, (size_t)2 * batch, &drows))) return rc;
-  }
-  const double* dcols = nullptr;
+  if (write_rows && (rc = check_rows(c, write_rows))) return rc;
+  std::vector<double> wc;
   if (write_cols) {
     if (!write_rows) return fail(c, PAOS_EINVAL, "a column window needs a row window");
     if ((rc = check_rows(c, write_cols))) return rc;
-    const std::vector<double> wc = rounded_cols(c, write_cols);
-    if ((rc = arena_push(c, wc.data(), wc.size(), &dcols))) return rc;
+    wc = rounded_cols(c, write_cols);
   }
   // groups of items that start from the same field (start_write_kernel): PAOS_SHARE_START=0: never
   static const bool share_start = !env_is("PAOS_SHARE_START", '0');
@@ -275,25 +251,76 @@ static int start_impl(paos_ctx* c, double re, double im, int shape, const double
       [](int) { return true; });
   // ... and, with a Zernike surface riding on the write, inside each of them the groups of items with one wfe map: records equal
   // in everything but the wavelength (zernike_apply's rule, PAOS_SHARE_WFE); items without a Zernike record form one more
+  std::vector<double> lead, same, subs;
+  const bool want_power = zk && zk->power_ticket;  // one sum per group of identical start fields (paos_norm2_enqueue_box: same_as)
+  if (zk) {
+    group_leaders(groups, lead, same);  // (of the groups of identical start fields, before they are split)
+    subs = split_by_map(groups, zk->params, zk->param_stride, ZP_ENABLE, ZP_INV_WL, share_wfe_maps());
+  }
+  // every block of the call in one slab, one copy in front of the first launch
+  const size_t zt_count = zk ? (size_t)(zk->nmax + 1) * zk->kdim * 3 : 0, zp_count = zk ? (size_t)batch * zk->param_stride : 0;
+  size_t total = arena_rounded((size_t)batch * AP_STRIDE) + 3 * arena_rounded(batch) + arena_rounded(groups.goff.size()) +
+                 arena_rounded(groups.glen.size()) + arena_rounded(groups.members.size());
+  if (write_rows) total += arena_rounded((size_t)2 * batch);
+  if (write_cols) total += arena_rounded(wc.size());
+  if (zk) total += arena_rounded(zt_count) + arena_rounded(zp_count) + arena_rounded(subs.size());
+  if (want_power) total += 2 * arena_rounded(batch);
+  ArenaBatch ab(c);
+  if ((rc = ab.begin(total))) return rc;
+  const double *dp = nullptr, *ds = nullptr, *dcompute = nullptr, *dpower_of = nullptr, *drows = nullptr, *dcols = nullptr;
+  if ((rc = ab.add(aperture, (size_t)batch * AP_STRIDE, &dp))) return rc;
+  if ((rc = ab.add(flags.data(), flags.size(), &ds))) return rc;
+  if ((rc = ab.add(compute.data(), compute.size(), &dcompute))) return rc;
+  if ((rc = ab.add(power_of.data(), power_of.size(), &dpower_of))) return rc;
+  if (write_rows && (rc = ab.add(write_rows, (size_t)2 * batch, &drows))) return rc;
+  if (write_cols && (rc = ab.add(wc.data(), wc.size(), &dcols))) return rc;
   const double *dzt = nullptr, *dzp = nullptr, *dsubs = nullptr, *dlead = nullptr, *dsame = nullptr;
   if (zk) {
-    std::vector<double> lead, same;
-    group_leaders(groups, lead, same);  // (of the groups of identical start fields, before they are split)
-    const std::vector<double> subs = split_by_map(groups, zk->params, zk->param_stride, ZP_ENABLE, ZP_INV_WL, share_wfe_maps());
-    if ((rc = arena_push(c, zk->table, (size_t)(zk->nmax + 1) * zk->kdim * 3, &dzt))) return rc;
-    if ((rc = arena_push(c, zk->params, (size_t)batch * zk->param_stride, &dzp))) return rc;
-    if ((rc = arena_push(c, subs.data(), subs.size(), &dsubs))) return rc;
-    if (zk->power_ticket) {  // one sum per group of identical start fields (paos_norm2_enqueue_box: same_as)
-      if ((rc = arena_push(c, lead.data(), lead.size(), &dlead))) return rc;
-      if ((rc = arena_push(c, same.data(), same.size(), &dsame))) return rc;
+    if ((rc = ab.add(zk->table, zt_count, &dzt))) return rc;
+    if ((rc = ab.add(zk->params, zp_count, &dzp))) return rc;
+    if ((rc = ab.add(subs.data(), subs.size(), &dsubs))) return rc;
+    if (want_power) {
+      if ((rc = ab.add(lead.data(), lead.size(), &dlead))) return rc;
+      if ((rc = ab.add(same.data(), same.size(), &dsame))) return rc;
     }
   }
   const double *dgoff = nullptr, *dglen = nullptr, *dmembers = nullptr;
-  if ((rc = arena_push(c, groups.goff.data(), groups.goff.size(), &dgoff))) return rc;
-  if ((rc = arena_push(c, groups.glen.data(), groups.glen.size(), &dglen))) return rc;
-  if ((rc = arena_push(c, groups.members.data(), groups.members.size(), &dmembers))) return rc;
+  if ((rc = ab.add(groups.goff.data(), groups.goff.size(), &dgoff))) return rc;
+  if ((rc = ab.add(groups.glen.data(), groups.glen.size(), &dglen))) return rc;
+  if ((rc = ab.add(groups.members.data(), groups.members.size(), &dmembers))) return rc;
+  if ((rc = ab.commit())) return rc;
+  // The power sums of a start with stops, into c->norm2: those of the last start if that had the same shape, constant,
+  // aperture records and stop flags (paos_ctx::start_key), else the launch evaluates them and they are kept.  The key is
+  // set BEHIND the launches that fill the sums: a start that fails in between leaves no key at all (start_impl).
+  const bool memo = start_memo_on();
+  std::vector<double> key, pkey;
+  if (memo && (any_stop || want_power)) {
+    key.reserve(3 + (size_t)batch * (AP_STRIDE + 1));
+    key.push_back((double)shape); key.push_back(re); key.push_back(im);
+    key.insert(key.end(), aperture, aperture + (size_t)batch * AP_STRIDE);
+    key.insert(key.end(), flags.begin(), flags.end());
+  }
   bool power_found = false;
-  if (any_stop && (rc = start_power_find(c, shape, re, im, aperture, flags, &power_found))) return rc;
+  if (any_stop) {
+    power_found = memo && c->start_norm2 && same_key(key, c->start_key);
+    if (power_found) HIPCHK(c, hipMemcpyAsync(c->norm2, c->start_norm2, (size_t)batch * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    else c->start_key.clear();
+  }
+  // ... and the per-workgroup sums of the power of the start field inside its box: those of the last start with the same
+  // key, row windows, rounded column windows and sharing (paos_ctx::start_partial), else the launch evaluates them THERE
+  bool partial_found = false;
+  double* partial = c->partial;
+  if (want_power && memo) {
+    pkey = key;
+    pkey.insert(pkey.end(), write_rows, write_rows + (size_t)2 * batch);
+    pkey.insert(pkey.end(), wc.begin(), wc.end());
+    pkey.insert(pkey.end(), lead.begin(), lead.end());
+    pkey.insert(pkey.end(), same.begin(), same.end());
+    partial_found = c->start_partial && same_key(pkey, c->start_partial_key);
+    if (!partial_found) c->start_partial_key.clear();
+    if (!c->start_partial) HIPCHK(c, hipMalloc(&c->start_partial, (size_t)batch * c->nparts * sizeof(double)));
+    partial = c->start_partial;
+  }
   const dim3 block(kPwThreads), sweep(pw_blocks(c), batch), parts(c->nparts, batch);
   dispatch_layout(c, [&](auto t, auto br) {
     using T = decltype(t);
@@ -317,15 +344,28 @@ static int start_impl(paos_ctx* c, double re, double im, int shape, const double
                            dp, c->n, c->pitch, c->item_stride, re, im, (const double*)c->norm2, ds, drows, dcols, dgoff, dglen, dsubs,
                            dmembers, dzt, dzp, zk->param_stride, zk->nmax, zk->kdim);
       });
-      if (zk->power_ticket)
-        hipLaunchKernelGGL((start_norm2_partial_kernel<T, BRV, BC, S>), parts, block, 0, c->stream, c->partial, dp, c->n, c->pitch,
+      if (want_power && !partial_found)
+        hipLaunchKernelGGL((start_norm2_partial_kernel<T, BRV, BC, S>), parts, block, 0, c->stream, partial, dp, c->n, c->pitch,
                            c->item_stride, re, im, (const double*)c->norm2, ds, dlead, drows, dcols);
     });
   });
   HIPCHK(c, hipGetLastError());
-  if (any_stop && !power_found && (rc = start_power_keep(c))) return rc;
-  if (zk && zk->power_ticket) return take_power_ticket(c, c->partial, c->nparts, dsame, zk->power_ticket);
+  if (any_stop && !power_found && memo) {  // keep the sums just evaluated (c->norm2 is rewritten by every reduction)
+    if (!c->start_norm2) HIPCHK(c, hipMalloc(&c->start_norm2, (size_t)batch * sizeof(double)));
+    HIPCHK(c, hipMemcpyAsync(c->start_norm2, c->norm2, (size_t)batch * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    c->start_key = std::move(key);
+  }
+  if (want_power && !partial_found && memo) c->start_partial_key = std::move(pkey);
+  if (want_power) return take_power_ticket(c, partial, c->nparts, dsame, zk->power_ticket);
   return PAOS_OK;
+}
+
+// a start that fails keeps nothing: neither key may point at sums of another start, or at sums that were never written
+static int start_impl(paos_ctx* c, double re, double im, int shape, const double* aperture, const double* stop,
+                      const double* write_rows, const double* write_cols = nullptr, const StartZernike* zk = nullptr) {
+  const int rc = arena_settled(c, start_body(c, re, im, shape, aperture, stop, write_rows, write_cols, zk));
+  if (rc != PAOS_OK && c) start_forget(c);
+  return rc;
 }
 
 int paos_start(paos_ctx* c, double re, double im, int shape, const double* aperture, const double* stop) {
@@ -359,7 +399,7 @@ int paos_zero_outside_box(paos_ctx* c, const double* live_rows, const double* li
   int rc = check_rows(c, live_rows);
   if (rc) return rc;
   if (live_cols && (rc = check_rows(c, live_cols))) return rc;
-  return zero_outside_box(c, live_rows, live_cols);
+  return arena_settled(c, zero_outside_box(c, live_rows, live_cols));
 }
 
 int paos_zero_outside_rows(paos_ctx* c, const double* live_rows) { return paos_zero_outside_box(c, live_rows, nullptr); }
@@ -613,9 +653,12 @@ int zero_outside_box(paos_ctx* c, const double* live_rows, const double* live_co
   if (!live_cols) return zero_outside_rows(c, live_rows);
   const double *drows = nullptr, *dcols = nullptr;
   int rc;
-  if ((rc = arena_push(c, live_rows, (size_t)2 * c->batch, &drows))) return rc;
   const std::vector<double> lc = rounded_cols(c, live_cols);
-  if ((rc = arena_push(c, lc.data(), lc.size(), &dcols))) return rc;
+  // (no begin: inside a pass program the program's reservation holds these two as well)
+  ArenaBatch ab(c);
+  if ((rc = ab.add(live_rows, (size_t)2 * c->batch, &drows))) return rc;
+  if ((rc = ab.add(lc.data(), lc.size(), &dcols))) return rc;
+  if ((rc = ab.commit())) return rc;
   const dim3 grid(pw_blocks(c), c->batch), block(kPwThreads);
   dispatch_layout(c, [&](auto t, auto br) {
     using T = decltype(t);
@@ -643,10 +686,13 @@ static int norm2_enqueue_rows_impl(paos_ctx* c, const double* live_rows, const d
   if (rc) return rc;
   if ((rc = power_ring_full(c))) return rc;
   const double *drows = nullptr, *dlead = nullptr, *dsame = nullptr, *dcols = nullptr;
-  if ((rc = arena_push(c, live_rows, (size_t)2 * c->batch, &drows))) return rc;
+  const size_t nb = (size_t)c->batch;
+  ArenaBatch ab(c);
+  if ((rc = ab.begin((live_cols ? 2 : 1) * arena_rounded(2 * nb) + (same_as ? 2 : 0) * arena_rounded(nb)))) return rc;
+  if ((rc = ab.add(live_rows, 2 * nb, &drows))) return rc;
   if (live_cols) {
     const std::vector<double> lc = rounded_cols(c, live_cols);
-    if ((rc = arena_push(c, lc.data(), lc.size(), &dcols))) return rc;
+    if ((rc = ab.add(lc.data(), lc.size(), &dcols))) return rc;
   }
   if (same_as) {  // items whose fields the caller knows to be copies of another item's: summed once
     if (!same_as_valid(same_as, c->batch, true)) return fail(c, PAOS_EINVAL, "same_as must name an item that stands for itself");
@@ -658,9 +704,10 @@ static int norm2_enqueue_rows_impl(paos_ctx* c, const double* live_rows, const d
         return fail(c, PAOS_EINVAL, "items that share a sum must share their row (and column) window");
       lead[i] = j == i ? 1.0 : 0.0;
     }
-    if ((rc = arena_push(c, lead.data(), lead.size(), &dlead))) return rc;
-    if ((rc = arena_push(c, same_as, (size_t)c->batch, &dsame))) return rc;
+    if ((rc = ab.add(lead.data(), lead.size(), &dlead))) return rc;
+    if ((rc = ab.add(same_as, nb, &dsame))) return rc;
   }
+  if ((rc = ab.commit())) return rc;
   norm2_partial_launch(c, dlead, drows, dcols);
   HIPCHK(c, hipGetLastError());
   return take_power_ticket(c, c->partial, c->nparts, dsame, ticket);
@@ -672,18 +719,18 @@ int paos_norm2_enqueue_box(paos_ctx* c, const double* live_rows, const double* l
     int rc = check_rows(c, live_cols);
     if (rc) return rc;
   }
-  return norm2_enqueue_rows_impl(c, live_rows, same_as, ticket, live_cols);
+  return arena_settled(c, norm2_enqueue_rows_impl(c, live_rows, same_as, ticket, live_cols));
 }
 
 int paos_norm2_enqueue_rows(paos_ctx* c, const double* live_rows, int* ticket) {
   SETTLE_SCALE(c);
-  return norm2_enqueue_rows_impl(c, live_rows, nullptr, ticket);
+  return arena_settled(c, norm2_enqueue_rows_impl(c, live_rows, nullptr, ticket));
 }
 
 int paos_norm2_enqueue_rows_like(paos_ctx* c, const double* live_rows, const double* same_as, int* ticket) {
   SETTLE_SCALE(c);
   if (!same_as) return fail(c, PAOS_EINVAL, "null argument");
-  return norm2_enqueue_rows_impl(c, live_rows, same_as, ticket);
+  return arena_settled(c, norm2_enqueue_rows_impl(c, live_rows, same_as, ticket));
 }
 
 int paos_norm2(paos_ctx* c, double* host_out) {
@@ -753,8 +800,10 @@ int paos_phase_map_items(paos_ctx* c, const double* host_wfe, unsigned long long
     if (!phase_map_argument_finite(c->map_max, wl[k])) return fail(c, PAOS_EINVAL, kPhaseMapOverflow);
   const double *ditems = nullptr, *dwl = nullptr;
   int rc;
-  if ((rc = arena_push(c, items, (size_t)n_items, &ditems))) return rc;
-  if ((rc = arena_push(c, wl, (size_t)n_items, &dwl))) return rc;
+  ArenaBatch ab(c);
+  if ((rc = ab.begin(2 * arena_rounded((size_t)n_items)))) return rc;
+  if ((rc = ab.add(items, (size_t)n_items, &ditems)) || (rc = ab.add(wl, (size_t)n_items, &dwl)) || (rc = ab.commit()))
+    return arena_settled(c, rc);
   const dim3 grid(pw_blocks(c), n_items), block(kPwThreads);
   dispatch_layout(c, [&](auto t, auto br) {
     using T = decltype(t);
@@ -874,16 +923,19 @@ static int zernike_apply(paos_ctx* c, int nmax, int kdim, const double* table, c
   if (rc) return rc;
   if (use_pupil && !c->mask) return fail(c, PAOS_EINVAL, "no pupil defined (paos_pupil_aperture / paos_pupil_upload)");
   const double *dt = nullptr, *dp = nullptr;
-  rc = arena_push(c, table, (size_t)(nmax + 1) * kdim * 3, &dt);
-  if (rc) return rc;
-  rc = arena_push(c, params, (size_t)c->batch * param_stride, &dp);
-  if (rc) return rc;
   // groups of items with one wfe map: records equal in everything but the wavelength (and no per-item pupil)
   const ItemGroups g = map_groups(c->batch, params, param_stride, ZP_ENABLE, ZP_INV_WL, share_wfe_maps() && !use_pupil);
   const double *dgoff = nullptr, *dglen = nullptr, *dmembers = nullptr, *dtwins = nullptr;
-  if ((rc = arena_push(c, g.goff.data(), g.goff.size(), &dgoff))) return rc;
-  if ((rc = arena_push(c, g.glen.data(), g.glen.size(), &dglen))) return rc;
-  if ((rc = arena_push(c, g.members.data(), g.members.size(), &dmembers))) return rc;
+  const size_t nt = (size_t)(nmax + 1) * kdim * 3, np = (size_t)c->batch * param_stride;
+  ArenaBatch ab(c);
+  if ((rc = ab.begin(arena_rounded(nt) + arena_rounded(np) + arena_rounded(g.goff.size()) + arena_rounded(g.glen.size()) +
+                     arena_rounded(g.members.size()) + arena_rounded((size_t)c->batch))))
+    return rc;
+  if ((rc = ab.add(table, nt, &dt))) return rc;
+  if ((rc = ab.add(params, np, &dp))) return rc;
+  if ((rc = ab.add(g.goff.data(), g.goff.size(), &dgoff))) return rc;
+  if ((rc = ab.add(g.glen.data(), g.glen.size(), &dglen))) return rc;
+  if ((rc = ab.add(g.members.data(), g.members.size(), &dmembers))) return rc;
   if (same_as) {  // a group whose members all hold copies of one field reads the leader's (paos_zernike_like)
     if (!same_as_valid(same_as, c->batch, false)) return fail(c, PAOS_EINVAL, "same_as must hold item indices");
     std::vector<double> twins(c->batch, 0.0);
@@ -895,8 +947,9 @@ static int zernike_apply(paos_ctx* c, int nmax, int kdim, const double* table, c
       twins[i] = all ? 1.0 : 0.0;
       any = any || all;
     }
-    if (any && (rc = arena_push(c, twins.data(), twins.size(), &dtwins))) return rc;
+    if (any && (rc = ab.add(twins.data(), twins.size(), &dtwins))) return rc;
   }
+  if ((rc = ab.commit())) return rc;
   const dim3 grid(pw_blocks(c), c->batch), block(kPwThreads);
   double* wfe = host_wfe ? (double*)c->staging : nullptr;
   const double* pupil = use_pupil ? c->mask : nullptr;
@@ -941,21 +994,21 @@ int paos_zernike(paos_ctx* c, int nmax, int kdim, const double* table, const dou
                  int param_stride, double* host_wfe) {
   SETTLE_SCALE(c);
   if (c) (void)hipSetDevice(c->device);  // one process may drive several GPUs
-  return zernike_apply(c, nmax, kdim, table, params, param_stride, host_wfe, false);
+  return arena_settled(c, zernike_apply(c, nmax, kdim, table, params, param_stride, host_wfe, false));
 }
 
 int paos_zernike_like(paos_ctx* c, int nmax, int kdim, const double* table, const double* params,
                       int param_stride, const double* same_as, double* host_wfe) {
   SETTLE_SCALE(c);
   if (c) (void)hipSetDevice(c->device);
-  return zernike_apply(c, nmax, kdim, table, params, param_stride, host_wfe, false, same_as);
+  return arena_settled(c, zernike_apply(c, nmax, kdim, table, params, param_stride, host_wfe, false, same_as));
 }
 
 int paos_zernike_pupil(paos_ctx* c, int nmax, int kdim, const double* table, const double* params,
                        int param_stride, double* host_wfe) {
   SETTLE_SCALE(c);
   if (c) (void)hipSetDevice(c->device);
-  return zernike_apply(c, nmax, kdim, table, params, param_stride, host_wfe, true);
+  return arena_settled(c, zernike_apply(c, nmax, kdim, table, params, param_stride, host_wfe, true));
 }
 
 static int ensure_pupil(paos_ctx* c) {
@@ -1031,10 +1084,12 @@ int paos_zernike_gram(paos_ctx* c, int nmax, int kdim, const double* table, cons
   }
   const double *dt = nullptr, *dp = nullptr, *dslots = nullptr, *dfac = nullptr;
   int rc;
-  if ((rc = arena_push(c, table, ncoef * 3, &dt))) return rc;
-  if ((rc = arena_push(c, params, (size_t)c->batch * param_stride, &dp))) return rc;
-  if ((rc = arena_push(c, slots.data(), slots.size(), &dslots))) return rc;
-  if ((rc = arena_push(c, fac.data(), fac.size(), &dfac))) return rc;
+  ArenaBatch ab(c);
+  if ((rc = ab.begin(arena_rounded(ncoef * 3) + arena_rounded((size_t)c->batch * param_stride) + arena_rounded(slots.size()) + arena_rounded(fac.size()))))
+    return rc;
+  if ((rc = ab.add(table, ncoef * 3, &dt)) || (rc = ab.add(params, (size_t)c->batch * param_stride, &dp)) ||
+      (rc = ab.add(slots.data(), slots.size(), &dslots)) || (rc = ab.add(fac.data(), fac.size(), &dfac)) || (rc = ab.commit()))
+    return arena_settled(c, rc);
   const int nvals = K * (K + 1) / 2 + 1;
   const size_t chunks = ((size_t)c->item_stride + kGramPix - 1) / kGramPix;
   const int nblocks = (int)(chunks < 512 ? chunks : 512);

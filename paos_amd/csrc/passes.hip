@@ -156,8 +156,15 @@ struct FusedGroup {
 // a fused group always does), point their slots at tables of the context's store, copy the item records of all of them to
 // the device in ONE transfer and build all tables with ONE launch -- in front of the program's first launch, so that
 // nothing but the pass kernels themselves stands between two passes (round 4: a copy and a table launch in front of
-// every pass cost ~50 us of an 1.3 ms launch).  *ditems: the device array; groups[g].item_base indexes it.
-int stage_groups(paos_ctx* c, std::vector<FusedGroup>& groups, const FrugalItem** ditems) {
+// every pass cost ~50 us of an 1.3 ms launch).  The records join the caller's batch `ab` (round 17: the block table and the
+// renderings' vectors of a program travel in the same transfer); the table launch, launch_staged_tables, follows the
+// batch's commit.  st->items: the device array; groups[g].item_base indexes it.
+struct StagedTables {
+  const FrugalItem* items = nullptr;
+  const PhaseSlotDesc* descs = nullptr;
+  unsigned count = 0;  // table descriptors: slots with phases
+};
+int stage_groups(paos_ctx* c, ArenaBatch& ab, std::vector<FusedGroup>& groups, StagedTables* st) {
   std::vector<FrugalItem> blob;
   std::vector<PhaseSlotDesc> descs;
   int slots = 0;
@@ -205,15 +212,19 @@ int stage_groups(paos_ctx* c, std::vector<FusedGroup>& groups, const FrugalItem*
   std::memcpy(flat.data(), blob.data(), item_doubles * sizeof(double));
   if (!descs.empty()) std::memcpy(flat.data() + item_doubles, descs.data(), descs.size() * sizeof(PhaseSlotDesc));
   const double* dflat = nullptr;
-  int rc = arena_push(c, flat.data(), flat.size(), &dflat);
+  int rc = ab.add(flat.data(), flat.size(), &dflat);
   if (rc) return rc;
-  *ditems = reinterpret_cast<const FrugalItem*>(dflat);
-  if (!descs.empty()) {
-    const PhaseTableArgs ta{*ditems, reinterpret_cast<const cx<double>*>(c->tw), reinterpret_cast<const PhaseSlotDesc*>(dflat + item_doubles), c->n,
-                            c->precision == PAOS_F64 ? 0 : 1};
-    hipLaunchKernelGGL(phase_table_kernel<0>, dim3(c->n / 256, c->batch, (unsigned)descs.size()), dim3(256), 0, c->stream, ta);
-    HIPCHK(c, hipGetLastError());
-  }
+  st->items = reinterpret_cast<const FrugalItem*>(dflat);
+  st->descs = reinterpret_cast<const PhaseSlotDesc*>(dflat + item_doubles);
+  st->count = (unsigned)descs.size();
+  return PAOS_OK;
+}
+// the tables of what stage_groups staged, behind the commit of its batch
+int launch_staged_tables(paos_ctx* c, const StagedTables& st) {
+  if (st.count == 0) return PAOS_OK;
+  const PhaseTableArgs ta{st.items, reinterpret_cast<const cx<double>*>(c->tw), st.descs, c->n, c->precision == PAOS_F64 ? 0 : 1};
+  hipLaunchKernelGGL(phase_table_kernel<0>, dim3(c->n / 256, c->batch, st.count), dim3(256), 0, c->stream, ta);
+  HIPCHK(c, hipGetLastError());
   return PAOS_OK;
 }
 
@@ -281,10 +292,12 @@ int launch_lowered(paos_ctx* c, const paos_pass& p, LoweredPass& lp, const doubl
     g.lp[0] = &lp; g.lp[1] = next; g.lp[2] = next2; g.count = next2 ? 3 : (next ? 2 : 1);
     g.axis = p.axis;
     std::vector<FusedGroup> one{g};
-    int rcg = stage_groups(c, one, &ditems_f);
-    if (rcg) return rcg;
+    ArenaBatch ab(c);  // (inside the program's reservation: no begin)
+    StagedTables st;
+    int rcg = stage_groups(c, ab, one, &st);
+    if (rcg || (rcg = ab.commit()) || (rcg = launch_staged_tables(c, st))) return rcg;
     tables = one[0].tables;
-    ditems_f += one[0].item_base;
+    ditems_f = st.items + one[0].item_base;
   }
   const double* ditems = reinterpret_cast<const double*>(ditems_f);
   FrugalArgs a{c->field, c->tw, reinterpret_cast<const FrugalItem*>(ditems), c->pitch, c->item_stride, nullptr, nullptr, nullptr};
@@ -452,9 +465,13 @@ int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const do
   // ... and two table descriptors (stage_groups)
   const size_t per_pass = (((size_t)c->batch * sizeof(FrugalItem) / sizeof(double) + 15) & ~size_t(15)) +
                           (((size_t)c->batch + 15) & ~size_t(15)) + 16;
-  int rc = arena_reserve(c, (size_t)n_blocks * c->batch * FP_STRIDE + 16 + (size_t)n_passes * per_pass);
+  // ... and the two windows of zero_outside_box.  Round 17: the block table, the vectors of the batched renderings and the
+  // staged records are ONE batch, copied once in front of the program's first launch that reads any of them; whatever is
+  // pushed launch by launch behind that (arena_push: a copy of its own) still lies inside this reservation.
+  ArenaBatch ab(c);
+  int rc = ab.begin((size_t)n_blocks * c->batch * FP_STRIDE + 16 + (size_t)n_passes * per_pass + 2 * arena_rounded((size_t)2 * c->batch));
   if (rc) return rc;
-  rc = arena_push(c, blocks, (size_t)n_blocks * c->batch * FP_STRIDE, &dblocks);
+  rc = ab.add(blocks, (size_t)n_blocks * c->batch * FP_STRIDE, &dblocks);
   if (rc) return rc;
   // Lower every pass for the frugal kernels first; when the whole program runs on them, plan the
   // pruning of dead lines across it (look-ahead), then launch.
@@ -595,6 +612,7 @@ int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const do
   // launch per shape, in front of the first pass -- when every rendering goes to a set no EARLIER pass of this program
   // reads (always, unless a program carries more distinct apertures than there are sets; then each is rendered in place,
   // right before its pass).  PAOS_BATCHED_RECORDS=0: in place, one launch per aperture, as before.
+  std::vector<MaskRender> renderings;
   {
     static const bool want = !env_is("PAOS_BATCHED_RECORDS", '0');
     std::vector<int> todo;
@@ -606,18 +624,13 @@ int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const do
         todo.push_back(q);
       }
     }
-    if (safe && todo.size() > 1) {
-      for (size_t at = 0; at < todo.size(); at += kMaskRenders) {
-        MaskRender jobs[kMaskRenders];
-        const int count = (int)std::min<size_t>(kMaskRenders, todo.size() - at);
-        for (int j = 0; j < count; ++j) {
-          LoweredPass& lp = low[todo[at + j]];
-          const double* dshared = nullptr;
-          if ((rc = arena_push(c, lp.mask_shared.data(), lp.mask_shared.size(), &dshared))) return rc;
-          jobs[j] = mask_job(c, passes[todo[at + j]], lp, dblocks + (size_t)lp.mask_block * c->batch * FP_STRIDE, dshared);
-          lp.mask_render = false;
-        }
-        if ((rc = render_mask_records(c, jobs, count))) return rc;
+    if (safe && todo.size() > 1) {  // (launched below, behind the commit)
+      for (int q : todo) {
+        LoweredPass& lp = low[q];
+        const double* dshared = nullptr;
+        if ((rc = ab.add(lp.mask_shared.data(), lp.mask_shared.size(), &dshared))) return rc;
+        renderings.push_back(mask_job(c, passes[q], lp, dblocks + (size_t)lp.mask_block * c->batch * FP_STRIDE, dshared));
+        lp.mask_render = false;
       }
     }
   }
@@ -627,6 +640,7 @@ int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const do
   std::vector<FusedGroup> groups;
   std::vector<int> group_of(n_passes, -1);
   const FrugalItem* staged_items = nullptr;
+  StagedTables staged;
   {
     for (int q = 0; q < n_passes;) {
       FusedGroup g;
@@ -646,9 +660,17 @@ int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const do
     // (a table per operator slot of every pass: 2 MiB each at 4096^2 x 32; a program that would need more than 1 GiB of
     // them -- hundreds of passes -- stages launch by launch, on six tables)
     const size_t table_bytes = (size_t)2 * n_passes * c->batch * c->n * sizeof(cx<double>);
-    if (all_frugal && !env_is("PAOS_STAGE_PROGRAM", '0') && table_bytes <= (size_t(1) << 30))
-      if ((rc = stage_groups(c, groups, &staged_items))) return rc;
+    if (all_frugal && !env_is("PAOS_STAGE_PROGRAM", '0') && table_bytes <= (size_t(1) << 30)) {
+      if ((rc = stage_groups(c, ab, groups, &staged))) return rc;
+      staged_items = staged.items;
+    }
   }
+  // THE copy of the program, in front of its first launch that reads a block: the record renderings, the table kernel, or
+  // the first pass.  (What ran above -- a settled stop scale, zeroed windows -- reads none of this batch.)
+  if ((rc = ab.commit())) return rc;
+  for (size_t at = 0; at < renderings.size(); at += kMaskRenders)
+    if ((rc = render_mask_records(c, renderings.data() + at, (int)std::min<size_t>(kMaskRenders, renderings.size() - at)))) return rc;
+  if ((rc = launch_staged_tables(c, staged))) return rc;
   // Walk the program in chunks whose phase operators fit the table store: fill the tables of
   // a chunk with one small launch, then run its passes.
   int i = 0;
@@ -728,7 +750,7 @@ int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const do
 
 int run_passes(paos_ctx* c, const paos_pass* passes, int n_passes, const double* blocks, int n_blocks, const double* entry_rows,
                bool entry_stale, int* final_ticket, int final_mode, const double* entry_cols) {
-  const int rc = run_passes_impl(c, passes, n_passes, blocks, n_blocks, entry_rows, entry_stale, final_ticket, final_mode, entry_cols);
+  const int rc = arena_settled(c, run_passes_impl(c, passes, n_passes, blocks, n_blocks, entry_rows, entry_stale, final_ticket, final_mode, entry_cols));
   if (rc != PAOS_OK && c) forget_mask_sets(c);  // a program that stopped half way: which records were rendered is moot
   return rc;
 }
