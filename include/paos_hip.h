@@ -446,6 +446,16 @@ int paos_record_set_stats(paos_ctx* ctx, unsigned long long* found, unsigned lon
  * the ordinary build (*plain).  PAOS_CENTRAL_HALF=0 / 1 in the environment when the context is created switches the
  * central-half builds off / on; results are equal as numbers either way. */
 int paos_central_half_stats(paos_ctx* ctx, unsigned long long* central, unsigned long long* plain);
+/* Test aid, host only (no context): is there a build of the frugal pass kernel of this name in the family (precision, n)?
+ * `record`: the nine fields of a build's name -- axis, kpre, kmid, nfft, store, tab, fuse, one_line, central.  1 / 0; a field out
+ * of its range names no build (0).  The families are complex128 at 1024, 2048 and 4096 and complex64 at 2048 and 4096: any other
+ * (precision, n), or a null record, gives -PAOS_EINVAL (negative, since PAOS_EINVAL itself is 1). */
+int paos_frugal_built(int precision, int n, const int* record);
+/* Test aid: the builds the frugal launches of the context's most recent pass program took (paos_run_passes and its kin, also
+ * the programs behind paos_ptp / paos_stw / paos_wts), nine ints per launch in the order above, in launch order -- what each launch
+ * handed to its family after the one-line and central-half decisions.  Launches of the generic kernel log nothing; the log is
+ * cleared where a program begins.  *count: launches logged; at most `capacity` records are written (capacity 0: count only). */
+int paos_pass_builds(paos_ctx* ctx, int* records, int capacity, int* count);
 /* Test aid: what became of the factors paos_stop_defer_last_power left pending, since the context was created: *rode
  * counts those the first pass of the next pass program multiplied into its middle slot, *settled those applied by the
  * scaling sweep (or dropped, where the field was about to be overwritten) because something else came first.  A test

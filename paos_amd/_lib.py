@@ -105,6 +105,8 @@ SYMBOLS = {
     "paos_copy_yardstick": (ctypes.c_int, [_c_ctx, ctypes.c_int, _dbl_p, _dbl_p]),
     "paos_record_set_stats": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
     "paos_central_half_stats": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
+    "paos_frugal_built": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "paos_pass_builds": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "paos_deferred_stop_stats": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
     "paos_ctx_set_pruning": (ctypes.c_int, [_c_ctx, ctypes.c_int]),
     "paos_run_passes_live": (ctypes.c_int, [_c_ctx, ctypes.POINTER(Pass), ctypes.c_int, _dbl_p, ctypes.c_int, _dbl_p]),
@@ -182,6 +184,22 @@ def as_blocks(blocks, batch, stride):
     if arr.shape != (batch, stride):
         raise ValueError(f"expected parameter blocks of shape {(batch, stride)}, got {arr.shape}")
     return arr
+
+
+BUILD_FIELDS = ("axis", "kpre", "kmid", "nfft", "store", "tab", "fuse", "one_line", "central")  # FrugalBuild of csrc/host.h
+
+
+def frugal_built(precision, n, record):
+    """Is there a build of the frugal pass kernel named ``record`` (nine ints, BUILD_FIELDS) in the family (precision, n)?
+    Host only.  ValueError for a (precision, n) that is no family."""
+    if len(record) != len(BUILD_FIELDS):
+        raise ValueError("a build record has nine fields")
+    rec = (ctypes.c_int * 9)(*[int(v) for v in record])
+    code = {"fp64": PAOS_F64, "fp32": PAOS_F32}.get(precision, -1)
+    rc = load().paos_frugal_built(code, int(n), rec)
+    if rc < 0:
+        raise ValueError(f"no family of pass-kernel builds for {precision} at n = {n}")
+    return bool(rc)
 
 
 def zoom_check(size, oversample, n):
@@ -749,6 +767,16 @@ class DeviceFields:
         self._check(self._lib.paos_central_half_stats(self._ctx, ctypes.byref(central), ctypes.byref(plain)),
                     "paos_central_half_stats")
         return int(central.value), int(plain.value)
+
+    def pass_builds(self, capacity=64):
+        """The build records (tuples of nine ints, BUILD_FIELDS) of the frugal launches of the most recent pass program, in
+        launch order; launches of the generic kernel are not listed."""
+        count = ctypes.c_int(0)
+        buf = (ctypes.c_int * (9 * capacity))()
+        self._check(self._lib.paos_pass_builds(self._ctx, buf, capacity, ctypes.byref(count)), "paos_pass_builds")
+        if count.value > capacity:
+            return self.pass_builds(count.value)
+        return [tuple(buf[9 * i:9 * i + 9]) for i in range(count.value)]
 
     def deferred_stop_stats(self):
         """(rode, settled): deferred stop factors (``make_stop(power_known=True, defer=True)``) that went into the first pass

@@ -192,6 +192,7 @@ struct paos_ctx {
   // context, so that a test can hold an "on" and an "off" context in one process.  (On by default: profiles/r11_central_half.md.)
   bool central_half = true;
   unsigned long long central_launches = 0, plain_launches = 0;  // frugal pass launches on CH / ordinary builds (paos_central_half_stats)
+  std::vector<int> pass_builds;  // the FrugalBuild of every frugal launch of the most recent pass program, nine ints each (paos_pass_builds)
   int* mask_overflow = nullptr;    // device counter: partial runs that did not fit (must stay 0)
   double* partial = nullptr;
   double* norm2 = nullptr;

@@ -354,9 +354,13 @@ int launch_lowered(paos_ctx* c, const paos_pass& p, LoweredPass& lp, const doubl
   const FrugalBuild b = pick_build(c, p.axis, lp, next, next2, tables, store_psf ? 1 : (sum_power ? 2 : 0));
   // PAOS_DUMP_PASSES=1: on stderr, the build the launch takes and one line per pass it runs (what item 0's two slots carry)
   static const bool dump = env_is("PAOS_DUMP_PASSES", '1');
+  {  // paos_pass_builds: the record the family function gets, in launch order
+    const int rec[9] = {b.axis, b.kpre, b.kmid, b.nfft, b.store, b.tab, b.fuse, b.one_line, b.central};
+    c->pass_builds.insert(c->pass_builds.end(), rec, rec + 9);
+  }
   if (dump) {
-    std::fprintf(stderr, "build axis %d kpre %d kmid %d nfft %d store %d tab %d fuse %d one_line %d central %d\n", b.axis, b.kpre, b.kmid, b.nfft,
-                 b.store, b.tab, b.fuse, b.one_line, b.central);
+    std::fprintf(stderr, "build axis %d kpre %d kmid %d nfft %d store %d tab %d fuse %d one_line %d central %d n %d %s\n", b.axis, b.kpre, b.kmid,
+                 b.nfft, b.store, b.tab, b.fuse, b.one_line, b.central, c->n, c->precision == PAOS_F64 ? "fp64" : "fp32");
     for (const LoweredPass* l : {(const LoweredPass*)&lp, (const LoweredPass*)next, (const LoweredPass*)next2}) {
       if (!l || l->items.empty()) continue;
       const FrugalItem& f = l->items[0];  // ("+pass": rides in the launch of the pass above it)
@@ -433,6 +437,7 @@ bool use_pruning() {
 // the field the program ends with, not the field.
 int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const double* blocks, int n_blocks,
                     const double* entry_rows, bool entry_stale, int* final_ticket, int final_mode, const double* entry_cols) {
+  if (c) c->pass_builds.clear();  // (paos_pass_builds: the launches of THIS program)
   if (!c || !passes || !blocks || n_passes < 0 || n_blocks < 1) return fail(c, PAOS_EINVAL, "bad pass program");
   c->norm2_of_field = false;  // (set again at the end when the last pass sums the power of what it stores)
   // A program that ends on the PSF gives the field up for it: the free power-ticket slot it will need is checked
@@ -843,6 +848,28 @@ int paos_run_program(paos_ctx* c, const paos_pass* passes, int n_passes, const d
   return run_passes(c, passes, n_passes, blocks, n_blocks, opts->live_rows, stale,
                     opts->final_intensity ? opts->power_ticket : nullptr, opts->final_intensity == 2 ? 2 : 1,
                     stale ? opts->live_cols : nullptr);
+}
+
+int paos_frugal_built(int precision, int n, const int* record) {
+  if (!record) return -PAOS_EINVAL;  // (negative: PAOS_EINVAL itself is 1, "built")
+  const FrugalBuild b{record[0], record[1], record[2], record[3], record[4], record[5], record[6], record[7], record[8]};
+  if (precision == PAOS_F64) {
+    if (n == 1024) return frugal_built<double, 1024>(b) ? 1 : 0;
+    if (n == 2048) return frugal_built<double, 2048>(b) ? 1 : 0;
+    if (n == 4096) return frugal_built<double, 4096>(b) ? 1 : 0;
+  } else if (precision == PAOS_F32) {
+    if (n == 2048) return frugal_built<float, 2048>(b) ? 1 : 0;
+    if (n == 4096) return frugal_built<float, 4096>(b) ? 1 : 0;
+  }
+  return -PAOS_EINVAL;
+}
+
+int paos_pass_builds(paos_ctx* c, int* records, int capacity, int* count) {
+  if (!c || !count || capacity < 0 || (capacity > 0 && !records)) return fail(c, PAOS_EINVAL, "bad pass-builds request");
+  const int have = (int)(c->pass_builds.size() / 9);
+  *count = have;
+  if (have > 0 && capacity > 0) std::memcpy(records, c->pass_builds.data(), (size_t)(have < capacity ? have : capacity) * 9 * sizeof(int));
+  return PAOS_OK;
 }
 
 int paos_phase(paos_ctx* c, const double* params, int mul2pi) {
