@@ -120,9 +120,8 @@ __device__ __forceinline__ cx<float> scale2(cx<float> v, float p, float q) { ret
 // n (the difference needs <= 34 bits), the later steps round at 1e-16 of |r| <= 1, and the
 // three-term pi/2 is good to 8.5e-32 * n, so the result is ~1 ulp for |a| up to 2^40
 // (the rounding trick below needs |a * 2/pi| < 2^51); the
-// library validates on the host that no phase argument exceeds kMaxPhaseArg (passes.hip: run_passes_impl)
+// library validates on the host that no phase argument exceeds kMaxPhaseArg (pass_records.h; pass_program.h: check_phase_args)
 // so the kernels carry no Payne-Hanek fallback.  ~45 instructions, branch-free.
-constexpr double kMaxPhaseArg = 1.0e12;
 __device__ __forceinline__ void sincos_fast(double a, double* sn, double* cs) {
   // round(a * 2/pi) by the 1.5 * 2^52 trick: the integer lands in the low mantissa bits, so its
   // two low bits (the quadrant) are read straight from the register, no conversion

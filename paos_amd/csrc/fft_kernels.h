@@ -16,6 +16,7 @@
 // rounded argument -- up to 1e6 rad -- is bit-identical to NumPy's.
 #pragma once
 #include "fft_core.h"
+#include "pass_records.h"
 
 namespace paos {
 
@@ -35,9 +36,7 @@ enum : int { PWF_MUL2PI = 1,   // argument gets an extra factor 2 pi (lens form,
 // Bits 8.. of PwOp::flags: 1 + index of this operator's separable phase table (0 = no table:
 // the phase is evaluated per pixel with sincos).
 constexpr int kTableShift = 8;
-enum : int { FP_ENABLE = 0, FP_SX = 1, FP_SY = 2, FP_COEF = 3, FP_SGN = 4, FP_STRIDE = 5 };
-// FFT control block: [enable, inverse, -, -, -]
-enum : int { FC_ENABLE = 0, FC_INVERSE = 1 };
+// (the layout of a parameter block, FP_*, and of an FFT control block, FC_*: pass_records.h)
 constexpr int kMaxPw = 6;
 
 struct PwOp {

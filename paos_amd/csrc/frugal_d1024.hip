@@ -1,4 +1,5 @@
 // frugal_d1024.hip -- the frugal pass kernels of 1024^2 complex128.
 #include "frugal_launch.h"
 
-int paos_frugal_d1024(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a) { return frugal_dispatch<double, 1024>(c, b, a); }
+template <>
+int frugal_family<double, 1024>(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a) { return frugal_dispatch<double, 1024>(c, b, a); }

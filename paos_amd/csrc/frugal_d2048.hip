@@ -1,4 +1,5 @@
 // frugal_d2048.hip -- the frugal pass kernels of 2048^2 complex128.
 #include "frugal_launch.h"
 
-int paos_frugal_d2048(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a) { return frugal_dispatch<double, 2048>(c, b, a); }
+template <>
+int frugal_family<double, 2048>(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a) { return frugal_dispatch<double, 2048>(c, b, a); }

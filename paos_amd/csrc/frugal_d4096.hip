@@ -1,4 +1,5 @@
 // frugal_d4096.hip -- the frugal pass kernels of 4096^2 complex128.
 #include "frugal_launch.h"
 
-int paos_frugal_d4096(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a) { return frugal_dispatch<double, 4096>(c, b, a); }
+template <>
+int frugal_family<double, 4096>(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a) { return frugal_dispatch<double, 4096>(c, b, a); }

@@ -1,4 +1,5 @@
 // frugal_f4096.hip -- the frugal pass kernels of 4096^2 complex64.
 #include "frugal_launch.h"
 
-int paos_frugal_f4096(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a) { return frugal_dispatch<float, 4096>(c, b, a); }
+template <>
+int frugal_family<float, 4096>(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a) { return frugal_dispatch<float, 4096>(c, b, a); }

@@ -1,41 +1,12 @@
-// frugal_launch.h -- from the name of a build of the frugal pass kernel (host.h: FrugalBuild) to its launch: which names have
-// a build (frugal_built), what a build's workgroup looks like (FrugalGeometry), the launch (frugal_launch) and the step from
+// frugal_launch.h -- from the name of a build of the frugal pass kernel (pass_records.h: FrugalBuild; frugal_built says which
+// names have a build) to its launch: what a build's workgroup looks like (FrugalGeometry), the launch (frugal_launch) and the step from
 // the run-time record to the template arguments (frugal_dispatch).  Each frugal_<family>.hip instantiates frugal_dispatch for
 // one (type, N) and nothing else.
 #pragma once
 #include "host.h"
+#include "pass_records.h"
 
-#ifndef PAOS_LONG_ONE_LINE
-#define PAOS_LONG_ONE_LINE 1
-#endif
-#ifndef PAOS_SINGLE_ONE_LINE
-#define PAOS_SINGLE_ONE_LINE 1   // 0 (A/B builds): single table passes keep the two-line workgroups whatever they load and store
-#endif
-
-// Which builds exist of the family (T, N): THE statement of it -- frugal_dispatch instantiates a kernel exactly where this
-// holds, and pick_build (passes.hip) asks here before it names a one-line or a central-half build.
-//   evaluating slots (tab = 0): any number of phases per slot; the PSF store where both slots have at most one (what a chain
-//     can end on: the last column pass of a separable program usually has the column half of a phase in front of its first
-//     transform), field + power where the first has at most one (what a program that ends on a saved surface ends with);
-//   table slots (tab = 1): one build for any number of phases per slot (kpre, kmid = 1: "has phases"), any store;
-//   fused launches (fuse = 1 .. 4): table slots with phases in both, behind a two-transform pass, any store;
-//   one-line workgroups (one_line = 1, round 5): field-storing single table passes of complex128 at 4096^2 and 2048^2;
-//   central half (central = 1, round 11; frugal_pass.h: frugal_pass_kernel, CH): 4096^2 complex128 table slots with kpre = 1, on
-//     the one-line workgroups -- the field-storing fused launches and the one-line single passes.  The PSF-storing fused build
-//     (two-line workgroups; the last column launch of a step loads a quarter too) was built and measured as well: 0.97 ->
-//     1.10 ms per launch, so it keeps the ordinary build (profiles/r11_central_half.md).
-template <typename T, int N>
-constexpr bool frugal_built(const FrugalBuild& b) {
-  constexpr bool kOneLineSizes = sizeof(T) == 8 && (N == 4096 || N == 2048) && PAOS_LONG_ONE_LINE != 0;
-  if (b.axis < 0 || b.axis > 1 || b.kpre < 0 || b.kpre > kFrugalMaxPre || b.kmid < 0 || b.kmid > kFrugalMaxMid) return false;
-  if (b.nfft < 1 || b.nfft > 2 || b.store < 0 || b.store > 2 || b.fuse < 0 || b.fuse > 4) return false;
-  if ((b.tab | b.one_line | b.central) & ~1) return false;
-  if (b.one_line && !(kOneLineSizes && PAOS_SINGLE_ONE_LINE != 0 && b.tab && !b.fuse && b.store == 0)) return false;
-  if (b.central && !(kOneLineSizes && N == 4096 && b.tab && b.kpre == 1 && b.store == 0 && (b.fuse || b.one_line))) return false;
-  if (b.fuse) return b.tab && b.kpre == 1 && b.kmid == 1 && b.nfft == 2;
-  if (b.tab) return b.kpre <= 1 && b.kmid <= 1 && b.kpre + b.kmid > 0;
-  return b.store == 0 || (b.kpre <= 1 && (b.store == 2 || b.kmid <= 1));
-}
+// (which names have a build: frugal_built<T, N>, with PAOS_LONG_ONE_LINE / PAOS_SINGLE_ONE_LINE, in pass_records.h)
 
 // ... what a launch of a name without a build fails with
 inline int frugal_not_built(paos_ctx* c, const FrugalBuild& b) {
@@ -114,8 +85,9 @@ constexpr int kFrugalFieldMax[] = {1, kFrugalMaxPre, kFrugalMaxMid, 2, 2, 1, 4, 
 template <typename T, int N, int X, int... V>
 int frugal_unfold(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a) {
   constexpr int I = sizeof...(V), kFields = sizeof(kFrugalFieldMax) / sizeof(int);
-  static_assert(sizeof(FrugalBuild) == kFields * sizeof(int), "one maximum per field");
-  const int field[] = {b.axis, b.kpre, b.kmid, b.nfft, b.store, b.tab, b.fuse, b.one_line, b.central};
+  static_assert(kFields == kBuildFields, "one maximum per field");
+  int field[kBuildFields];
+  build_to_ints(b, field);
   if (field[I] != X) {
     if constexpr (X < kFrugalFieldMax[I]) return frugal_unfold<T, N, X + 1, V...>(c, b, a);
     else return frugal_not_built(c, b);

@@ -13,6 +13,7 @@
 // what pushes the generic interpreter to ~230 VGPRs (profiles/r01_vgpr_experiments.txt).
 #pragma once
 #include "fft_kernels.h"
+#include "pass_records.h"
 
 #ifndef PAOS_FENCE_EVERY
 #define PAOS_FENCE_EVERY 2
@@ -20,56 +21,7 @@
 
 namespace paos {
 
-constexpr int kFrugalMaxPre = 2, kFrugalMaxMid = 3;
-
-struct FrugalPhase {
-  double sx, sy, coef, sgn, m2, natural;  // natural != 0: np.fft.fftfreq index order
-};
-// A convex aperture along one line (a row for row passes, a column for column passes):
-//   pos < p0: w_out | p0 <= pos < p1: vals[pos-p0] | p1 <= pos < p2: w_in |
-//   p2 <= pos < p3: vals[kMaskW + pos-p2] | pos >= p3: w_out          (times the line factor lm)
-// rendered by mask_lines_kernel (pointwise.h) with the same per-pixel functions the stand-alone
-// aperture kernel uses, so values and the {0, partial, 1} classification are identical.
-constexpr int kMaskW = 192;  // longest partial run per side the records can hold
-struct MaskLine {
-  int p0, p1, p2, p3;
-  double lm;  // line multiplier (rectangles: the separable count of the other axis / 32)
-  double pad;
-};
-struct FrugalSlot {
-  double sign_on, scale;
-  double mask_on, w_in, w_out;   // aperture riding on this slot (0/1), interior / exterior weight
-  const MaskLine* lines;          // [N] records of THIS item for the pass axis
-  const double* vals;             // [N][2 * kMaskW]
-  // Round 4 (complex128): when every phase of the slot varies ALONG the line only -- the row / column factors of the
-  // separable pass programs -- its factor is the same on every line of the pass: [N] factors of THIS item by position,
-  // filled by phase_table_kernel right before the pass with the arithmetic of frugal_slot (slot_factor) and read back
-  // instead of being evaluated 16 times per thread on each of a thousand lines.  nullptr: the slot evaluates.
-  const cx<double>* table;
-};
-static_assert(sizeof(FrugalSlot) == 8 * sizeof(double), "record of 8-byte fields");
-// per-item record, doubles: [fft1_on, fft1_inv, fft2_on, fft2_inv, pruning ranges, pre slot, pre phases[2],
-// mid slot, mid phases[3]]
-struct FrugalItem {
-  double active;  // 0: the item takes no part in this pass (no load, no store)
-  double fft1_on, fft1_inv, fft2_on, fft2_inv;
-  // Pruning (zero lines of a field stay zero under every operator of a pass, and a transform of a
-  // zero line is a zero line): the host tracks which rows / columns an aperture has just zeroed.
-  //   lines outside [line_lo, line_hi) come out zero: tiles made of such lines only are not
-  //     processed -- written with zeros when line_fill != 0, otherwise left alone because the next
-  //     pass (along the other axis) will not read them;
-  //   positions along a line outside [pos_lo, pos_hi) are known to be zero (and may hold stale
-  //     data): they are not loaded.
-  // Full ranges [0, N) switch all of it off.  Bounds are multiples of the block height.
-  double line_lo, line_hi, line_fill, pos_lo, pos_hi;
-  // positions along a line outside [spos_lo, spos_hi) need not be STORED: the next pass (along the other axis)
-  // does not process the tiles of those lines -- an aperture in it is about to zero them
-  double spos_lo, spos_hi;
-  FrugalSlot pre;
-  FrugalPhase pre_ph[kFrugalMaxPre];
-  FrugalSlot mid;
-  FrugalPhase mid_ph[kFrugalMaxMid];
-};
+// (the records of a pass -- FrugalPhase, MaskLine, FrugalSlot, FrugalItem -- and kFrugalMaxPre / Mid, kMaskW: pass_records.h)
 
 // table entries the stage twiddles can address: the base twiddle of a stage is tw[k N / (NS R)] with
 // k < NS, i.e. an index below N / R <= N / 4; with 16 points per thread every supported N stays below 256,
@@ -537,9 +489,7 @@ __device__ __forceinline__ void frugal_slot(cx<T>* v, const FrugalSlot& sl, cons
 // blockIdx = (position / 256, item, table) -- the tables of every launch of a pass program in one go --, complex128 passes.  The unit circle of sincos_tab is rebuilt from
 // the context's twiddle table exactly as frugal_pass_kernel builds it, the arguments are formed by slot_factor: an entry
 // is bit for bit what the slot would have evaluated at that position on any line.
-// One table: the slot (`mid` = 0: in front of the first transform, 1: behind it) of the pass whose item records start at
-// items[item_base], with `k` phases, along `axis`.
-struct PhaseSlotDesc { int item_base, mid, k, axis; };
+// One table: a PhaseSlotDesc (pass_records.h).
 struct PhaseTableArgs {
   const FrugalItem* items;     // the staged records of every launch the tables are for (passes.hip: stage_groups)
   const cx<double>* tw;        // the context's twiddle table for n

@@ -1,11 +1,12 @@
 // host.h -- what the translation units of libpaoship share (internal; the C ABI is include/paos_hip.h).
 //
 // The host side of the library is split by what it launches: context.hip (contexts, the parameter arena, errors,
-// the launch timer), pass_plan.hip and passes.hip (pass programs), generic_pass.hip and frugal_<family>.hip (the pass
-// kernels), paos_hip.hip (the pointwise entry points: every kernel of pointwise.h) and the products: focus_otf.hip, zoom.hip,
+// the launch timer), passes.hip (pass programs; what a program launches is planned in plain C++: pass_program.h on the
+// records of pass_records.h), generic_pass.hip and frugal_<family>.hip (the pass kernels), paos_hip.hip (the pointwise entry points: every kernel of pointwise.h) and the products: focus_otf.hip, zoom.hip,
 // detector.hip.  Here: the build-time layout, the context, the error and launch helpers, the dispatchers that turn what a
 // context is at run time into template arguments (dispatch_n: the grid size; dispatch_layout / dispatch_block_rows: element
-// type and block height -- every launch is written once, inside a generic lambda), and the declarations of the functions
+// type and block height; with pass_records.h's dispatch_family: the families of the frugal pass kernel -- every launch is
+// written once, inside a generic lambda), and the declarations of the functions
 // that cross unit boundaries.  Whatever is not declared here lives in an anonymous namespace of its unit.  Which items of a
 // batch share what is plain C++ in item_groups.h, where the blocks of the parameter arena go in arena_layout.h.
 #pragma once
@@ -20,6 +21,7 @@
 
 #include "arena_layout.h"
 #include "frugal_pass.h"
+#include "pass_records.h"
 
 using namespace paos;
 
@@ -367,25 +369,6 @@ auto dispatch_either(bool first, F&& f) {
   return f(std::integral_constant<int, B>{});
 }
 
-// ---- pass_plan.hip: a pass of a program lowered for the frugal kernels, and the pruning of dead lines across a program ----
-// One pass of a program, lowered for the frugal kernels before anything is launched, so that the
-// planner can look ahead.
-struct LoweredPass {
-  bool ok = false;
-  std::vector<FrugalItem> items;
-  int kpre = 0, kmid = 0, nfft = 1, mask_block = -1, mask_slot = -1;
-  std::vector<double> mask_shared;  // [batch] 1: the item reads the line records of an earlier, identical item
-  std::vector<int> mask_rep;        // [batch] item whose records this item reads (-1: none)
-  int mask_set = -1;                // which of the context's record sets this pass reads
-  int mask_shapes = 3;              // bit s: some item's aperture has shape s (0 ellipse, 1 rectangle) and renders its own records
-  int mask_lo = 0, mask_hi = 0;     // lines whose records this pass reads (run_passes_impl, behind the pruning plan)
-  bool mask_render = false;         // ... and whether it has to be rendered first
-};
-
-bool lower_frugal(const paos_ctx* c, const paos_pass& p, const double* blocks /*host*/, LoweredPass& lp);
-void plan_pruning(const paos_ctx* c, const paos_pass* passes, int n_passes, const double* blocks, std::vector<LoweredPass>& low,
-                  const double* entry_rows, bool entry_stale, const double* entry_cols);
-
 // ---- passes.hip ----------------------------------------------------------------------------------------------------
 // final_mode (with final_ticket): 1 = the PSF instead of the field, 2 = the field as usual plus the ticket of its power
 int run_passes(paos_ctx* c, const paos_pass* passes, int n_passes, const double* blocks, int n_blocks,
@@ -399,25 +382,9 @@ bool mask_rect_blocks();
 int generic_pass(paos_ctx* c, int axis, const PassArgs& a, int feat);
 
 // ---- frugal_<family>.hip: the pass-kernel builds of one (type, N) family behind one ordinary function each ----
-// One build of the pass kernel, by name: the record passes.hip picks per launch (pick_build) and frugal_launch.h turns into
-// template arguments (frugal_built says which records have a build).  The fields stand in frugal_launch<>'s order.
-struct FrugalBuild {
-  int axis;      // 0 rows, 1 columns
-  int kpre;      // phases in front of the first transform: 0 .. kFrugalMaxPre (table builds: 1 = however many)
-  int kmid;      // phases behind it: 0 .. kFrugalMaxMid (table builds likewise)
-  int nfft;      // transforms of the launch's first pass: 1 or 2
-  int store;     // 0 the field, 1 the PSF instead (FrugalArgs::psf), 2 the field and its power (FrugalArgs::pow_partial)
-  int tab;       // every slot with phases reads FrugalSlot::table
-  int fuse;      // the transforms of the NEXT one or two passes of the program that ride along: 0, [1], [2], 3 = [2][1], 4 = [2][2]
-                 // (same axis, same lines; their item records follow this pass's in FrugalArgs::items: [2 or 3][batch])
-  int one_line;  // a single table pass on the one-line workgroups of the fused launches
-  int central;   // every active item of the first pass loads positions of [n / 4, 3 n / 4) only: the central-half build
-};
-int paos_frugal_d1024(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a);
-int paos_frugal_d2048(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a);
-int paos_frugal_d4096(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a);
-int paos_frugal_f2048(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a);
-int paos_frugal_f4096(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a);
+// (the record that names a build, FrugalBuild, and the list of the families, dispatch_family: pass_records.h)
+template <typename T, int N>
+int frugal_family(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a);
 
 // ---- paos_hip.hip: the one unit that includes pointwise.h (its non-template kernels can be compiled once only), so
 // whatever another unit needs of that header's kernels is launched through these ----

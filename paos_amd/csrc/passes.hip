@@ -1,5 +1,6 @@
-// passes.hip -- pass programs: which kernel runs each pass, the aperture line records that ride on the frugal passes, the
-// staging of item records and phase tables, the launches, and the reference's primitives as programs (paos_ptp / stw / wts).
+// passes.hip -- pass programs: the record sets of the apertures that ride on the frugal passes, the staging of item records
+// and phase tables, the launches, and the reference's primitives as programs (paos_ptp / stw / wts).  What a program
+// launches -- which kernel runs each pass, which passes share a launch, the build it takes -- is planned in pass_program.h.
 #include "frugal_launch.h"
 
 #include <algorithm>
@@ -7,6 +8,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "pass_program.h"
 #include "phase_tables.h"
 
 namespace {
@@ -103,57 +105,32 @@ void forget_mask_sets(paos_ctx* c) {  // after a failed program: what the sets h
   for (auto& ms : c->mask_sets) ms.key.clear();
 }
 
-MaskRender mask_job(paos_ctx* c, const paos_pass& p, const LoweredPass& lp, const double* ap, const double* dshared) {
+MaskRender mask_job(paos_ctx* c, int axis, const LoweredPass& lp, const double* ap, const double* dshared) {
   const int line0 = lp.mask_lo, line_end = lp.mask_hi > lp.mask_lo ? lp.mask_hi : c->n;
-  return MaskRender{ap, dshared, lp.mask_set, p.axis, line0, line_end, lp.mask_shapes};
+  return MaskRender{ap, dshared, lp.mask_set, axis, line0, line_end, lp.mask_shapes};
 }
 
-// Do all phases of the pass vary along its lines only (the row / column factors of the separable programs)?  Then their
-// factors come from tables by position (frugal_pass.h: FrugalSlot::table).  complex128 only (the complex64 slots use the
-// hardware sin / cos).  PAOS_LINE_TABLES=0: every slot evaluates.
-bool phases_along_lines(const paos_ctx* c, const paos_pass& p, const LoweredPass& lp, bool or_none = false) {
-  static const bool want = !env_is("PAOS_LINE_TABLES", '0');
-  if (!want || (lp.kpre + lp.kmid == 0 && !or_none)) return false;
-  const int counts[2] = {lp.kpre, lp.kmid};
-  for (int l = 0; l < 2; ++l)
-    for (const FrugalItem& fi : lp.items) {
-      if (fi.active == 0.0) continue;
-      const FrugalPhase* ph = l == 0 ? fi.pre_ph : fi.mid_ph;
-      for (int j = 0; j < counts[l]; ++j)
-        if ((p.axis == 0 ? ph[j].sy : ph[j].sx) != 0.0) return false;
-    }
-  return true;
+// What the planner (pass_program.h) reads of a context ...
+PlanDims plan_dims(const paos_ctx* c) { return PlanDims{c->n, c->batch, c->br, c->precision, c->central_half ? 1 : 0}; }
+// ... and of the environment: read once per process, except the two that tests switch (host.h: env_is)
+PlanSwitches plan_switches(const paos_ctx* c) {
+  static const bool line_tables = !env_is("PAOS_LINE_TABLES", '0'), compact_grid = !env_is("PAOS_COMPACT_GRID", '0'),
+                    env_prune = !env_is("PAOS_NO_PRUNE", '1'), batched_records = !env_is("PAOS_BATCHED_RECORDS", '0'),
+                    psf_zero_reuse = !env_is("PAOS_PSF_ZERO_REUSE", '0');
+  PlanSwitches sw;
+  sw.line_tables = line_tables;
+  sw.fuse_pairs = !env_is("PAOS_FUSE_PAIRS", '0');
+  sw.compact_grid = compact_grid;
+  sw.env_prune = env_prune;
+  sw.stage_program = !env_is("PAOS_STAGE_PROGRAM", '0');
+  sw.batched_records = batched_records;
+  sw.psf_zero_reuse = psf_zero_reuse;
+  sw.ctx_prune = c->prune;
+  return sw;
 }
 
-// Can the launch of pass `p` go on with the next pass `p2` of the program (frugal_pass.h: LONG builds)?  Same axis, both on
-// table slots with phases in every slot, a two-transform pass in front, and every item takes both or neither, on the same lines.  PAOS_FUSE_PAIRS=0: never.
-bool can_fuse_pair(const paos_ctx* c, const paos_pass& p, const LoweredPass& lp, const paos_pass& p2, const LoweredPass& lp2) {
-  if (env_is("PAOS_FUSE_PAIRS", '0')) return false;
-  if (!lp.ok || !lp2.ok || p.axis != p2.axis || lp.nfft != 2) return false;
-  // (an aperture may ride on either pass -- the second one's slots read their line records themselves -- but the two must not
-  // share a record set that the second would have to re-render between them: sets are assigned per pass, in program order)
-  if (lp.mask_block >= 0 && lp2.mask_block >= 0 && lp.mask_set == lp2.mask_set) return false;
-  // (a slot without phases takes part with a table of ones: (v 1) f is v f bit for bit)
-  if (!phases_along_lines(c, p, lp, true) || !phases_along_lines(c, p2, lp2, true)) return false;
-  for (int it = 0; it < c->batch; ++it) {
-    const FrugalItem &f1 = lp.items[it], &f2 = lp2.items[it];
-    if ((f1.active != 0.0) != (f2.active != 0.0)) return false;
-    if (f1.active != 0.0 && (f1.line_lo != f2.line_lo || f1.line_hi != f2.line_hi || f1.line_fill != 0.0)) return false;
-  }
-  return true;
-}
-
-// launch a pass that lower_frugal accepted -- and, with `next`, the pass behind it in the same launch (can_fuse_pair)
-// One launch of a pass program: a pass and the one or two behind it that ride along (can_fuse_pair).
-struct FusedGroup {
-  LoweredPass* lp[3] = {nullptr, nullptr, nullptr};
-  int q = 0, count = 1, axis = 0;
-  bool tables = false;   // its slots read their phase factors from tables
-  size_t item_base = 0;  // index of its first item record in the staged array
-};
-
-// Stage the launches `groups`: decide which of them run on table slots (all phases of all their passes along the lines;
-// a fused group always does), point their slots at tables of the context's store, copy the item records of all of them to
+// Stage the launches `groups`: point the slots of those that run on table slots (decide_tables) at tables of the context's
+// store, copy the item records of all of them to
 // the device in ONE transfer and build all tables with ONE launch -- in front of the program's first launch, so that
 // nothing but the pass kernels themselves stands between two passes (round 4: a copy and a table launch in front of
 // every pass cost ~50 us of an 1.3 ms launch).  The records join the caller's batch `ab` (round 17: the block table and the
@@ -164,33 +141,19 @@ struct StagedTables {
   const PhaseSlotDesc* descs = nullptr;
   unsigned count = 0;  // table descriptors: slots with phases
 };
-int stage_groups(paos_ctx* c, ArenaBatch& ab, std::vector<FusedGroup>& groups, StagedTables* st) {
+int stage_groups(paos_ctx* c, ArenaBatch& ab, std::vector<Launch>& groups, StagedTables* st) {
   std::vector<FrugalItem> blob;
   std::vector<PhaseSlotDesc> descs;
   int slots = 0;
-  for (FusedGroup& g : groups) {
-    paos_pass axis_only{};
-    axis_only.axis = g.axis;
-    // (complex64: a slot evaluates its factors with the hardware sin / cos for less than the table's loads cost -- measured: dense
-    // launches 2.03 -> 2.41 ms with tables -- so only the fused groups, whose one build reads tables, use them)
-    g.tables = g.count > 1 || (c->precision == PAOS_F64 && phases_along_lines(c, axis_only, *g.lp[0]));
-    if (g.tables && g.count == 1) {
-      // (a single pass over most of the grid is bound by HBM, and the table's reads are traffic too: dense launches
-      // 3.75 ms evaluated, 3.85-4.0 with tables -- tables where the pass works on at most half of the lines)
-      double lines = 0.0, active = 0.0;
-      for (const FrugalItem& fi : g.lp[0]->items)
-        if (fi.active != 0.0) { lines += fi.line_hi - fi.line_lo; active += 1.0; }
-      if (active > 0.0 && lines > 0.5 * active * c->n) g.tables = false;
-    }
+  for (const Launch& g : groups)
     if (g.tables) slots += 2 * g.count;
-  }
   if (slots > c->ptab_slots) {
     if (c->ptab) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->ptab); c->ptab = nullptr; c->ptab_slots = 0; }
     HIPCHK(c, hipMalloc(&c->ptab, (size_t)slots * c->batch * c->n * sizeof(cx<double>)));
     c->ptab_slots = slots;
   }
   int slot = 0;
-  for (FusedGroup& g : groups) {
+  for (Launch& g : groups) {
     g.item_base = blob.size();
     for (int k = 0; k < g.count; ++k) {
       LoweredPass& l = *g.lp[k];
@@ -228,179 +191,79 @@ int launch_staged_tables(paos_ctx* c, const StagedTables& st) {
   return PAOS_OK;
 }
 
-// Is there a build of this name in the context's family (frugal_launch.h: frugal_built)?
-bool build_exists(const paos_ctx* c, const FrugalBuild& b) {
-  if (c->precision != PAOS_F64) return c->n == 2048 ? frugal_built<float, 2048>(b) : frugal_built<float, 4096>(b);
-  return c->n == 1024 ? frugal_built<double, 1024>(b) : (c->n == 2048 ? frugal_built<double, 2048>(b) : frugal_built<double, 4096>(b));
-}
-
-// THE place that says which build a launch takes: from the passes it runs (`lp` and the one or two that ride along), whether
-// their slots read tables (stage_groups) and what it stores (FrugalBuild::store) to the name of the build.
-FrugalBuild pick_build(const paos_ctx* c, int axis, const LoweredPass& lp, const LoweredPass* next, const LoweredPass* next2, bool tables,
-                       int store) {
-  FrugalBuild b{};
-  b.axis = axis;
-  // The table builds take "has phases" for the number of phases -- their slots read one factor --, and a fused launch runs on
-  // the one build whose slots all read tables (a slot without phases: a table of ones).
-  b.kpre = next ? 1 : (tables && lp.kpre > 1 ? 1 : lp.kpre);
-  b.kmid = next ? 1 : (tables && lp.kmid > 1 ? 1 : lp.kmid);
-  b.nfft = lp.nfft >= 2 ? 2 : 1;
-  b.store = store;
-  b.tab = tables ? 1 : 0;
-  b.fuse = next2 ? 2 + next2->nfft : (next ? next->nfft : 0);
-  // The PSF- and power-storing launches take neither of the builds below: their sums are laid out per two-line tile.
-  if (!tables || store != 0) return b;
-  // light: a single table pass whose every item loads and stores at most half of its positions -- one-line workgroups.
-  // central: every active item of the FIRST pass loads positions of the central half only -- the central-half build of the
-  // shape.  Per launch, not per item: one item outside sends the whole launch to the ordinary build.  (There is no device-side
-  // guard: frugal_pass.h, CH.)
-  bool light = !next, central = c->central_half, any = false;
-  for (const FrugalItem& fi : lp.items) {
-    if (fi.active == 0.0) continue;
-    any = true;
-    light = light && 2.0 * (fi.pos_hi - fi.pos_lo) <= (double)c->n && 2.0 * (fi.spos_hi - fi.spos_lo) <= (double)c->n;
-    central = central && 4.0 * fi.pos_lo >= (double)c->n && 4.0 * fi.pos_hi <= 3.0 * (double)c->n;
-  }
-  // ... where there is one (the central-half builds run on one-line workgroups: a fused launch, or a light pass)
-  b.one_line = light ? 1 : 0;
-  if (!build_exists(c, b)) b.one_line = 0;
-  b.central = central && any ? 1 : 0;
-  if (!build_exists(c, b)) b.central = 0;
-  return b;
-}
-
-int launch_lowered(paos_ctx* c, const paos_pass& p, LoweredPass& lp, const double* dblocks, bool store_psf = false,
-                   bool sum_power = false, LoweredPass* next = nullptr, LoweredPass* next2 = nullptr,
-                   const FrugalItem* staged = nullptr, bool staged_tables = false) {
-  LoweredPass* const last = next2 ? next2 : next;  // the pass whose stores leave the launch (nullptr: this one)
-  for (LoweredPass* l : {&lp, next, next2}) {  // render the records along the pass axis, right before the pass (every pass of a chain)
-    if (!l || l->mask_block < 0 || !l->mask_render) continue;
+// One launch of a program, as planned (pass_program.h: Launch).  staged: its item records in the array the program staged
+// in front of its first launch, or nullptr.
+int launch_lowered(paos_ctx* c, const Launch& g, const double* dblocks, const FrugalItem* staged) {
+  for (int k = 0; k < g.count; ++k) {  // render the records along the pass axis, right before the pass (every pass of a chain)
+    LoweredPass* l = g.lp[k];
+    if (l->mask_block < 0 || !l->mask_render) continue;
     const double* ap = dblocks + (size_t)l->mask_block * c->batch * FP_STRIDE;
     const double* dshared = nullptr;
     int rcs = arena_push(c, l->mask_shared.data(), l->mask_shared.size(), &dshared);
     if (rcs) return rcs;
-    const MaskRender job = mask_job(c, p, *l, ap, dshared);  // (a pair runs along one axis)
+    const MaskRender job = mask_job(c, g.axis, *l, ap, dshared);  // (a chain runs along one axis)
     if ((rcs = render_mask_records(c, &job, 1))) return rcs;
     l->mask_render = false;
   }
   // The item records (with the pointers to their slots' phase tables) and the tables themselves: staged for the whole
   // program in front of its first launch (stage_groups: one copy, one table launch), or here for this launch alone.
-  bool tables = staged_tables;
-  const FrugalItem* ditems_f = staged;
-  if (!ditems_f) {
-    FusedGroup g;
-    g.lp[0] = &lp; g.lp[1] = next; g.lp[2] = next2; g.count = next2 ? 3 : (next ? 2 : 1);
-    g.axis = p.axis;
-    std::vector<FusedGroup> one{g};
+  if (!staged) {
+    std::vector<Launch> one{g};
     ArenaBatch ab(c);  // (inside the program's reservation: no begin)
     StagedTables st;
     int rcg = stage_groups(c, ab, one, &st);
     if (rcg || (rcg = ab.commit()) || (rcg = launch_staged_tables(c, st))) return rcg;
-    tables = one[0].tables;
-    ditems_f = st.items + one[0].item_base;
+    staged = st.items + one[0].item_base;
   }
-  const double* ditems = reinterpret_cast<const double*>(ditems_f);
-  FrugalArgs a{c->field, c->tw, reinterpret_cast<const FrugalItem*>(ditems), c->pitch, c->item_stride, nullptr, nullptr, nullptr};
-  if (store_psf) { a.psf = c->psf; a.psf_partial = c->psf_partial; }
-  if (sum_power) a.pow_partial = c->pow_partial;
+  FrugalArgs a{c->field, c->tw, staged, c->pitch, c->item_stride, nullptr, nullptr, nullptr};
+  if (g.store == 1) { a.psf = c->psf; a.psf_partial = c->psf_partial; }
+  if (g.store == 2) a.pow_partial = c->pow_partial;
   a.dyn_scale = c->dyn_scale;
-  {  // the lines some item still works on: the grid need not cover the others when their tiles have nothing to write
-    // PAOS_COMPACT_GRID=0 launches the full grid (dead workgroups exit in their prologue)
-    static const bool want = !env_is("PAOS_COMPACT_GRID", '0');
-    double lo = (double)c->n, hi = 0.0;
-    bool fill = false;
-    // (a fused pair: the lines are the same for both passes, what is stored and filled is the second pass's business)
-    const std::vector<FrugalItem>& out_items = last ? last->items : lp.items;
-    for (const FrugalItem& fi : out_items) {
-      if (fi.active == 0.0) continue;
-      lo = fi.line_lo < lo ? fi.line_lo : lo;
-      hi = fi.line_hi > hi ? fi.line_hi : hi;
-      if (fi.line_fill != 0.0 && store_psf) {  // dead tiles write PSF zeros inside [spos_lo, spos_hi) only (run_passes_impl)
-        lo = fi.spos_lo < lo ? fi.spos_lo : lo;
-        hi = fi.spos_hi > hi ? fi.spos_hi : hi;
-      } else {
-        fill = fill || fi.line_fill != 0.0;
-      }
-    }
-    a.live_lo = a.live_hi = a.wg0 = 0;
-    if (want && !fill && hi > lo && (lo > 0.0 || hi < (double)c->n)) {
-      a.live_lo = (unsigned)lo;
-      a.live_hi = (unsigned)hi;
-    }
+  a.live_lo = g.live_lo; a.live_hi = g.live_hi; a.wg0 = 0;
+  c->prof_next_tag = g.tag;
+  c->prof_next_bytes = g.bytes;
+  c->prof_next_lines = g.lines;
+  const FrugalBuild& b = g.build;
+  {  // paos_pass_builds: the record the family function gets, in launch order
+    int rec[kBuildFields];
+    build_to_ints(b, rec);
+    c->pass_builds.insert(c->pass_builds.end(), rec, rec + kBuildFields);
   }
-  // for the launch timer: what does this launch skip?  bit 0: whole tiles of dead lines, bit 1: loads of dead
-  // positions, bit 2: stores nobody reads, bit 3: it stores the PSF instead of the field
-  c->prof_next_tag = store_psf ? 8 : 0;
-  c->prof_next_bytes = 0.0;
-  c->prof_next_lines = 0.0;
-  if (next) c->prof_next_tag |= next2 ? 32 : 16;  // bit 4: the launch ran two passes of the program, bit 5: three
-  for (int it = 0; it < c->batch; ++it) {
-    const FrugalItem& fi = lp.items[it];
-    const FrugalItem& fo = last ? last->items[it] : fi;  // the pass whose stores leave the launch
-    if (fi.active == 0.0) continue;
-    if (fi.line_lo > 0.0 || fi.line_hi < (double)c->n) c->prof_next_tag |= 1;
-    if (fi.pos_lo > 0.0 || fi.pos_hi < (double)c->n) c->prof_next_tag |= 2;
-    if (!store_psf && (fo.spos_lo > 0.0 || fo.spos_hi < (double)c->n)) c->prof_next_tag |= 4;
-    // what the plan has this launch move: its live lines' loaded and stored positions (the PSF store: doubles, every position)
-    c->prof_next_bytes += (fi.line_hi - fi.line_lo) * ((fi.pos_hi - fi.pos_lo) * (double)elem_bytes(c) +
-                                                        (store_psf ? (double)c->n * 8.0 : (fo.spos_hi - fo.spos_lo) * (double)elem_bytes(c)));
-    // ... and compute: every live line goes through the transforms that are switched on for this item, in every pass of the launch
-    for (const LoweredPass* l : {(const LoweredPass*)&lp, (const LoweredPass*)next, (const LoweredPass*)next2}) {
-      if (!l) continue;
-      const FrugalItem& fk = l->items[it];
-      c->prof_next_lines += (fi.line_hi - fi.line_lo) * ((fk.fft1_on != 0.0 ? 1.0 : 0.0) + (l->nfft >= 2 && fk.fft2_on != 0.0 ? 1.0 : 0.0));
-    }
-  }
-  const FrugalBuild b = pick_build(c, p.axis, lp, next, next2, tables, store_psf ? 1 : (sum_power ? 2 : 0));
   // PAOS_DUMP_PASSES=1: on stderr, the build the launch takes and one line per pass it runs (what item 0's two slots carry)
   static const bool dump = env_is("PAOS_DUMP_PASSES", '1');
-  {  // paos_pass_builds: the record the family function gets, in launch order
-    const int rec[9] = {b.axis, b.kpre, b.kmid, b.nfft, b.store, b.tab, b.fuse, b.one_line, b.central};
-    c->pass_builds.insert(c->pass_builds.end(), rec, rec + 9);
-  }
   if (dump) {
     std::fprintf(stderr, "build axis %d kpre %d kmid %d nfft %d store %d tab %d fuse %d one_line %d central %d n %d %s\n", b.axis, b.kpre, b.kmid,
                  b.nfft, b.store, b.tab, b.fuse, b.one_line, b.central, c->n, c->precision == PAOS_F64 ? "fp64" : "fp32");
-    for (const LoweredPass* l : {(const LoweredPass*)&lp, (const LoweredPass*)next, (const LoweredPass*)next2}) {
-      if (!l || l->items.empty()) continue;
+    for (int k = 0; k < g.count; ++k) {
+      const LoweredPass* l = g.lp[k];
+      if (l->items.empty()) continue;
       const FrugalItem& f = l->items[0];  // ("+pass": rides in the launch of the pass above it)
       std::fprintf(stderr, "%spass axis %d kpre %d kmid %d nfft %d | pre: sign %g scale %g mask %g | fft1 on %g inv %g | mid: sign %g scale %g mask %g | "
-                   "fft2 on %g inv %g | lines [%g, %g) fill %g loads [%g, %g) stores [%g, %g)\n", l == &lp ? "" : "+", p.axis, l->kpre, l->kmid, l->nfft,
+                   "fft2 on %g inv %g | lines [%g, %g) fill %g loads [%g, %g) stores [%g, %g)\n", k == 0 ? "" : "+", g.axis, l->kpre, l->kmid, l->nfft,
                    f.pre.sign_on, f.pre.scale, f.pre.mask_on, f.fft1_on, f.fft1_inv, f.mid.sign_on, f.mid.scale, f.mid.mask_on, f.fft2_on, f.fft2_inv,
                    f.line_lo, f.line_hi, f.line_fill, f.pos_lo, f.pos_hi, f.spos_lo, f.spos_hi);
     }
   }
-  if (c->precision == PAOS_F64) {
-    switch (c->n) {
-      case 1024: return paos_frugal_d1024(c, b, a);
-      case 2048: return paos_frugal_d2048(c, b, a);
-      default: return paos_frugal_d4096(c, b, a);
-    }
-  }
-  switch (c->n) {
-    case 2048: return paos_frugal_f2048(c, b, a);
-    default: return paos_frugal_f4096(c, b, a);
-  }
+  // (a pass is lowered only in a context of one of the families: frugal_sizes)
+  return dispatch_family(c->precision, c->n, (int)PAOS_EUNSUPPORTED,
+                         [&](auto t, auto n) { return frugal_family<decltype(t), decltype(n)::value>(c, b, a); });
 }
 
 int launch_one_pass(paos_ctx* c, const paos_pass& p, const double* dblocks, int n_blocks,
                     const int* table_of_op /* [3][PAOS_MAX_PW], -1 = none */) {
   int rc;
-  if ((rc = check_ops(c, p.pre, p.n_pre, n_blocks))) return rc;
-  if ((rc = check_ops(c, p.mid, p.n_mid, n_blocks))) return rc;
-  if ((rc = check_ops(c, p.post, p.n_post, n_blocks))) return rc;
+  for (int l = 0; l < 3; ++l)
+    if ((rc = check_ops(c, op_list(p, l).ops, op_list(p, l).count, n_blocks))) return rc;
   if (p.fft1 >= n_blocks || p.fft2 >= n_blocks) return fail(c, PAOS_EINVAL, "transform control block out of range");
-  {  // at most one aperture operator per pass: its weight map is rendered right before it
-    const paos_pw_op* lists3[3] = {p.pre, p.mid, p.post};
-    const int counts3[3] = {p.n_pre, p.n_mid, p.n_post};
-    int nmask = 0;
-    for (int l = 0; l < 3; ++l)
-      for (int o = 0; o < counts3[l]; ++o)
-        if (lists3[l][o].kind == PAOS_PW_MASK) {
-          if (++nmask > 1) return fail(c, PAOS_EINVAL, "one aperture operator per pass");
-          int rcm = render_mask_weights(c, dblocks + (size_t)lists3[l][o].block * c->batch * FP_STRIDE);
-          if (rcm) return rcm;
-        }
+  int nmask = 0;  // at most one aperture operator per pass: its weight map is rendered right before it
+  for (int l = 0; l < 3; ++l) {
+    const OpList ol = op_list(p, l);
+    for (int o = 0; o < ol.count; ++o)
+      if (ol.ops[o].kind == PAOS_PW_MASK) {
+        if (++nmask > 1) return fail(c, PAOS_EINVAL, "one aperture operator per pass");
+        int rcm = render_mask_weights(c, dblocks + (size_t)ol.ops[o].block * c->batch * FP_STRIDE);
+        if (rcm) return rcm;
+      }
   }
   PassArgs a{};
   a.field = c->field; a.tw = c->tw; a.blocks = dblocks; a.tables = c->tables; a.mask = c->mask; a.batch = c->batch;
@@ -410,14 +273,13 @@ int launch_one_pass(paos_ctx* c, const paos_pass& p, const double* dblocks, int 
   std::memcpy(a.mid, p.mid, sizeof(a.mid));
   std::memcpy(a.post, p.post, sizeof(a.post));
   PwOp* lists[3] = {a.pre, a.mid, a.post};
-  const int counts[3] = {a.n_pre, a.n_mid, a.n_post};
   int feat = 0;
   for (int l = 0; l < 3; ++l)
     for (int o = 0; o < PAOS_MAX_PW; ++o) {
       lists[l][o].flags &= (1 << kTableShift) - 1;
       const int t = table_of_op[l * PAOS_MAX_PW + o];
       if (t >= 0) { lists[l][o].flags |= (t + 1) << kTableShift; feat = 3; }
-      if (o < counts[l] && lists[l][o].kind == PWK_MASK) feat = 3;
+      if (o < op_list(p, l).count && lists[l][o].kind == PWK_MASK) feat = 3;
     }
   a.pitch = c->pitch; a.item_stride = c->item_stride;
   if (p.axis == 0 || p.axis == 1) return generic_pass(c, p.axis, a, feat);
@@ -427,271 +289,185 @@ int launch_one_pass(paos_ctx* c, const paos_pass& p, const double* dblocks, int 
   return pointwise_pass(c, a);
 }
 
-// PAOS_NO_PRUNE=1 processes every tile (A/B tests of the dead-line pruning).
-bool use_pruning() {
-  static const bool on = !env_is("PAOS_NO_PRUNE", '1');
-  return on;
-}
+// ---- a pass program, step by step (run_passes_impl): what the steps hand to each other -------------------------------
+struct ProgramRun {
+  paos_ctx* c;
+  const paos_pass* passes;
+  int n_passes;
+  const double* blocks;  // host
+  int n_blocks;
+  PlanDims d;
+  PlanSwitches sw;
+  ArenaBatch ab;                    // THE copy of the program: the block table, the renderings' vectors, the staged records
+  const double* dblocks = nullptr;  // the block table on the device
+  std::vector<LoweredPass> low;
+  bool all_frugal = false, pruned = false;
+  int store = 0;         // what the last pass stores on the way out (pass_program.h: last_pass_store)
+  int power_groups = 0;  // store = 2: the per-workgroup sums of an item
+  std::vector<MaskRender> renderings;  // the record renderings that go in one batch, in front of the first pass
+  std::vector<Launch> launches;
+  std::vector<int> launch_of;
+  StagedTables staged;   // items != nullptr: records and tables of the whole program were staged in front of its first launch
+  ProgramRun(paos_ctx* c_, const paos_pass* passes_, int n_passes_, const double* blocks_, int n_blocks_)
+      : c(c_), passes(passes_), n_passes(n_passes_), blocks(blocks_), n_blocks(n_blocks_), d(plan_dims(c_)), sw(plan_switches(c_)), ab(c_) {}
+};
 
-// entry_rows / entry_stale: see paos_program_opts.  final_ticket != nullptr: the caller wants |u|^2 and its sum of
-// the field the program ends with, not the field.
-int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const double* blocks, int n_blocks,
-                    const double* entry_rows, bool entry_stale, int* final_ticket, int final_mode, const double* entry_cols) {
+int validate_program(paos_ctx* c, const paos_pass* passes, int n_passes, const double* blocks, int n_blocks, const int* final_ticket) {
   if (c) c->pass_builds.clear();  // (paos_pass_builds: the launches of THIS program)
   if (!c || !passes || !blocks || n_passes < 0 || n_blocks < 1) return fail(c, PAOS_EINVAL, "bad pass program");
   c->norm2_of_field = false;  // (set again at the end when the last pass sums the power of what it stores)
   // A program that ends on the PSF gives the field up for it: the free power-ticket slot it will need is checked
   // BEFORE anything is launched (found full afterwards, the context held neither field nor ticket).
   if (int rcr = final_ticket ? power_ring_full(c) : PAOS_OK) return rcr;
-  // The device sincos has no huge-argument path: bound every enabled phase operator here.
-  for (int i = 0; i < n_passes; ++i) {
-    const paos_pw_op* lists[3] = {passes[i].pre, passes[i].mid, passes[i].post};
-    const int counts[3] = {passes[i].n_pre, passes[i].n_mid, passes[i].n_post};
-    for (int l = 0; l < 3; ++l)
-      for (int o = 0; o < counts[l] && o < PAOS_MAX_PW; ++o) {
-        const paos_pw_op& op = lists[l][o];
-        if (op.kind != PAOS_PW_QPHASE_CENTRED && op.kind != PAOS_PW_QPHASE_NATURAL) continue;
-        if (op.block < 0 || op.block >= n_blocks) return fail(c, PAOS_EINVAL, "operator block index out of range");
-        for (int it = 0; it < c->batch; ++it) {
-          const double* p = blocks + ((size_t)op.block * c->batch + it) * FP_STRIDE;
-          if (p[FP_ENABLE] == 0.0) continue;
-          const double hx = 0.5 * c->n * p[FP_SX], hy = 0.5 * c->n * p[FP_SY];
-          double arg = std::fabs(p[FP_COEF]) * (hx * hx + hy * hy);
-          if (op.flags & PAOS_PWF_MUL2PI) arg *= 6.283185307179586;
-          if (!(arg < kMaxPhaseArg))
-            return fail(c, PAOS_EUNSUPPORTED, "quadratic phase exceeds 1e12 rad at the grid corner (or is not finite)");
-        }
-      }
+  switch (check_phase_args(plan_dims(c), passes, n_passes, blocks, n_blocks)) {
+    case PHASE_BLOCK_OUT_OF_RANGE: return fail(c, PAOS_EINVAL, "operator block index out of range");
+    case PHASE_TOO_LARGE: return fail(c, PAOS_EUNSUPPORTED, "quadratic phase exceeds 1e12 rad at the grid corner (or is not finite)");
+    default: return PAOS_OK;
   }
-  const double* dblocks = nullptr;
-  // everything this program pushes stays live until its last pass has run: the block table and,
-  // per pass, one FrugalItem record per batch item (each push is rounded up to 16 doubles)
-  // plus, for a pass that carries an aperture, the [batch] "shares its line records" vector (launch_lowered)
-  // ... and two table descriptors (stage_groups)
+}
+
+// Everything the program pushes stays live until its last pass has run: the block table and,
+// per pass, one FrugalItem record per batch item (each push is rounded up to 16 doubles)
+// plus, for a pass that carries an aperture, the [batch] "shares its line records" vector (launch_lowered)
+// ... and two table descriptors (stage_groups)
+// ... and the two windows of zero_outside_box.  Round 17: the block table, the vectors of the batched renderings and the
+// staged records are ONE batch, copied once in front of the program's first launch that reads any of them; whatever is
+// pushed launch by launch behind that (arena_push: a copy of its own) still lies inside this reservation.
+int open_batch(ProgramRun& r) {
+  paos_ctx* c = r.c;
   const size_t per_pass = (((size_t)c->batch * sizeof(FrugalItem) / sizeof(double) + 15) & ~size_t(15)) +
                           (((size_t)c->batch + 15) & ~size_t(15)) + 16;
-  // ... and the two windows of zero_outside_box.  Round 17: the block table, the vectors of the batched renderings and the
-  // staged records are ONE batch, copied once in front of the program's first launch that reads any of them; whatever is
-  // pushed launch by launch behind that (arena_push: a copy of its own) still lies inside this reservation.
-  ArenaBatch ab(c);
-  int rc = ab.begin((size_t)n_blocks * c->batch * FP_STRIDE + 16 + (size_t)n_passes * per_pass + 2 * arena_rounded((size_t)2 * c->batch));
+  int rc = r.ab.begin((size_t)r.n_blocks * c->batch * FP_STRIDE + 16 + (size_t)r.n_passes * per_pass + 2 * arena_rounded((size_t)2 * c->batch));
   if (rc) return rc;
-  rc = ab.add(blocks, (size_t)n_blocks * c->batch * FP_STRIDE, &dblocks);
+  return r.ab.add(r.blocks, (size_t)r.n_blocks * c->batch * FP_STRIDE, &r.dblocks);
+}
+
+// Lower every pass for the frugal kernels first, so that the planner can look ahead across the program, and give every
+// pass that carries an aperture a record set of the context's store, in program order.
+int lower_and_assign_sets(ProgramRun& r) {
+  paos_ctx* c = r.c;
+  r.low.resize(r.n_passes);
+  r.all_frugal = !use_tables() && frugal_sizes(c) && r.n_passes > 0;
+  if (use_tables() || !frugal_sizes(c)) return PAOS_OK;
+  int rc = ensure_mask_store(c);
   if (rc) return rc;
-  // Lower every pass for the frugal kernels first; when the whole program runs on them, plan the
-  // pruning of dead lines across it (look-ahead), then launch.
-  std::vector<LoweredPass> low(n_passes);
-  bool all_frugal = !use_tables() && frugal_sizes(c) && n_passes > 0;
-  if (!use_tables() && frugal_sizes(c)) {
-    if ((rc = ensure_mask_store(c))) return rc;
-    for (int q = 0; q < n_passes; ++q) {
-      LoweredPass& lp = low[q];
-      lp.ok = lower_frugal(c, passes[q], blocks, lp);
-      if (lp.ok && lp.mask_block >= 0 && (rc = assign_mask_set(c, passes[q], lp, blocks))) return rc;
-      all_frugal = all_frugal && lp.ok;
-    }
+  for (int q = 0; q < r.n_passes; ++q) {
+    LoweredPass& lp = r.low[q];
+    lp.ok = lower_frugal(r.d, r.passes[q], r.blocks, lp);
+    if (lp.ok && lp.mask_block >= 0 && (rc = assign_mask_set(c, r.passes[q], lp, r.blocks))) return rc;
+    r.all_frugal = r.all_frugal && lp.ok;
   }
-  if (c->dyn_pending) {
-    // a stop's scaling is waiting: the first pass takes it along in its middle slot when it is a frugal pass every item
-    // takes part in; otherwise the field gets it now
-    bool ride = n_passes > 0 && low[0].ok;
-    if (ride)
-      for (const FrugalItem& fi : low[0].items) ride = ride && fi.active != 0.0;
-    if (ride) ++c->deferred_rode;
-    if (!ride && (rc = settle_scale(c))) return rc;
+  return PAOS_OK;
+}
+
+// A stop's scaling is waiting: the first pass takes it along in its middle slot when it is a frugal pass every item
+// takes part in; otherwise the field gets it now.
+int settle_stop(ProgramRun& r) {
+  paos_ctx* c = r.c;
+  if (!c->dyn_pending) return PAOS_OK;
+  bool ride = r.n_passes > 0 && r.low[0].ok;
+  if (ride)
+    for (const FrugalItem& fi : r.low[0].items) ride = ride && fi.active != 0.0;
+  if (ride) ++c->deferred_rode;
+  return ride ? PAOS_OK : settle_scale(c);
+}
+
+// When the whole program runs on the frugal kernels, plan the pruning of dead lines across it (look-ahead); then the lines
+// whose aperture records each pass reads (record_window): a set found in the context's store is good only if it was rendered
+// that far.
+void plan_lines(ProgramRun& r, const double* entry_rows, bool entry_stale, const double* entry_cols) {
+  paos_ctx* c = r.c;
+  r.pruned = r.all_frugal && r.sw.env_prune && r.sw.ctx_prune;
+  if (r.pruned) plan_pruning(r.d, r.passes, r.n_passes, r.blocks, r.low, entry_rows, entry_stale, entry_cols);
+  for (LoweredPass& lp : r.low) {
+    if (!lp.ok || lp.mask_block < 0) continue;
+    record_window(r.d, lp);
+    paos_ctx::MaskSet& ms = c->mask_sets[lp.mask_set];
+    if (!lp.mask_render && !(ms.line_lo <= lp.mask_lo && ms.line_hi >= lp.mask_hi)) {
+      lp.mask_render = true;  // found, but rendered for a narrower window than this pass reads
+      --c->mask_hits; ++c->mask_rendered;
+    }
+    if (lp.mask_render) { ms.line_lo = lp.mask_lo; ms.line_hi = lp.mask_hi; }
   }
-  const bool pruned = all_frugal && use_pruning() && c->prune;
-  if (pruned) plan_pruning(c, passes, n_passes, blocks, low, entry_rows, entry_stale, entry_cols);
-  // Which lines' aperture records does each pass read?  Those of its live tiles only: a workgroup whose lines are dead
-  // for its item (frugal_pass_kernel: outside [line_lo, line_hi), bounds that are multiples of the tile height)
-  // leaves before it looks at a record.  Only these lines are rendered (a quarter of them behind a clear aperture at
-  // zoom 4), and a set found in the context's store is good only if it was rendered that far.
-  {
-    for (int q = 0; q < n_passes; ++q) {
-      LoweredPass& lp = low[q];
-      if (!lp.ok || lp.mask_block < 0) continue;
-      double lo = (double)c->n, hi = 0.0;
-      for (const FrugalItem& fi : lp.items) {
-        if (fi.active == 0.0) continue;
-        lo = fi.line_lo < lo ? fi.line_lo : lo;
-        hi = fi.line_hi > hi ? fi.line_hi : hi;
-      }
-      const bool window = hi > lo;
-      lp.mask_lo = window ? (int)lo : 0;
-      lp.mask_hi = window ? (int)hi : c->n;
-      paos_ctx::MaskSet& ms = c->mask_sets[lp.mask_set];
-      if (!lp.mask_render && !(ms.line_lo <= lp.mask_lo && ms.line_hi >= lp.mask_hi)) {
-        lp.mask_render = true;  // found, but rendered for a narrower window than this pass reads
-        --c->mask_hits; ++c->mask_rendered;
-      }
-      if (lp.mask_render) { ms.line_lo = lp.mask_lo; ms.line_hi = lp.mask_hi; }
+}
+
+// What the store mode of the last pass needs on the device: the buffers of its sums, zeroed where dead tiles and workgroups
+// that are not launched contribute nothing, and the PSF buffer itself -- and, for a PSF store, which zeros it still owes.
+int prepare_store(ProgramRun& r, int final_mode) {
+  paos_ctx* c = r.c;
+  r.store = last_pass_store(r.low, final_mode);
+  if (final_mode == 2 && r.store == 2) {
+    r.power_groups = c->n / frugal_tile_lines(c, r.passes[r.n_passes - 1].axis);
+    if (c->pow_nparts < c->n / 2) {  // (sized for the finest tiling of either axis)
+      if (c->pow_partial) (void)hipFree(c->pow_partial);
+      c->pow_partial = nullptr; c->pow_nparts = 0;
+      HIPCHK(c, hipMalloc(&c->pow_partial, (size_t)c->batch * (c->n / 2) * sizeof(double)));
+      c->pow_nparts = c->n / 2;
     }
+    // dead tiles and workgroups that are not launched at all contribute nothing: zeros
+    HIPCHK(c, hipMemsetAsync(c->pow_partial, 0, (size_t)c->batch * r.power_groups * sizeof(double), c->stream));
   }
-  if (entry_stale && entry_rows) {
-    // Rows that merely stand for zeros must become zeros wherever the program will not consume them: everywhere when
-    // the planner is off, and for an item no pass of the program touches.
-    bool need = !pruned;
-    for (int it = 0; it < c->batch && !need; ++it) {
-      bool active = false;
-      for (int q = 0; q < n_passes; ++q) active = active || low[q].items[it].active != 0.0;
-      need = !active;
-    }
-    // ... and for an item whose window is empty: the planner takes an empty window for no window at all (plan_pruning),
-    // so its first pass would load every line of stale data
-    const double* windows[2] = {entry_rows, entry_cols};
-    for (int w = 0; w < 2 && !need; ++w)
-      for (int it = 0; windows[w] && it < c->batch && !need; ++it) {
-        const int br = c->br, l = ((int)windows[w][2 * it] / br) * br;
-        int h = (((int)windows[w][2 * it + 1] + br - 1) / br) * br;
-        if (h > c->n) h = c->n;
-        need = l >= h;
-      }
-    if (need) {
-      // (all items at once: the ones the planner handles lose nothing but a little time, and the planner was told
-      // "stale", which is also right for zeros)
-      if ((rc = entry_cols ? zero_outside_box(c, entry_rows, entry_cols) : zero_outside_rows(c, entry_rows))) return rc;
-    }
+  if (final_mode != 1) return PAOS_OK;
+  if (!c->psf) HIPCHK(c, hipMalloc(&c->psf, (size_t)c->batch * c->item_stride * sizeof(double)));
+  c->otf_valid = false;  // a new PSF: the transfer functions computed from the previous one are stale
+  if (r.store != 1) return PAOS_OK;
+  const int axis = r.passes[r.n_passes - 1].axis, groups = c->n / frugal_tile_lines(c, axis);
+  if (c->psf_nparts < groups) {
+    if (c->psf_partial) (void)hipFree(c->psf_partial);
+    c->psf_partial = nullptr; c->psf_nparts = 0;
+    c->psf_zero_axis = -1;
+    HIPCHK(c, hipMalloc(&c->psf_partial, (size_t)c->batch * groups * sizeof(double)));
+    c->psf_nparts = groups;
   }
-  // The PSF instead of the field: the last pass stores |u|^2 and its per-workgroup sums (frugal_pass.h: STORE) when
-  // it runs on the frugal kernels in a shape built for it and every item takes part; otherwise the program runs as
-  // usual and the intensity sweep follows.
-  bool fused_store = false, fused_power = false;
-  int power_groups = 0;
-  if (final_ticket && final_mode == 2) {
-    // The field is kept AND its power is wanted (a saved surface, run.py:218-223 callers): the last pass sums |u|^2 of
-    // its tiles while it stores them (FrugalArgs::pow_partial) -- when it runs on the frugal kernels and every item
-    // takes part; otherwise the ordinary reduction follows the program.
-    fused_power = n_passes > 0 && low[n_passes - 1].ok && low[n_passes - 1].kpre <= 1;  // (the shapes built with STORE = 2)
-    if (fused_power)
-      for (const FrugalItem& fi : low[n_passes - 1].items) fused_power = fused_power && fi.active != 0.0;
-    if (fused_power) {
-      power_groups = c->n / frugal_tile_lines(c, passes[n_passes - 1].axis);
-      if (c->pow_nparts < c->n / 2) {  // (sized for the finest tiling of either axis)
-        if (c->pow_partial) (void)hipFree(c->pow_partial);
-        c->pow_partial = nullptr; c->pow_nparts = 0;
-        HIPCHK(c, hipMalloc(&c->pow_partial, (size_t)c->batch * (c->n / 2) * sizeof(double)));
-        c->pow_nparts = c->n / 2;
-      }
-      // dead tiles and workgroups that are not launched at all contribute nothing: zeros
-      HIPCHK(c, hipMemsetAsync(c->pow_partial, 0, (size_t)c->batch * power_groups * sizeof(double), c->stream));
-    }
+  psf_zero_fill(r.d, r.sw, axis, r.low[r.n_passes - 1].items, c->psf_zero_axis, c->psf_zero_lo, c->psf_zero_hi);
+  c->psf_zero_axis = -1;  // set again once the pass is on the stream (hand_out_ticket)
+  return PAOS_OK;
+}
+
+// The record renderings that go in ONE launch per shape (batched_renderings): their vectors join the program's batch, the
+// launches follow its commit.  Every other rendering happens in place, right before its pass (launch_lowered).
+int batch_renderings(ProgramRun& r) {
+  for (int q : batched_renderings(r.sw, r.all_frugal, r.low)) {
+    LoweredPass& lp = r.low[q];
+    const double* dshared = nullptr;
+    int rc = r.ab.add(lp.mask_shared.data(), lp.mask_shared.size(), &dshared);
+    if (rc) return rc;
+    r.renderings.push_back(mask_job(r.c, r.passes[q].axis, lp, r.dblocks + (size_t)lp.mask_block * r.c->batch * FP_STRIDE, dshared));
+    lp.mask_render = false;
   }
-  if (final_ticket && final_mode != 2) {
-    if (!c->psf) HIPCHK(c, hipMalloc(&c->psf, (size_t)c->batch * c->item_stride * sizeof(double)));
-    c->otf_valid = false;  // a new PSF: the transfer functions computed from the previous one are stale
-    fused_store = n_passes > 0 && low[n_passes - 1].ok && low[n_passes - 1].kpre <= 1 && low[n_passes - 1].kmid <= 1;
-    if (fused_store)
-      for (const FrugalItem& fi : low[n_passes - 1].items) fused_store = fused_store && fi.active != 0.0;
-    if (fused_store) {
-      const int groups = c->n / frugal_tile_lines(c, passes[n_passes - 1].axis);
-      if (c->psf_nparts < groups) {
-        if (c->psf_partial) (void)hipFree(c->psf_partial);
-        c->psf_partial = nullptr; c->psf_nparts = 0;
-        c->psf_zero_axis = -1;
-        HIPCHK(c, hipMalloc(&c->psf_partial, (size_t)c->batch * groups * sizeof(double)));
-        c->psf_nparts = groups;
-      }
-      // dead tiles of the storing pass write PSF zeros (line_fill) -- unless the buffer already holds zeros there:
-      // the previous storing pass had the same live lines (the next batch of a sweep, the next Monte-Carlo batch)
-      static const bool reuse = !env_is("PAOS_PSF_ZERO_REUSE", '0');
-      const int axis = passes[n_passes - 1].axis;
-      std::vector<FrugalItem>& last = low[n_passes - 1].items;
-      // Round 4: per item.  What the buffer may still hold of the previous storing pass lies inside that pass's live
-      // lines [psf_zero_lo, psf_zero_hi); only dead tiles of THIS pass that meet them write zeros (the range travels in
-      // the item's -- here otherwise unused -- store-position fields).  A walked sweep changes the sampling at the
-      // image plane from batch to batch, so the live lines are never the same twice, but they move by a few lines.
-      const bool known = reuse && c->psf_zero_axis == axis && (int)c->psf_zero_lo.size() == c->batch;
-      c->psf_zero_lo.resize(c->batch); c->psf_zero_hi.resize(c->batch);
-      for (int it = 0; it < c->batch; ++it) {
-        const double old_lo = known ? c->psf_zero_lo[it] : 0.0, old_hi = known ? c->psf_zero_hi[it] : (double)c->n;
-        const bool covered = old_lo >= last[it].line_lo && old_hi <= last[it].line_hi;  // every old line is rewritten
-        last[it].line_fill = covered ? 0.0 : 1.0;
-        last[it].spos_lo = covered ? 0.0 : old_lo;
-        last[it].spos_hi = covered ? (double)c->n : old_hi;
-        c->psf_zero_lo[it] = last[it].line_lo; c->psf_zero_hi[it] = last[it].line_hi;
-      }
-      c->psf_zero_axis = -1;  // set again below once the pass is on the stream
-    }
+  return PAOS_OK;
+}
+
+// The launches of the program, each with its tables flag, its build, its grid window and its timer figures; when every
+// pass runs on the frugal kernels their item records and phase tables are staged here, once, for all of them
+// (stage_groups); otherwise each launch stages its own.
+int plan_and_stage_launches(ProgramRun& r) {
+  r.launches = form_launches(r.d, r.sw, r.passes, r.n_passes, r.low, r.all_frugal && r.pruned, r.launch_of);
+  for (Launch& g : r.launches) {
+    if (!g.lp[0]->ok) continue;  // (a pass on the generic kernel: launch_one_pass)
+    decide_tables(r.d, r.sw, g);
+    finish_launch(r.d, r.sw, g, g.q + g.count == r.n_passes ? r.store : 0);
   }
-  // The aperture line records this program has to render (not found in the context's kept sets): all of them in ONE
-  // launch per shape, in front of the first pass -- when every rendering goes to a set no EARLIER pass of this program
-  // reads (always, unless a program carries more distinct apertures than there are sets; then each is rendered in place,
-  // right before its pass).  PAOS_BATCHED_RECORDS=0: in place, one launch per aperture, as before.
-  std::vector<MaskRender> renderings;
-  {
-    static const bool want = !env_is("PAOS_BATCHED_RECORDS", '0');
-    std::vector<int> todo;
-    bool safe = want && all_frugal;
-    for (int q = 0; q < n_passes && safe; ++q) {
-      if (low[q].mask_block < 0) continue;
-      if (low[q].mask_render) {
-        for (int r = 0; r < q; ++r) safe = safe && !(low[r].mask_block >= 0 && low[r].mask_set == low[q].mask_set);
-        todo.push_back(q);
-      }
-    }
-    if (safe && todo.size() > 1) {  // (launched below, behind the commit)
-      for (int q : todo) {
-        LoweredPass& lp = low[q];
-        const double* dshared = nullptr;
-        if ((rc = ab.add(lp.mask_shared.data(), lp.mask_shared.size(), &dshared))) return rc;
-        renderings.push_back(mask_job(c, passes[q], lp, dblocks + (size_t)lp.mask_block * c->batch * FP_STRIDE, dshared));
-        lp.mask_render = false;
-      }
-    }
-  }
-  // The launches of the program: a pass, or two / three consecutive passes of one row / column chain (can_fuse_pair).
-  // When every pass runs on the frugal kernels their item records and phase tables are staged here, once, for all of
-  // them (stage_groups); otherwise each launch stages its own.  PAOS_STAGE_PROGRAM=0: each launch stages its own.
-  std::vector<FusedGroup> groups;
-  std::vector<int> group_of(n_passes, -1);
-  const FrugalItem* staged_items = nullptr;
-  StagedTables staged;
-  {
-    for (int q = 0; q < n_passes;) {
-      FusedGroup g;
-      g.q = q; g.axis = passes[q].axis; g.lp[0] = &low[q];
-      if (low[q].ok && all_frugal && pruned) {
-        const bool pair = q + 1 < n_passes && can_fuse_pair(c, passes[q], low[q], passes[q + 1], low[q + 1]);
-        // (and a third: the five-transform chains -- ptp, stw, ptp -- that end a SYN20-like prescription)
-        const bool triple = pair && q + 2 < n_passes && can_fuse_pair(c, passes[q + 1], low[q + 1], passes[q + 2], low[q + 2]) &&
-                            !(low[q].mask_block >= 0 && low[q + 2].mask_block >= 0 && low[q].mask_set == low[q + 2].mask_set);
-        g.count = triple ? 3 : (pair ? 2 : 1);
-        for (int k = 1; k < g.count; ++k) g.lp[k] = &low[q + k];
-      }
-      group_of[q] = (int)groups.size();
-      groups.push_back(g);
-      q += g.count;
-    }
-    // (a table per operator slot of every pass: 2 MiB each at 4096^2 x 32; a program that would need more than 1 GiB of
-    // them -- hundreds of passes -- stages launch by launch, on six tables)
-    const size_t table_bytes = (size_t)2 * n_passes * c->batch * c->n * sizeof(cx<double>);
-    if (all_frugal && !env_is("PAOS_STAGE_PROGRAM", '0') && table_bytes <= (size_t(1) << 30)) {
-      if ((rc = stage_groups(c, ab, groups, &staged))) return rc;
-      staged_items = staged.items;
-    }
-  }
-  // THE copy of the program, in front of its first launch that reads a block: the record renderings, the table kernel, or
-  // the first pass.  (What ran above -- a settled stop scale, zeroed windows -- reads none of this batch.)
-  if ((rc = ab.commit())) return rc;
-  for (size_t at = 0; at < renderings.size(); at += kMaskRenders)
-    if ((rc = render_mask_records(c, renderings.data() + at, (int)std::min<size_t>(kMaskRenders, renderings.size() - at)))) return rc;
-  if ((rc = launch_staged_tables(c, staged))) return rc;
-  // Walk the program in chunks whose phase operators fit the table store: fill the tables of
-  // a chunk with one small launch, then run its passes.
+  if (!stage_whole_program(r.d, r.sw, r.all_frugal, r.n_passes)) return PAOS_OK;
+  return stage_groups(r.c, r.ab, r.launches, &r.staged);
+}
+
+// Walk the program in chunks whose phase operators fit the table store of the generic kernel (PAOS_PHASE_TABLES=1; without
+// it the whole program is one chunk): fill the tables of a chunk with one small launch, then run its passes.
+int launch_chunks(ProgramRun& r) {
+  paos_ctx* c = r.c;
+  int rc;
   int i = 0;
-  while (i < n_passes) {
+  while (i < r.n_passes) {
     TableArgs ta{};
-    ta.blocks = dblocks; ta.tables = c->tables; ta.batch = c->batch; ta.n = c->n; ta.count = 0;
+    ta.blocks = r.dblocks; ta.tables = c->tables; ta.batch = c->batch; ta.n = c->n; ta.count = 0;
     std::vector<int> assign;  // per pass of the chunk: [3][PAOS_MAX_PW]
     int j = i;
-    for (; j < n_passes; ++j) {
-      const paos_pass& p = passes[j];
-      const paos_pw_op* lists[3] = {p.pre, p.mid, p.post};
-      const int counts[3] = {p.n_pre, p.n_mid, p.n_post};
+    for (; j < r.n_passes; ++j) {
+      const paos_pass& p = r.passes[j];
       int need = 0;
       for (int l = 0; l < 3; ++l)
-        for (int o = 0; o < counts[l] && o < PAOS_MAX_PW; ++o)
-          need += (lists[l][o].kind == PAOS_PW_QPHASE_CENTRED || lists[l][o].kind == PAOS_PW_QPHASE_NATURAL);
+        for (int o = 0; o < op_list(p, l).count && o < PAOS_MAX_PW; ++o) need += is_phase(op_list(p, l).ops[o]);
       if (use_tables() && ta.count + need > kMaxTables) {
         if (j == i) return fail(c, PAOS_EINVAL, "one pass needs more phase tables than the store holds");
         break;
@@ -700,10 +476,10 @@ int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const do
       assign.resize(base + 3 * PAOS_MAX_PW, -1);
       if (!use_tables()) continue;
       for (int l = 0; l < 3; ++l)
-        for (int o = 0; o < counts[l] && o < PAOS_MAX_PW; ++o) {
-          const paos_pw_op& op = lists[l][o];
-          if (op.kind != PAOS_PW_QPHASE_CENTRED && op.kind != PAOS_PW_QPHASE_NATURAL) continue;
-          if (op.block < 0 || op.block >= n_blocks) return fail(c, PAOS_EINVAL, "operator block index out of range");
+        for (int o = 0; o < op_list(p, l).count && o < PAOS_MAX_PW; ++o) {
+          const paos_pw_op& op = op_list(p, l).ops[o];
+          if (!is_phase(op)) continue;
+          if (op.block < 0 || op.block >= r.n_blocks) return fail(c, PAOS_EINVAL, "operator block index out of range");
           ta.jobs[ta.count] = {op.block, op.kind, op.flags & PAOS_PWF_MUL2PI};
           assign[base + l * PAOS_MAX_PW + o] = ta.count++;
         }
@@ -718,37 +494,62 @@ int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const do
       HIPCHK(c, hipGetLastError());
     }
     for (int q = i; q < j; ++q) {
-      if (low[q].ok) {
-        // (a group of up to three passes of one row / column chain runs in ONE launch: frugal_pass.h, LONG builds)
-        const FusedGroup& g = groups[group_of[q]];
-        const int last = q + g.count - 1;
-        if (last >= j) return fail(c, PAOS_EINVAL, "a fused group crosses a table chunk");
-        if ((rc = launch_lowered(c, passes[q], low[q], dblocks, fused_store && last == n_passes - 1, fused_power && last == n_passes - 1,
-                                 g.lp[1], g.lp[2], staged_items ? staged_items + g.item_base : nullptr, g.tables))) return rc;
-        q = last;
-        if (c->dyn_pending) {  // (first launch of the program) the stop's factor has gone into the field: ones again for the next
-          if ((rc = dyn_scale_reset(c))) return rc;
-        }
+      if (!r.low[q].ok) {
+        if ((rc = launch_one_pass(c, r.passes[q], r.dblocks, r.n_blocks, &assign[(size_t)(q - i) * 3 * PAOS_MAX_PW]))) return rc;
         continue;
       }
-      if ((rc = launch_one_pass(c, passes[q], dblocks, n_blocks, &assign[(size_t)(q - i) * 3 * PAOS_MAX_PW]))) return rc;
+      // (a group of up to three passes of one row / column chain runs in ONE launch: frugal_pass.h, LONG builds)
+      const Launch& g = r.launches[r.launch_of[q]];
+      const int last = q + g.count - 1;
+      if (last >= j) return fail(c, PAOS_EINVAL, "a fused group crosses a table chunk");
+      if ((rc = launch_lowered(c, g, r.dblocks, r.staged.items ? r.staged.items + g.item_base : nullptr))) return rc;
+      q = last;
+      if (c->dyn_pending) {  // (first launch of the program) the stop's factor has gone into the field: ones again for the next
+        if ((rc = dyn_scale_reset(c))) return rc;
+      }
     }
     i = j;
   }
-  if (final_ticket && final_mode == 2) {
-    // (the fallback: a generic-kernel pass, or an item that sat the last pass out)
-    const int rcp = fused_power ? take_power_ticket(c, c->pow_partial, power_groups, nullptr, final_ticket) : paos_norm2_enqueue(c, final_ticket);
+  return PAOS_OK;
+}
+
+// The ticket of the power the caller asked for: of the sums the last pass left, or -- the fallback: a generic-kernel pass, or
+// an item that sat the last pass out -- of the reduction or the intensity sweep that follows the program.
+int hand_out_ticket(ProgramRun& r, int final_mode, int* final_ticket) {
+  paos_ctx* c = r.c;
+  if (final_mode == 2) {
+    const int rcp = r.store == 2 ? take_power_ticket(c, c->pow_partial, r.power_groups, nullptr, final_ticket) : paos_norm2_enqueue(c, final_ticket);
     if (rcp == PAOS_OK) c->norm2_of_field = true;  // c->norm2 = the power of every item's field as stored
     return rcp;
   }
-  if (final_ticket) {
-    if (fused_store) {
-      c->psf_zero_axis = passes[n_passes - 1].axis;  // every launch of the program went through
-      return take_power_ticket(c, c->psf_partial, c->n / frugal_tile_lines(c, passes[n_passes - 1].axis), nullptr, final_ticket);
-    }
-    return psf_keep_power_impl(c, final_ticket);
+  if (r.store != 1) return psf_keep_power_impl(c, final_ticket);
+  c->psf_zero_axis = r.passes[r.n_passes - 1].axis;  // every launch of the program went through
+  return take_power_ticket(c, c->psf_partial, c->n / frugal_tile_lines(c, r.passes[r.n_passes - 1].axis), nullptr, final_ticket);
+}
+
+// entry_rows / entry_stale: see paos_program_opts.  final_ticket != nullptr: the caller wants |u|^2 and its sum of
+// the field the program ends with, not the field (final_mode 1), or the field and the sum (2).
+int run_passes_impl(paos_ctx* c, const paos_pass* passes, int n_passes, const double* blocks, int n_blocks,
+                    const double* entry_rows, bool entry_stale, int* final_ticket, int final_mode, const double* entry_cols) {
+  int rc = validate_program(c, passes, n_passes, blocks, n_blocks, final_ticket);
+  if (rc) return rc;
+  final_mode = final_ticket ? (final_mode == 2 ? 2 : 1) : 0;
+  ProgramRun r(c, passes, n_passes, blocks, n_blocks);
+  if ((rc = open_batch(r)) || (rc = lower_and_assign_sets(r)) || (rc = settle_stop(r))) return rc;
+  plan_lines(r, entry_rows, entry_stale, entry_cols);
+  if (entry_stale && entry_rows && entry_zero_first(r.d, r.pruned, r.low, entry_rows, entry_cols)) {
+    // (all items at once: the ones the planner handles lose nothing but a little time, and the planner was told
+    // "stale", which is also right for zeros)
+    if ((rc = entry_cols ? zero_outside_box(c, entry_rows, entry_cols) : zero_outside_rows(c, entry_rows))) return rc;
   }
-  return PAOS_OK;
+  if ((rc = prepare_store(r, final_mode)) || (rc = batch_renderings(r)) || (rc = plan_and_stage_launches(r))) return rc;
+  // THE copy of the program, in front of its first launch that reads a block: the record renderings, the table kernel, or
+  // the first pass.  (What ran above -- a settled stop scale, zeroed windows -- reads none of this batch.)
+  if ((rc = r.ab.commit())) return rc;
+  for (size_t at = 0; at < r.renderings.size(); at += kMaskRenders)
+    if ((rc = render_mask_records(c, r.renderings.data() + at, (int)std::min<size_t>(kMaskRenders, r.renderings.size() - at)))) return rc;
+  if ((rc = launch_staged_tables(c, r.staged)) || (rc = launch_chunks(r))) return rc;
+  return final_mode ? hand_out_ticket(r, final_mode, final_ticket) : PAOS_OK;
 }
 
 }  // namespace
@@ -852,23 +653,15 @@ int paos_run_program(paos_ctx* c, const paos_pass* passes, int n_passes, const d
 
 int paos_frugal_built(int precision, int n, const int* record) {
   if (!record) return -PAOS_EINVAL;  // (negative: PAOS_EINVAL itself is 1, "built")
-  const FrugalBuild b{record[0], record[1], record[2], record[3], record[4], record[5], record[6], record[7], record[8]};
-  if (precision == PAOS_F64) {
-    if (n == 1024) return frugal_built<double, 1024>(b) ? 1 : 0;
-    if (n == 2048) return frugal_built<double, 2048>(b) ? 1 : 0;
-    if (n == 4096) return frugal_built<double, 4096>(b) ? 1 : 0;
-  } else if (precision == PAOS_F32) {
-    if (n == 2048) return frugal_built<float, 2048>(b) ? 1 : 0;
-    if (n == 4096) return frugal_built<float, 4096>(b) ? 1 : 0;
-  }
-  return -PAOS_EINVAL;
+  const FrugalBuild b = build_from_ints(record);
+  return dispatch_family(precision, n, -(int)PAOS_EINVAL, [&](auto t, auto size) { return frugal_built<decltype(t), decltype(size)::value>(b) ? 1 : 0; });
 }
 
 int paos_pass_builds(paos_ctx* c, int* records, int capacity, int* count) {
   if (!c || !count || capacity < 0 || (capacity > 0 && !records)) return fail(c, PAOS_EINVAL, "bad pass-builds request");
-  const int have = (int)(c->pass_builds.size() / 9);
+  const int have = (int)(c->pass_builds.size() / kBuildFields);
   *count = have;
-  if (have > 0 && capacity > 0) std::memcpy(records, c->pass_builds.data(), (size_t)(have < capacity ? have : capacity) * 9 * sizeof(int));
+  if (have > 0 && capacity > 0) std::memcpy(records, c->pass_builds.data(), (size_t)(have < capacity ? have : capacity) * kBuildFields * sizeof(int));
   return PAOS_OK;
 }
 

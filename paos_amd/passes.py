@@ -396,7 +396,7 @@ class SeparableCompiler(PassCompiler):
     For SYN20 at zoom 4 (a 1024-pixel pupil on a 4096 grid) that is 4 x 1024 + 4 x 1024 line transforms per relay
     instead of the 2 x 1024 + 6 x 4096 of the operator-by-operator order (PassCompiler), with every pass touching a
     sixteenth of the grid on the way in and on the way out.  Which lines are alive / wanted is the library's planner's
-    business (csrc/pass_plan.hip: plan_pruning); this class only orders the factors.
+    business (csrc/pass_program.h: plan_pruning); this class only orders the factors.
 
     The identities of PassCompiler (consecutive ptp share their transforms, ptp(+d) ptp(-d) = 1, a wts and the stw that
     undoes it) are applied to the operator stream before it is split.  Arguments: the reference rounds

@@ -3,7 +3,7 @@ build a program can reach a recipe: a pass program that makes passes.hip's pick_
 
 Needs no device: ``built_records`` asks the library's host-only query (paos_frugal_built), the recipes are plain data in the
 terms of the long-double harness (test_gpu_xprec._run, xprec_np.run_item).  tests/test_pass_builds_host.py holds the table to
-restatements of the host rules (pass_plan.hip: lower_frugal; passes.hip: can_fuse_pair); tests/test_gpu_pass_builds.py runs
+restatements of the host rules (pass_program.h: lower_frugal; passes.hip: can_fuse_pair); tests/test_gpu_pass_builds.py runs
 every recipe, reads back the build each launch took (DeviceFields.pass_builds) and holds the result to the long-double reference.
 
 What a recipe varies inside its record is a function of the record alone (``_mix``), so a failure reproduces:
@@ -309,7 +309,7 @@ def recipe(precision, n, record):
 
 # ---- restatements of the host rules (what test_pass_builds_host.py holds the recipes to) ---------------------------------
 def lowered_counts(p, blocks, lib=_lib):
-    """pass_plan.hip, lower_frugal: (kpre, kmid, nfft) of a pass as lowered -- phases per slot, every enabled phase with
+    """pass_program.h, lower_frugal: (kpre, kmid, nfft) of a pass as lowered -- phases per slot, every enabled phase with
     |sgn| = 1 (else None: the generic kernel), and a sign, a scale != 1 or an aperture in an otherwise phase-free first slot
     of an active item promotes kpre 0 -> 1."""
     blocks = np.asarray(blocks)

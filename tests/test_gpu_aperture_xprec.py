@@ -421,7 +421,7 @@ def test_generic_pass_mask_in_every_slot(precision):
 
 def test_generic_pass_takes_what_the_records_cannot_hold():
     """At 1024^2 the production kernels take a riding aperture as line records -- unless it is thinner than two pixels
-    across the lines, tilted, or a rectangular obscuration: those passes run on the generic kernel (pass_plan.hip:
+    across the lines, tilted, or a rectangular obscuration: those passes run on the generic kernel (pass_program.h:
     lower_frugal), as does every pass with an operator in its post slot -- with the same weights."""
     n = 1024
     lib = _lib()

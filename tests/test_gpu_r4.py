@@ -1,5 +1,5 @@
 """GPU tests added in round 4: the separable pass programs (passes.py: SeparableCompiler) and the two-axis planner
-behind them (csrc/pass_plan.hip: plan_pruning).
+behind them (csrc/pass_program.h: plan_pruning).
 
 * SYN20 at 4096^2 (the benchmark's size) from the separable programs against the operator-by-operator ones -- which
   tests/test_gpu_r3.py and tests/test_gpu.py pin to the oracle at that size -- fp64 and fp32, and against the oracle

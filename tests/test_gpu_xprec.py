@@ -146,7 +146,7 @@ def test_host_refuses_phase_arguments_at_1e12_and_nan(precision):
 
 
 # ---- b) phase factors riding on transforms ------------------------------------------------------------------------
-# (family, precision, n, K, where): the builds that evaluate phases (pass_plan.hip: lower_frugal; passes.hip: phases_along_lines,
+# (family, precision, n, K, where): the builds that evaluate phases (pass_program.h: lower_frugal; passes.hip: phases_along_lines,
 # can_fuse_pair, pick_build)
 #   generic   fp64 N <= 512, fp32 N <= 1024; at any N a pass with a post operator ("post") or a phase with |sgn| != 1
 #   frugal    fp64 N >= 1024, phases across the lines: sincos_tab; K = 2 in one slot: merged (slot_factor<2>); K = 3 sits in

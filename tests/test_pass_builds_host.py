@@ -1,6 +1,6 @@
 """The table of pass-kernel builds and recipes (tests/pass_builds.py) against the library's own statement of what is built
 (paos_frugal_built -> csrc/frugal_launch.h: frugal_built) and against restatements of the host rules that lead a program to a
-build (pass_plan.hip: lower_frugal's counting; passes.hip: can_fuse_pair's static conditions).  No device."""
+build (pass_program.h: lower_frugal's counting; passes.hip: can_fuse_pair's static conditions).  No device."""
 import collections
 import ctypes
 
