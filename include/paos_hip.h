@@ -372,6 +372,40 @@ enum { PAOS_BLUR_ITEM = 6 };   /* dx, dy, sigma_x, sigma_y, pixel_x, pixel_y */
  * neither read nor written.  PAOS_EINVAL, the context left usable and both buffers untouched: before paos_otf_compute or
  * when its result is stale (the test of paos_otf_fetch), a parameter paos_blur_table refuses, a null pointer. */
 int paos_blur_apply(paos_ctx* ctx, const double* per_item);
+/* ---- energy profiles: encircled / ensquared energy of the kept PSFs about their own centres (README.md, "Encircled energy") - */
+/* The reference's Monte-Carlo workflow reduces every draw to an encircled-energy radius on the host
+ * (docs/source/user/montecarlo/index.rst); here the curves are made on the device from the kept PSF P[k][j] (N x N doubles, rows
+ * k along y, as paos_psf_fetch returns it; in fp32 contexts too, so everything below is fp64 in both).  Per item a ring
+ * width D in units of dx and an aspect a = dy / dx.
+ *   Sums over the whole grid: S = sum P, Sx = sum P j, Sy = sum P k; peak = the largest value, (peak_col, peak_row) its
+ *   first occurrence in row-major order.
+ *   Centre (cx, cy), column and row in pixels: PAOS_EE_GIVEN as passed; PAOS_EE_PEAK (peak_col, peak_row);
+ *   PAOS_EE_CENTROID cx = Sx / S, cy = Sy / S, one division each, on the device -- and if S > 0 is false or a centroid
+ *   coordinate is not inside [0, N), (N/2, N/2) with fallback = 1 (the flag concerns the centroid; it is 0 otherwise).
+ *   Membership, every operation rounded once (no contraction): x = (double)j - cx, y = ((double)k - cy) a,
+ *   d2 = x x + y y, r_b = (double)(b + 1) D, t_b = r_b r_b; pixel (k, j) is inside circle b iff d2 <= t_b (the
+ *   pixel-centre rule of paos_psf_metrics) and inside square b iff fmax(|x|, |y|) <= r_b.  No wrap: pixels outside the
+ *   grid do not exist.
+ *   Curves: ee[b] = sum of P over the pixels inside circle b, ensq[b] likewise for square b: powers, not fractions; with
+ *   negative values in a blurred PSF they need not be monotone.
+ * No float atomics and a fixed summation order: a repeated call gives the same bits, and an item's results do not depend
+ * on the batch size or on its place in the batch. */
+enum { PAOS_EE_GIVEN = 0, PAOS_EE_CENTROID = 1, PAOS_EE_PEAK = 2 };
+enum { PAOS_EE_ITEM = 4 };     /* delta, aspect, cx, cy (cx, cy read for PAOS_EE_GIVEN only) */
+enum { PAOS_EE_SUMMARY = 9 };  /* S, Sx, Sy, peak, peak_col, peak_row, cx, cy, fallback */
+/* per_item[batch][PAOS_EE_ITEM]; bins in 1 .. 1024; square != 0: the ensquared curve too.  Enqueues only: the centre is
+ * formed on the device between the sweep that sums and the launch that bins.  Scratch is allocated on first use and again
+ * when a request needs more; its size follows batch x bins x bands of 16 rows, never N^2.  PAOS_EINVAL, nothing touched
+ * and the context left usable: before any PSF is kept, a null pointer, bins outside 1 .. 1024, an unknown centre_mode, a
+ * delta or aspect that is not finite and positive, bins delta > N/2 or bins delta / aspect > N/2 (the largest circle
+ * would be wider or taller than the grid), a given centre that is not finite or not inside [0, N).  PAOS_EHIP for a failed
+ * scratch allocation. */
+int paos_ee_compute(paos_ctx* ctx, int bins, int square, int centre_mode, const double* per_item);
+/* summary[batch][PAOS_EE_SUMMARY] and curves[batch][1 + square][bins] (ee, then ensq) of the last paos_ee_compute.  Either
+ * pointer may be NULL, not both.  Synchronises.  PAOS_EINVAL before a compute, with both pointers null, and for `curves`
+ * of a compute whose PSFs were stored anew since (paos_psf_keep, paos_psf_keep_power, a PSF-storing pass program,
+ * paos_blur_apply): compute again. */
+int paos_ee_fetch(paos_ctx* ctx, double* summary, double* curves);
 /* ---- zoomed PSF windows: the field interpolated exactly onto a finer grid (README.md, "Zoomed PSFs") ------------------- */
 /* No reference counterpart.  With u[k][j] the N x N field of item i (rows k along y), its band-limited interpolant with the
  * Nyquist term split evenly is u(y, x) = sum_k sum_j u[k][j] d(y - k) d(x - j), d(t) = sin(pi t) / (N tan(pi t / N)),

@@ -24,6 +24,11 @@ exact band-limited interpolant of the field, two fp64 matrix-instruction contrac
 ``run_batch(..., psf_blur=PsfBlur(sigma_x, sigma_y, pixel=...))`` blurs the last surface's kept PSFs by pointing jitter,
 charge diffusion and the pixel aperture: one multiplication on their spectra and a packed real-output inverse transform
 on the GPU; detector images and transfer functions are then the system ones (README.md, "Blurred PSFs").
+
+``run_batch(..., psf_energy=EnergyProfile(bins, step, centre="centroid", fractions=(0.9,)))`` adds the encircled (and
+ensquared) energy of the last surface's kept PSFs on up to 1024 radii in metres, each about the item's own centroid, peak
+or given centre, with the radii that enclose the requested fractions -- summed, centred and binned on the GPU, on the lean
+walk and behind a blur (README.md, "Encircled energy").
 """
 from .abcd import ABCD
 from .coordinate_break import coordinate_break
@@ -32,7 +37,7 @@ from .zernike import Zernike
 
 from .raytrace import raytrace
 
-__all__ = ["ABCD", "Detector", "PsfBlur", "PsfWindow", "WFO", "Zernike", "coordinate_break", "parse_config", "raytrace",
+__all__ = ["ABCD", "Detector", "EnergyProfile", "PsfBlur", "PsfWindow", "WFO", "Zernike", "coordinate_break", "parse_config", "raytrace",
            "run_batch", "run_broadband", "run_sharded"]
 __version__ = "0.1.0"
 
@@ -51,6 +56,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(".detector", __name__), name)
     if name == "PsfBlur":
         return importlib.import_module(".blur", __name__).PsfBlur
+    if name == "EnergyProfile":
+        return importlib.import_module(".energy", __name__).EnergyProfile
     if name == "PsfWindow":
         return importlib.import_module(".zoom", __name__).PsfWindow
     if name == "run_sharded":

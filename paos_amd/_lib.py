@@ -25,6 +25,8 @@ PWF_MUL2PI = 1
 PWF_X_ONLY, PWF_Y_ONLY = 2, 4  # PW_SIGN: (-1)^column / (-1)^row instead of the checkerboard (-1)^(row + column)
 MAX_PW = 6
 OTF_MTF, OTF_COMPLEX = 0, 1  # paos_otf_fetch: |OTF| as doubles / the complex OTF
+EE_GIVEN, EE_CENTROID, EE_PEAK = 0, 1, 2  # paos_ee_compute: where the circles of an item are centred
+EE_ITEM, EE_SUMMARY, EE_MAX_BINS = 4, 9, 1024
 ZOOM_PSF, ZOOM_FIELD = 0, 1  # paos_zoom_fetch: |u|^2 of the window as doubles / the complex window
 ZOOM_MAX_TABLES = 256  # phase tables a context keeps; the most distinct fractional parts among the centres of one call
 NORM_SLOTS = 64  # PAOS_NORM_SLOTS: tickets of paos_norm2_enqueue that may be outstanding
@@ -96,6 +98,8 @@ SYMBOLS = {
     "paos_otf_cuts": (ctypes.c_int, [_c_ctx, _dbl_p]),
     "paos_blur_table": (ctypes.c_int, [ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, _dbl_p]),
     "paos_blur_apply": (ctypes.c_int, [_c_ctx, _dbl_p]),
+    "paos_ee_compute": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dbl_p]),
+    "paos_ee_fetch": (ctypes.c_int, [_c_ctx, _dbl_p, _dbl_p]),
     "paos_zoom_weights": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_double, _dbl_p, ctypes.POINTER(ctypes.c_int)]),
     "paos_zoom_compute": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, _dbl_p, ctypes.c_int]),
     "paos_zoom_fetch": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
@@ -723,6 +727,35 @@ class DeviceFields:
             raise ValueError(f"blur_apply takes scalars or one value per item ({self.batch})") from None
         per_item = np.ascontiguousarray(per_item)
         self._check(self._lib.paos_blur_apply(self._ctx, _dptr(per_item)), "paos_blur_apply")
+
+    # -- energy profiles (paos_ee_*: README.md, "Encircled energy") ---------------------------------------------------
+    def energy_compute(self, bins, deltas, aspects, centre_mode, centres=None, square=False):
+        """Encircled (and, with ``square``, ensquared) energy of every item's kept PSF on ``bins`` radii ``(b + 1) *
+        deltas[i]`` (units of the item's dx; ``aspects[i]`` = dy / dx) about its own centre: ``centre_mode`` EE_GIVEN
+        (``centres``, a (batch, 2) array of pixel positions ``(x, y)``; None: the grid centre), EE_CENTROID or EE_PEAK, both
+        formed on the device.  ``deltas`` / ``aspects`` are scalars or one value per item.  Enqueued only."""
+        per_item = np.empty((self.batch, EE_ITEM), dtype=np.float64)
+        try:
+            per_item[:, 0] = np.broadcast_to(np.asarray(deltas, dtype=np.float64), (self.batch,))
+            per_item[:, 1] = np.broadcast_to(np.asarray(aspects, dtype=np.float64), (self.batch,))
+            per_item[:, 2:] = self.n / 2 if centres is None else np.asarray(centres, dtype=np.float64)
+        except ValueError:
+            raise ValueError(f"energy_compute takes scalars or one value per item ({self.batch}) and (batch, 2) centres") from None
+        self._check(self._lib.paos_ee_compute(self._ctx, int(bins), int(bool(square)), int(centre_mode), _dptr(per_item)),
+                    "paos_ee_compute")
+        self._ee_shape = (self.batch, 2 if square else 1, int(bins))
+
+    def energy_fetch(self, curves=True):
+        """(summary, curves) of the last ``energy_compute``: summary (batch, 9) = S, Sx, Sy, peak, peak_col, peak_row, cx,
+        cy, fallback; curves (batch, 1 + square, bins) = ee, then ensq (None with ``curves=False``).  Synchronises.
+        Refused (``PaosHipError``) before a compute, and for the curves once the PSFs were stored anew."""
+        shape = getattr(self, "_ee_shape", None)
+        if shape is None:
+            raise PaosHipError("paos_ee_fetch failed (1): no energy profiles computed (paos_ee_compute)")
+        summary = np.empty((self.batch, EE_SUMMARY), dtype=np.float64)
+        out = np.empty(shape, dtype=np.float64) if curves else None
+        self._check(self._lib.paos_ee_fetch(self._ctx, _dptr(summary), _dptr(out) if curves else None), "paos_ee_fetch")
+        return summary, out
 
     # -- zoomed windows (paos_zoom_*: README.md, "Zoomed PSFs") ------------------------------------------------------
     def zoom_compute(self, size, oversample, centres=None, field=False):

@@ -224,6 +224,7 @@ int paos_blur_apply(paos_ctx* c, const double* per_item) {
   // the PSF buffer is rewritten as a whole: what the context knew about zeros in it (the dead-tile memo of the storing
   // passes) is void.  The spectrum is rewritten along with it, so the transfer functions stay valid: those of P'.
   c->psf_zero_axis = -1;
+  c->ee_valid = false;  // (energy curves read the PSFs themselves: those of P are stale)
   for (int axis = 1; axis >= 0; --axis) {
     rc = blur_pass(c, axis, a);
     if (rc) {

@@ -159,6 +159,13 @@ struct paos_ctx {
   size_t det_rows_bytes = 0;
   double* det_out = nullptr;       // per-item images of one chunk (paos_detector_images)
   size_t det_out_bytes = 0;
+  // energy profiles (paos_ee_compute): one buffer -- summary [batch][9] | curves [batch][ee_curves][ee_bins] | the partial
+  // sums of the launches -- allocated on first use and again when a request needs more.  ee_valid: the curves were
+  // computed from what the PSF buffer holds NOW -- cleared by everything that stores a PSF, paos_blur_apply included
+  double* ee_buf = nullptr;
+  size_t ee_bytes = 0;
+  int ee_bins = 0, ee_curves = 0;
+  bool ee_computed = false, ee_valid = false;
   void* bounce[2] = {nullptr, nullptr};  // pinned host buffers for device -> pageable host copies
   hipEvent_t bounce_ev[2] = {nullptr, nullptr};
   void* field = nullptr;

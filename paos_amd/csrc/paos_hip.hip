@@ -458,7 +458,7 @@ int paos_psf_keep(paos_ctx* c) {
   if (!c) return fail(c, PAOS_EINVAL, "null context");
   if (!c->psf) HIPCHK(c, hipMalloc(&c->psf, (size_t)c->batch * c->item_stride * sizeof(double)));
   c->psf_zero_axis = -1;  // the whole buffer is rewritten
-  c->otf_valid = false;   // ... and the transfer functions computed from the previous PSFs are stale
+  c->otf_valid = c->ee_valid = false;  // ... and the transfer functions and energy curves computed from the previous PSFs are stale
   const dim3 grid(pw_blocks(c), c->batch), block(kPwThreads);
   dispatch_layout(c, [&](auto t, auto br) {
     using T = decltype(t);
@@ -620,7 +620,7 @@ int psf_keep_power_impl(paos_ctx* c, int* ticket) {
   if (int rc = power_ring_full(c)) return rc;
   if (!c->psf) HIPCHK(c, hipMalloc(&c->psf, (size_t)c->batch * c->item_stride * sizeof(double)));
   c->psf_zero_axis = -1;  // the whole buffer is rewritten
-  c->otf_valid = false;   // ... and the transfer functions computed from the previous PSFs are stale
+  c->otf_valid = c->ee_valid = false;  // ... and the transfer functions and energy curves computed from the previous PSFs are stale
   const dim3 grid(c->nparts, c->batch), block(kPwThreads);
   dispatch_layout(c, [&](auto t, auto br) {
     using T = decltype(t);

@@ -409,7 +409,7 @@ int prepare_store(ProgramRun& r, int final_mode) {
   }
   if (final_mode != 1) return PAOS_OK;
   if (!c->psf) HIPCHK(c, hipMalloc(&c->psf, (size_t)c->batch * c->item_stride * sizeof(double)));
-  c->otf_valid = false;  // a new PSF: the transfer functions computed from the previous one are stale
+  c->otf_valid = c->ee_valid = false;  // a new PSF: the transfer functions and energy curves computed from the previous one are stale
   if (r.store != 1) return PAOS_OK;
   const int axis = r.passes[r.n_passes - 1].axis, groups = c->n / frugal_tile_lines(c, axis);
   if (c->psf_nparts < groups) {

@@ -1262,8 +1262,8 @@ def _plan_focus(states, chains, focus_planes, last_key):
     return beams, planes
 
 
-# The products of the last surface -- a blur of the kept PSFs (blur.PsfBlur), detector images, transfer functions, zoomed
-# windows (zoom.PsfWindow) -- share one
+# The products of the last surface -- a blur of the kept PSFs (blur.PsfBlur), their energy curves (energy.EnergyProfile),
+# detector images, transfer functions, zoomed windows (zoom.PsfWindow) -- share one
 # method: ``attach(dev, recs, dxs, dys)`` gives ``recs[i]`` item i's entries from what ``dev`` holds right now (the kept
 # PSFs: ``reads_psf``, or the field) on the samplings ``dxs`` / ``dys``.  ``_attach_products`` walks them.
 class _DetectorRequest:
@@ -1387,7 +1387,7 @@ def _focus_stack(dev, focus, outputs, metrics_radii_px, power, products):
 def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, precision="fp64",
               device=0, outputs=("psf",), dev=None, sync=True, stats=None, metrics_radii_px=None,
               keep_psf=False, power=True, detector=None, detector_weights=None, detector_origin=None, focus_planes=None,
-              mtf_cuts=False, psf_zoom=None, psf_blur=None):
+              mtf_cuts=False, psf_zoom=None, psf_blur=None, psf_energy=None):
     """Propagate ``B = len(opt_chains)`` wavefronts together on one GPU.
 
     ``wavelengths[i]`` / ``opt_chains[i]`` describe wavefront ``i`` (chains must
@@ -1480,6 +1480,21 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     ``ValueError``, before anything is launched: an argument that is not a ``PsfBlur``; a last surface that is not saved;
     ``sync=False``; per-item values of another length than the batch; ``pixel`` together with ``detector`` (the rebinning
     already integrates over the pixel).
+
+    ``psf_energy`` (a :class:`paos_amd.EnergyProfile`) adds the encircled energy of every item's kept PSF at the LAST
+    surface, which must be saved, computed on the GPU (README.md, "Encircled energy"; it implies ``keep_psf``): up to
+    1024 radii ``(b + 1) step`` in metres at the image plane (or pixels), each item about its own centre -- the grid
+    centre, given positions, or the centroid or the peak, which are formed on the device between the sweep that sums the
+    PSF and the launch that bins it (``paos_ee_compute``; one small copy, ``paos_ee_fetch``).  The last surface's record
+    gets ``'ee_radius'``, ``'ee'`` (the power inside each circle, not normalised), ``'ensq'`` with ``square=True``,
+    ``'ee_total'``, ``'ee_centre'`` ``(x, y)`` in pixels, ``'ee_peak'`` ``(value, (col, row))``, ``'ee_fallback'`` and
+    ``'ree'``, the radii at which ``'ee'`` reaches the requested fractions of ``'ee_total'`` (NaN where it does not).  It
+    reads the kept PSFs: behind ``psf_blur`` the curves are those of ``P'``, ``outputs=()`` stays on the lean walk, and
+    with ``focus_planes`` every plane's dict gets the same keys, each plane about its own centre (the ``dz == 0.0``
+    plane's equal the nominal record's bit for bit).  ``ValueError``, before anything is launched: an argument that is
+    not an ``EnergyProfile``; a last surface that is not saved; ``sync=False``; centres of another shape than (B, 2) or
+    outside ``[0, N)``.  An item whose largest circle would be wider or taller than the grid (``bins step / dx_i`` or
+    ``bins step / dy_i`` above ``N / 2``) is a ``ValueError`` that names it, raised before the curves are computed.
     """
     nb = len(opt_chains)
     if len(wavelengths) != nb:
@@ -1504,6 +1519,15 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
         psf_blur.check(nb)
         if psf_blur.pixel is not None and detector is not None:
             raise ValueError("psf_blur with a pixel aperture and a detector: the rebinning already integrates over the pixel")
+    if psf_energy is not None:
+        from .energy import EnergyProfile
+
+        if not isinstance(psf_energy, EnergyProfile):
+            raise ValueError(f"psf_energy must be a paos_amd.EnergyProfile, got {psf_energy!r}")
+        if not sync:
+            raise ValueError("psf_energy synchronises: it cannot be combined with sync=False")
+        _need_saved_last(opt_chains, last_key, "psf_energy needs")
+        psf_energy.check(nb, int(gridsize))
     if otf:
         if not sync:
             raise ValueError("'mtf' / 'otf' outputs and mtf_cuts synchronise: they cannot be combined with sync=False")
@@ -1542,7 +1566,7 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
                 raise ValueError("detector_origin must be finite")
     det = None if detector is None else _DetectorRequest(detector, detector_weights, origins, isinstance(detector_origin, str))
     # (in the order in which they are attached: a blur rewrites the kept PSFs, so it goes before everything that reads them)
-    products = [p for p in (psf_blur, det, otf, psf_zoom) if p]
+    products = [p for p in (psf_blur, psf_energy, det, otf, psf_zoom) if p]
     keep_psf = keep_psf or any(p.reads_psf for p in products)
     fields = _fields_of(field, nb)
     states = [_Item(pupil_diameter, wl, gridsize, zoom, f) for wl, f in zip(wavelengths, fields)]
