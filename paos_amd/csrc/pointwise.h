@@ -10,21 +10,20 @@
 //   lens      -> wfo.py:359-366 (the scalar pilot-beam part stays on the host)
 //   zernikes  -> wfo.py:620-652 + paos/classes/zernike.py:85-109,245-247
 //   amplitude / phase / intensity -> wfo.py:166-172, paos/core/plot.py:125-130
+//
+// What several kernels must agree on is written once and called:
+//   ItemWindow (item_window.h)  the rows x columns box of a lean step: the start kernels write it (dense walk), the two
+//                               summing kernels read it (filtered walk), zero_outside_box_kernel clears its complement
+//   StartItem / start_value     what a start stores at a pixel: the four start kernels
+//   rotated                     one member's value turned by exp(i turns / lambda): zernike_kernel, zernike_start_write_kernel
+//   store_block_sum             how a reduction kernel ends
+//   MaskLineGeom, line_weight, window_fit, extents_from_windows, close_record
+//                               the aperture line records: one geometry, one pixel rule, one window fit for every renderer
 #pragma once
 #include "frugal_pass.h"
+#include "item_window.h"
 
 namespace paos {
-
-// memory index (inside one item) -> (row, col); false for pitch-padding slots
-template <int BR, int BC>
-__device__ __forceinline__ bool layout_unmap(size_t m, int n, unsigned pitch, int& row, int& col) {
-  const unsigned brow = (unsigned)(m / pitch), rem = (unsigned)(m % pitch);
-  if (rem >= (unsigned)n * BR) return false;
-  const unsigned in = rem % (BR * BC);
-  row = (int)(brow * BR + in / BC);
-  col = (int)((rem / (BR * BC)) * BC + in % BC);
-  return true;
-}
 
 constexpr int kPwThreads = 256;
 
@@ -254,9 +253,17 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {
   return s;  // valid in thread 0
 }
 
+// how a reduction kernel ends: this workgroup's sum goes to partial[item][workgroup] (blockIdx.y = item)
+__device__ __forceinline__ void store_block_sum(double acc, double* sh, double* partial) {
+  const double s = block_sum(acc, sh);
+  if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+
 // ``rows`` (optional, [batch][2]): rows of the item outside [lo, hi) are exact zeros (or hold stale data standing for
 // zeros) and are not read.  Block rows are contiguous in memory, so that is a window of the walk; every thread keeps
 // the elements it would have had, in the same order, and a zero adds nothing: the sum is bit-identical.
+// (round 5) ``cols``: columns outside [lo, hi) -- rounded outward to blocks -- are zero or stand for zeros: not read
+// (ItemWindow's filtered walk).
 template <typename T, int BR, int BC>
 __global__ void norm2_partial_kernel(const cx<T>* field, double* partial, int n, unsigned pitch,
                                      unsigned item_stride, const double* enable, int enable_stride,
@@ -265,31 +272,15 @@ __global__ void norm2_partial_kernel(const cx<T>* field, double* partial, int n,
   if (enable && enable[(size_t)item * enable_stride] == 0.0) return;
   __shared__ double sh[kPwThreads / 64];
   const cx<T>* f = field + (size_t)item * item_stride;
-  size_t total = item_stride, first = 0;
-  if (rows) {
-    first = (size_t)((int)rows[2 * item] / BR) * pitch;
-    total = (size_t)(((int)rows[2 * item + 1] + BR - 1) / BR) * pitch;
-    if (total > item_stride) total = item_stride;
-  }
+  const ItemWindow<BR, BC> win(rows, cols, item, n, pitch, item_stride);
   double acc = 0.0;
   const size_t step = (size_t)gridDim.x * blockDim.x;
-  size_t m = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (m < first) m += (first - m + step - 1) / step * step;
-  // (round 5) ``cols``: columns outside [lo, hi) -- rounded outward to blocks -- are zero or stand for zeros: not read
-  unsigned in_lo = 0, in_hi = (unsigned)n * BR;  // element offsets inside a block row
-  if (cols) {
-    in_lo = (unsigned)((int)cols[2 * item] / BC) * (BR * BC);
-    const unsigned h = (unsigned)(((int)cols[2 * item + 1] + BC - 1) / BC) * (BR * BC);
-    in_hi = h < in_hi ? h : in_hi;
-  }
-  for (; m < total; m += step) {
-    const unsigned off = (unsigned)(m % pitch);
-    if (off >= in_hi || off < in_lo) continue;  // pitch padding / outside the column window
+  for (size_t m = win.start((size_t)blockIdx.x * blockDim.x + threadIdx.x, step); m < win.total; m += step) {
+    if (win.skips(m)) continue;  // pitch padding / outside the column window
     const double x = (double)f[m].x, y = (double)f[m].y;
     acc += __dadd_rn(__dmul_rn(x, x), __dmul_rn(y, y));
   }
-  const double s = block_sum(acc, sh);
-  if (threadIdx.x == 0) partial[(size_t)item * gridDim.x + blockIdx.x] = s;
+  store_block_sum(acc, sh, partial);
 }
 
 // intensity_kernel that also leaves the partial sums of sum |u|^2 norm2_partial_kernel would (same grid,
@@ -312,8 +303,7 @@ __global__ void intensity_power_kernel(const cx<T>* field, double* out, double* 
     o[m] = v;
     acc += v;
   }
-  const double s = block_sum(acc, sh);
-  if (threadIdx.x == 0) partial[(size_t)item * gridDim.x + blockIdx.x] = s;
+  store_block_sum(acc, sh, partial);
 }
 
 // ``source`` (optional): item whose partial sums make up this item's result (identical inputs, summed once)
@@ -621,29 +611,57 @@ __global__ void aperture_kernel(cx<T>* field, const double* params, const double
 // the constant `value`.  Stage 1 sums |value w|^2 from the weights alone (no HBM traffic), stage 2
 // (norm2_final_kernel) orders the partial sums, stage 3 writes value * w [* 1/sqrt(norm)] once:
 // 16 B/px instead of fill 16 + aperture ~8 + norm 16 + scale 32.
+//
+// What a start stores at a pixel of weight w, read back the way zernike_kernel / norm2_partial_kernel read it: the same
+// roundings as fill -> aperture_kernel -> stop_scale_kernel, via the field's type
+template <typename T>
+__device__ __forceinline__ cx<double> start_value(double w, double v0re, double v0im, bool scaled, double s) {
+  double x = w == 1.0 ? v0re : (w == 0.0 ? 0.0 : (double)(T)__dmul_rn(v0re, w));
+  double y = w == 1.0 ? v0im : (w == 0.0 ? 0.0 : (double)(T)__dmul_rn(v0im, w));
+  if (scaled) { x = __dmul_rn(x, s); y = __dmul_rn(y, s); }
+  return {(double)(T)x, (double)(T)y};
+}
+
+// One item of a start: its aperture, the constant it starts from and, if ``scaled`` (the item's stop flag is set), the
+// scale 1 / sqrt(norm2[item]) from the sums of start_power_kernel, put in order.  start_power_kernel itself sums the
+// unscaled value.
+template <typename T, int SHAPE>
+struct StartItem {
+  ApertureEval<SHAPE> ap;
+  bool on, scaled;
+  double s, v0re, v0im;
+
+  __device__ __forceinline__ StartItem(const double* params, int item, double vre, double vim, bool scaled_, const double* norm2) {
+    const double* p = params + (size_t)item * AP_STRIDE;
+    ap.init(p, p + AP_THETA);
+    on = p[AP_ENABLE] != 0.0;
+    scaled = scaled_;
+    s = scaled ? 1.0 / sqrt(norm2[item]) : 1.0;
+    v0re = (double)(T)vre; v0im = (double)(T)vim;  // what fill stores
+  }
+  __device__ __forceinline__ cx<double> value(int r, int c) const {
+    return start_value<T>(on ? ap.weight(ap.mask(r, c)) : 1.0, v0re, v0im, scaled, s);
+  }
+};
+
 template <typename T, int BR, int BC, int SHAPE>
 __global__ void start_power_kernel(const double* params, int n, unsigned pitch, unsigned item_stride,
                                    double vre, double vim, double* partial, const double* stop) {
   const int item = blockIdx.y;
   if (stop[item] == 0.0) return;
   __shared__ double sh[kPwThreads / 64];
-  const double* p = params + (size_t)item * AP_STRIDE;
-  ApertureEval<SHAPE> ap;
-  ap.init(p, p + AP_THETA);
-  const bool on = p[AP_ENABLE] != 0.0;
-  const double v0re = (double)(T)vre, v0im = (double)(T)vim;  // what fill stores
+  const StartItem<T, SHAPE> start(params, item, vre, vim, false, nullptr);
   const size_t total = item_stride;
   double acc = 0.0;
   size_t m = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (; m < total; m += (size_t)gridDim.x * blockDim.x) {
     int r, c;
     if (!layout_unmap<BR, BC>(m, n, pitch, r, c)) continue;
-    const double w = on ? ap.weight(ap.mask(r, c)) : 1.0;
     // the value aperture_kernel leaves in the field, read back the way norm2_partial_kernel does
-    const double x = w == 1.0 ? v0re : (w == 0.0 ? 0.0 : (double)(T)__dmul_rn(v0re, w));
-    const double y = w == 1.0 ? v0im : (w == 0.0 ? 0.0 : (double)(T)__dmul_rn(v0im, w));
-    acc += __dadd_rn(__dmul_rn(x, x), __dmul_rn(y, y));
+    const cx<double> u = start.value(r, c);
+    acc += __dadd_rn(__dmul_rn(u.x, u.x), __dmul_rn(u.y, u.y));
   }
+  // (store_block_sum, spelled out: through the helper the fp64 ellipse build spills one scalar register more)
   const double s = block_sum(acc, sh);
   if (threadIdx.x == 0) partial[(size_t)item * gridDim.x + blockIdx.x] = s;
 }
@@ -660,44 +678,18 @@ __global__ void start_write_kernel(cx<T>* field, const double* params, int n, un
   const int glen = (int)grp_len[item];
   if (glen == 0) return;
   const double* members = grp_members + (int)grp_off[item];
-  const double* p = params + (size_t)item * AP_STRIDE;
-  ApertureEval<SHAPE> ap;
-  ap.init(p, p + AP_THETA);
-  const bool on = p[AP_ENABLE] != 0.0;
-  const bool scaled = stop[item] != 0.0;
-  const double s = scaled ? 1.0 / sqrt(norm2[item]) : 1.0;
-  const double v0re = (double)(T)vre, v0im = (double)(T)vim;
+  const StartItem<T, SHAPE> start(params, item, vre, vim, stop[item] != 0.0, norm2);
   // ``rows`` ([batch][2], optional): only the rows [lo, hi) are written; the others are left as they are and stand
   // for zeros (paos_start_rows: the caller promises that nobody reads them before a pass program consumes them)
-  size_t total = item_stride, first = 0;
-  if (rows) {
-    first = (size_t)((int)rows[2 * item] / BR) * pitch;
-    total = (size_t)(((int)rows[2 * item + 1] + BR - 1) / BR) * pitch;
-    if (total > item_stride) total = item_stride;
-  }
-  // (round 5) ``cols``: only the columns [lo, hi) -- whole blocks -- of those rows are written: the walk covers the
-  // in-window part of every block row, `span` elements starting `in_lo` elements into it
-  unsigned in_lo = 0, span = pitch;
-  if (cols) {
-    in_lo = (unsigned)((int)cols[2 * item] / BC) * (BR * BC);
-    unsigned h = (unsigned)(((int)cols[2 * item + 1] + BC - 1) / BC) * (BR * BC);
-    if (h > (unsigned)n * BR) h = (unsigned)n * BR;
-    span = h > in_lo ? h - in_lo : 0;
-  }
-  const size_t nbr = (total - first) / pitch;  // block rows to write
-  const size_t work = cols ? nbr * span : total - first;
+  // (round 5) ``cols``: only the columns [lo, hi) -- whole blocks -- of those rows are written: ItemWindow's dense walk
+  const ItemWindow<BR, BC> win(rows, cols, item, n, pitch, item_stride);
+  const size_t work = win.work();
   for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < work; j += (size_t)gridDim.x * blockDim.x) {
-    const size_t m = cols ? first + (j / span) * pitch + in_lo + (j % span) : first + j;
+    const size_t m = win.element(j);
     int r, c;
-    double x = 0.0, y = 0.0;
-    if (layout_unmap<BR, BC>(m, n, pitch, r, c)) {
-      const double w = on ? ap.weight(ap.mask(r, c)) : 1.0;
-      // the same roundings as fill -> aperture_kernel -> stop_scale_kernel, via the field's type
-      x = w == 1.0 ? v0re : (w == 0.0 ? 0.0 : (double)(T)__dmul_rn(v0re, w));
-      y = w == 1.0 ? v0im : (w == 0.0 ? 0.0 : (double)(T)__dmul_rn(v0im, w));
-      if (scaled) { x = __dmul_rn(x, s); y = __dmul_rn(y, s); }
-    }
-    for (int g = 0; g < glen; ++g) field[(size_t)(int)members[g] * item_stride + m] = {(T)x, (T)y};
+    cx<double> u = {0.0, 0.0};
+    if (layout_unmap<BR, BC>(m, n, pitch, r, c)) u = start.value(r, c);
+    for (int g = 0; g < glen; ++g) field[(size_t)(int)members[g] * item_stride + m] = {(T)u.x, (T)u.y};
   }
 }
 
@@ -707,13 +699,12 @@ template <typename T, int BR, int BC>
 __global__ void zero_outside_box_kernel(cx<T>* field, int n, unsigned pitch, unsigned item_stride, const double* rows,
                                         const double* cols) {
   const int item = blockIdx.y;
-  const int rlo = ((int)rows[2 * item] / BR) * BR, rhi = (((int)rows[2 * item + 1] + BR - 1) / BR) * BR;
-  const int clo = cols ? ((int)cols[2 * item] / BC) * BC : 0, chi = cols ? (((int)cols[2 * item + 1] + BC - 1) / BC) * BC : n;
+  const ItemWindow<BR, BC> win(rows, cols, item, n, pitch, item_stride);
   cx<T>* f = field + (size_t)item * item_stride;
   for (size_t m = (size_t)blockIdx.x * blockDim.x + threadIdx.x; m < item_stride; m += (size_t)gridDim.x * blockDim.x) {
     int r, c;
     if (!layout_unmap<BR, BC>(m, n, pitch, r, c)) continue;
-    if (r < rlo || r >= rhi || c < clo || c >= chi) f[m] = {(T)0, (T)0};
+    if (win.outside(r, c)) f[m] = {(T)0, (T)0};
   }
 }
 
@@ -752,106 +743,155 @@ struct MaskJobs {
   int* overflow;
 };
 
-// one line by the 64 lanes of a wave (the whole wave calls it: ballots, a wave-private LDS cache)
+// The theta = 0 geometry of one item's aperture, as every renderer below needs it.  (Rectangles: obscurations never get
+// here, the weight is the mask.)
+template <int SHAPE>
+struct MaskLineGeom {
+  double xc, yc, a, b, hw, hh, full_disk, w_in, w_out;
+  bool obsc;
+  int subpix;
+  ApertureBox box;
+
+  // false: the item has no aperture of this shape -- nothing to render
+  __device__ __forceinline__ bool init(const MaskJobs& jobs, const MaskJob& jb, int item) {
+    const double* p = jb.params + (size_t)item * jobs.param_stride;
+    const double* p2 = jb.params + jobs.batch_stride + (size_t)item * jobs.param_stride;
+    if (p[AP_ENABLE] == 0.0 || SHAPE != (int)p2[3]) return false;
+    xc = p[AP_XC]; yc = p[AP_YC]; a = p[AP_A]; b = p[AP_B];
+    obsc = SHAPE == 0 && p2[1] != 0.0;
+    subpix = (int)p2[2];
+    w_in = obsc ? 0.0 : 1.0; w_out = obsc ? 1.0 : 0.0;
+    double xe, ye;
+    hw = hh = full_disk = 0.0;
+    if (SHAPE == 0) {
+      xe = sqrt(__dmul_rn(a, a));  // cos 0 = 1, sin 0 = 0: the theta = 0 form of aperture_kernel's extents
+      ye = sqrt(__dmul_rn(b, b));
+      full_disk = fmin(__dmul_rn(__dmul_rn(3.141592653589793, a), b), 1.0);
+    } else {
+      hw = a / 2.0; hh = b / 2.0;
+      xe = fabs(hw); ye = fabs(hh);
+    }
+    box = make_box(xc, yc, xe, ye);
+    return true;
+  }
+  // the bounding box along a line of `axis`, and whether the line meets it
+  __device__ __forceinline__ int lo(int axis) const { return axis == 0 ? box.ixmin : box.iymin; }
+  __device__ __forceinline__ int hi(int axis) const { return axis == 0 ? box.ixmax : box.iymax; }
+  __device__ __forceinline__ bool in_box(int axis, int line) const {
+    return axis == 0 ? (line >= box.iymin && line < box.iymax) : (line >= box.ixmin && line < box.ixmax);
+  }
+  // rectangle: the factor of the line itself (`lm`), the count of the other axis over S
+  __device__ __forceinline__ double line_factor(int axis, int line) const {
+    const int c_other = axis == 0 ? subpixel_count_1d(line, yc, hh, subpix) : subpixel_count_1d(line, xc, hw, subpix);
+    return (double)c_other / (double)subpix;
+  }
+  // ellipse: x'^2 + y'^2 of the point `al` along and `ac` across the line from the centre, summed in ellipse_pixel's order
+  __device__ __forceinline__ double sum2(int axis, double al, double ac) const {
+    const double u = al / (axis == 0 ? a : b), v = ac / (axis == 0 ? b : a);
+    return axis == 0 ? __dadd_rn(__dmul_rn(u, u), __dmul_rn(v, v)) : __dadd_rn(__dmul_rn(v, v), __dmul_rn(u, u));
+  }
+};
+
+// The weight a record holds for position `pos` of line `line`: aperture_kernel's per-pixel functions -- the exact overlap
+// of an ellipse [1 - ... for an obscuration], the count of the line's axis over S of a rectangle
+template <int SHAPE>
+__device__ __forceinline__ double line_weight(const MaskLineGeom<SHAPE>& g, int axis, int line, int pos) {
+  const int c = axis == 0 ? pos : line, r = axis == 0 ? line : pos;
+  double mask = 0.0;
+  if (c >= g.box.ixmin && c < g.box.ixmax && r >= g.box.iymin && r < g.box.iymax) {
+    if (SHAPE == 0) mask = ellipse_pixel(c, r, g.xc, g.yc, g.a, g.b, 1.0, 0.0, g.full_disk);
+    else mask = (double)(axis == 0 ? subpixel_count_1d(c, g.xc, g.hw, g.subpix) : subpixel_count_1d(r, g.yc, g.hh, g.subpix)) / (double)g.subpix;
+  }
+  return g.obsc ? __dsub_rn(1.0, mask) : mask;
+}
+
+// A record's four extents: first non-out, first in, last in + 1, last non-out + 1
+struct LineExtents {
+  int p0, p1, p2i, p3;
+};
+
+// Close a record: a line that never leaves w_out is empty, one without interior is a single partial run [p0, p3), and
+// partial runs that do not fit kMaskW are counted in jobs.overflow (by `leader`, for `lines` lines) and dropped
+__device__ __forceinline__ void close_record(LineExtents& e, int* overflow, bool leader, int lines = 1) {
+  if (e.p3 <= e.p0) { e.p0 = e.p1 = e.p2i = e.p3 = 0; }
+  else if (e.p1 < 0) { e.p1 = e.p2i = e.p3; }
+  if (e.p1 - e.p0 > kMaskW || e.p3 - e.p2i > kMaskW) {
+    if (leader) atomicAdd(overflow, lines);
+    e.p0 = e.p1 = e.p2i = e.p3 = 0;
+  }
+}
+
+// Round 4: the two boundary windows of the chord at once.  The partially covered pixels of a line lie where the ellipse
+// crosses the strip of the line: between the chord at the strip's edge nearer the centre and the chord at its far edge, on
+// either side.  When both of these runs fit W pixels (with a margin of M) one evaluation of the exact overlap per window
+// pixel is all the line needs: the rest of it is classified by the two rectangle tests the scan's chunks use (exactly
+// consistent with the per-pixel rule), applied to the span between the windows (the four outer corners inside the
+// ellipse => every pixel of it is, monotone) and to the two spans outside them (the nearest point of each outside by a
+// margin no rounding bridges).  True: the windows [wl0, wl0 + W) and [wr0, wr0 + W) are exact for this line, which lies
+// inside the box; false: a window too wide or a test that does not hold -- the caller takes wider windows or the scan.
+template <int W, int M>
+__device__ __forceinline__ bool window_fit(const MaskLineGeom<0>& g, int axis, int line, int n, int& wl0, int& wr0) {
+  const double sa = axis == 0 ? g.a : g.b, sc = axis == 0 ? g.b : g.a;          // semi-axes along / across the line
+  const double ca = axis == 0 ? g.xc : g.yc, cc = axis == 0 ? g.yc : g.xc;      // centre along / across
+  const double lo_c = __dsub_rn((double)line - 0.5, cc), hi_c = __dsub_rn((double)line + 0.5, cc);
+  const double near_c = (lo_c > 0.0 ? lo_c : (hi_c < 0.0 ? -hi_c : 0.0)) / sc;   // strip edge nearer the centre
+  const double far_c = fmax(fabs(lo_c), fabs(hi_c)) / sc;
+  const double half_long = near_c < 1.0 ? sa * sqrt(1.0 - near_c * near_c) : 0.0;
+  const double half_short = far_c < 1.0 ? sa * sqrt(1.0 - far_c * far_c) : 0.0;
+  const int box_lo = max(0, g.lo(axis)), box_hi = min(n, g.hi(axis));
+  wl0 = max(box_lo, (int)floor(ca - half_long) - M);
+  const int wl1 = (int)ceil(ca - half_short) + M;                    // left run: [wl0, wl1]
+  const int wr1 = min(box_hi - 1, (int)ceil(ca + half_long) + M);   // right run: [wr_need, wr1]
+  wr0 = wr1 - (W - 1);
+  const int wr_need = (int)floor(ca + half_short) - M;
+  bool ok = wl1 - wl0 < W && wr_need >= wr0 && wl0 + W <= wr0 && half_long > 0.0;
+  if (ok) {
+    const double ia = __dsub_rn((double)(wl0 + W) - 0.5, ca), ib = __dsub_rn((double)(wr0 - 1) + 0.5, ca);
+    ok = g.sum2(axis, ia, lo_c) <= 1.0 && g.sum2(axis, ib, lo_c) <= 1.0 && g.sum2(axis, ia, hi_c) <= 1.0 && g.sum2(axis, ib, hi_c) <= 1.0;
+    const double nc = lo_c > 0.0 ? lo_c : (hi_c < 0.0 ? hi_c : 0.0);
+    if (ok && wl0 > box_lo) {
+      const double hi_a = __dsub_rn((double)(wl0 - 1) + 0.5, ca);
+      ok = hi_a < 0.0 && g.sum2(axis, hi_a, nc) > 1.0 + 1.0e-9;
+    }
+    if (ok && wr1 + 1 < box_hi) {
+      const double lo_a = __dsub_rn((double)(wr1 + 1) - 0.5, ca);
+      ok = lo_a > 0.0 && g.sum2(axis, lo_a, nc) > 1.0 + 1.0e-9;
+    }
+  }
+  return ok;
+}
+
+// The scan's four extents over: left window | span | right window.  no_* / in_*: the window pixels that are not w_out /
+// are w_in, bit k = pixel k of the window; the span [wl0 + W, wr0) between them is w_in throughout (empty when equal).
+template <int W>
+__device__ __forceinline__ LineExtents extents_from_windows(unsigned no_l, unsigned no_r, unsigned in_l, unsigned in_r, int wl0, int wr0, int n) {
+  const int i0 = wl0 + W, i1 = wr0;
+  LineExtents e;
+  e.p0 = no_l ? wl0 + (__ffs((int)no_l) - 1) : (i0 < i1 ? i0 : (no_r ? wr0 + (__ffs((int)no_r) - 1) : n));
+  e.p3 = no_r ? wr0 + 32 - __clz((int)no_r) : (i0 < i1 ? i1 : (no_l ? wl0 + 32 - __clz((int)no_l) : 0));
+  e.p1 = in_l ? wl0 + (__ffs((int)in_l) - 1) : (i0 < i1 ? i0 : (in_r ? wr0 + (__ffs((int)in_r) - 1) : -1));
+  e.p2i = in_r ? wr0 + 32 - __clz((int)in_r) : (i0 < i1 ? i1 : (in_l ? wl0 + 32 - __clz((int)in_l) : -1));
+  return e;
+}
+
+// One line by the 64 lanes of a wave, scanned (the whole wave calls it: ballots, a wave-private LDS cache): the line is
+// walked 64 pixels at a time over the box's extent.  What every line gets that the windows below cannot render, and every
+// line of a rectangle outside mask_rect_block_render.
 template <int SHAPE>
 __device__ void mask_line_render(const MaskJobs& jobs, const MaskJob& jb, int item, int line, int lane) {
-  const int n = jobs.n, axis = jb.axis, param_stride = jobs.param_stride;
-  int* const overflow = jobs.overflow;
+  const int n = jobs.n, axis = jb.axis;
   if (line >= jb.line_end || line >= n) return;
-  const double* p = jb.params + (size_t)item * param_stride;
-  const double* p2 = jb.params + jobs.batch_stride + (size_t)item * param_stride;
+  MaskLineGeom<SHAPE> g;
+  if (!g.init(jobs, jb, item)) return;
   MaskLine* out = jb.lines + (size_t)item * n + line;
   double* vout = jb.vals + ((size_t)item * n + line) * (2 * kMaskW);
-  if (p[AP_ENABLE] == 0.0 || SHAPE != (int)p2[3]) return;
-  const double xc = p[AP_XC], yc = p[AP_YC], a = p[AP_A], b = p[AP_B];
-  const bool obsc = p2[1] != 0.0;
-  const int subpix = (int)p2[2];
-  const double w_in = obsc ? 0.0 : 1.0, w_out = obsc ? 1.0 : 0.0;
-  double xe, ye, hw = 0.0, hh = 0.0, full_disk = 0.0, lm = 1.0;
-  if (SHAPE == 0) {
-    xe = sqrt(__dmul_rn(a, a));  // cos 0 = 1, sin 0 = 0: the theta = 0 form of aperture_kernel's extents
-    ye = sqrt(__dmul_rn(b, b));
-    full_disk = fmin(__dmul_rn(__dmul_rn(3.141592653589793, a), b), 1.0);
-  } else {
-    hw = a / 2.0; hh = b / 2.0;
-    xe = fabs(hw); ye = fabs(hh);
-  }
-  const ApertureBox box = make_box(xc, yc, xe, ye);
-  if (SHAPE == 1) {
-    const int c_other = axis == 0 ? subpixel_count_1d(line, yc, hh, subpix) : subpixel_count_1d(line, xc, hw, subpix);
-    const bool in_box = axis == 0 ? (line >= box.iymin && line < box.iymax) : (line >= box.ixmin && line < box.ixmax);
-    lm = in_box ? (double)c_other / (double)subpix : 0.0;
-  }
-  int p0 = n, p1 = -1, p2i = -1, p3 = 0;  // first non-out, first in, last in + 1, last non-out + 1
   // Only the part of the line inside the bounding box can differ from w_out: lines that miss
   // the box are done, the others are scanned over the box's extent along the line only.
-  const bool line_in_box = axis == 0 ? (line >= box.iymin && line < box.iymax) : (line >= box.ixmin && line < box.ixmax);
-  const int scan_lo = line_in_box ? max(0, (axis == 0 ? box.ixmin : box.iymin)) & ~63 : 0;
-  const int scan_hi = line_in_box ? min(n, axis == 0 ? box.ixmax : box.iymax) : 0;
-  // Round 4: the two boundary windows of the chord at once.  The partially covered pixels of a line lie where the
-  // ellipse crosses the strip of the line: between the chord at the strip's edge nearer the centre and the chord at its
-  // far edge, on either side.  When both of these runs fit 32 pixels (with a margin of 3; every line but the few near
-  // the tips of the ellipse), lanes 0-31 evaluate the exact overlap of the left window and lanes 32-63 of the right one
-  // -- ONE evaluation of ellipse_pixel per line instead of one per 64-pixel chunk that touches the boundary (2-4) --
-  // and the rest of the line is classified by the same two rectangle tests the chunks use (see below: exactly
-  // consistent with the per-pixel rule), applied to the span between the windows (inside) and to the two spans
-  // outside them (outside).  Whatever fails -- a window too wide, a test that does not hold -- takes the scan below.
-  // Records are identical to the scan's bit for bit (tests/test_gpu_r4.py, PAOS_MASK_SCAN=1 forces the scan).
-  if (SHAPE == 0 && line_in_box && jobs.windows != 0) {
-    const double sa = axis == 0 ? a : b, sc = axis == 0 ? b : a;          // semi-axes along / across the line
-    const double ca = axis == 0 ? xc : yc, cc = axis == 0 ? yc : xc;      // centre along / across
-    const double lo_c = __dsub_rn((double)line - 0.5, cc), hi_c = __dsub_rn((double)line + 0.5, cc);
-    const double near_c = (lo_c > 0.0 ? lo_c : (hi_c < 0.0 ? -hi_c : 0.0)) / sc;   // strip edge nearer the centre
-    const double far_c = fmax(fabs(lo_c), fabs(hi_c)) / sc;
-    const double half_long = near_c < 1.0 ? sa * sqrt(1.0 - near_c * near_c) : 0.0;
-    const double half_short = far_c < 1.0 ? sa * sqrt(1.0 - far_c * far_c) : 0.0;
-    const int box_lo = max(0, axis == 0 ? box.ixmin : box.iymin), box_hi = min(n, axis == 0 ? box.ixmax : box.iymax);
-    const int wl0 = max(box_lo, (int)floor(ca - half_long) - 3), wl1 = (int)ceil(ca - half_short) + 3;   // [wl0, wl1]
-    const int wr1 = min(box_hi - 1, (int)ceil(ca + half_long) + 3), wr0 = wr1 - 31;                       // [wr0, wr1]
-    const int wr_need = (int)floor(ca + half_short) - 3;
-    auto sum2 = [&](double al, double ac) { const double u = al / sa, v = ac / sc; return axis == 0 ? __dadd_rn(__dmul_rn(u, u), __dmul_rn(v, v)) : __dadd_rn(__dmul_rn(v, v), __dmul_rn(u, u)); };
-    bool ok = wl1 - wl0 < 32 && wr_need >= wr0 && wl0 + 32 <= wr0 && half_long > 0.0;
-    if (ok) {
-      // between the windows: the four outer corners of the span inside the ellipse => every pixel of it is (monotone)
-      const double ia = __dsub_rn((double)(wl0 + 32) - 0.5, ca), ib = __dsub_rn((double)(wr0 - 1) + 0.5, ca);
-      ok = sum2(ia, lo_c) <= 1.0 && sum2(ib, lo_c) <= 1.0 && sum2(ia, hi_c) <= 1.0 && sum2(ib, hi_c) <= 1.0;
-      // left of the left window and right of the right one: the nearest point of each span outside by a margin
-      const double nc = lo_c > 0.0 ? lo_c : (hi_c < 0.0 ? hi_c : 0.0);
-      if (ok && wl0 > box_lo) {
-        const double hi_a = __dsub_rn((double)(wl0 - 1) + 0.5, ca);
-        ok = hi_a < 0.0 && sum2(hi_a, nc) > 1.0 + 1.0e-9;
-      }
-      if (ok && wr1 + 1 < box_hi) {
-        const double lo_a = __dsub_rn((double)(wr1 + 1) - 0.5, ca);
-        ok = lo_a > 0.0 && sum2(lo_a, nc) > 1.0 + 1.0e-9;
-      }
-    }
-    if (ok) {  // wave-uniform
-      const int pos = lane < 32 ? wl0 + lane : wr0 + (lane - 32);
-      const int c = axis == 0 ? pos : line, r = axis == 0 ? line : pos;
-      double mask = 0.0;
-      if (c >= box.ixmin && c < box.ixmax && r >= box.iymin && r < box.iymax) mask = ellipse_pixel(c, r, xc, yc, a, b, 1.0, 0.0, full_disk);
-      const double w = obsc ? __dsub_rn(1.0, mask) : mask;
-      const unsigned long long not_out = __ballot(w != w_out), is_in = __ballot(w == w_in);
-      const unsigned no_l = (unsigned)not_out, no_r = (unsigned)(not_out >> 32), in_l = (unsigned)is_in, in_r = (unsigned)(is_in >> 32);
-      const int i0 = wl0 + 32, i1 = wr0;  // the span between the windows: w_in throughout (i0 <= i1; empty when equal)
-      // the scan's four extents over: left window | span | right window
-      p0 = no_l ? wl0 + (__ffs((int)no_l) - 1) : (i0 < i1 ? i0 : (no_r ? wr0 + (__ffs((int)no_r) - 1) : n));
-      p3 = no_r ? wr0 + 32 - __clz((int)no_r) : (i0 < i1 ? i1 : (no_l ? wl0 + 32 - __clz((int)no_l) : 0));
-      p1 = in_l ? wl0 + (__ffs((int)in_l) - 1) : (i0 < i1 ? i0 : (in_r ? wr0 + (__ffs((int)in_r) - 1) : -1));
-      p2i = in_r ? wr0 + 32 - __clz((int)in_r) : (i0 < i1 ? i1 : (in_l ? wl0 + 32 - __clz((int)in_l) : -1));
-      if (p3 <= p0) { p0 = p1 = p2i = p3 = 0; }
-      else if (p1 < 0) { p1 = p2i = p3; }
-      if (p1 - p0 > kMaskW || p3 - p2i > kMaskW) {
-        if (lane == 0) atomicAdd(overflow, 1);
-        p0 = p1 = p2i = p3 = 0;
-      }
-      if (pos >= p0 && pos < p1) vout[pos - p0] = w;
-      if (pos >= p2i && pos < p3) vout[kMaskW + pos - p2i] = w;
-      if (lane == 0) *out = {p0, p1, p2i, p3, lm, 0.0};
-      return;
-    }
-  }
+  const bool line_in_box = g.in_box(axis, line);
+  const double lm = SHAPE == 1 ? (line_in_box ? g.line_factor(axis, line) : 0.0) : 1.0;
+  const int scan_lo = line_in_box ? max(0, g.lo(axis)) & ~63 : 0;
+  const int scan_hi = line_in_box ? min(n, g.hi(axis)) : 0;
+  LineExtents e = {n, -1, -1, 0};
   // pass 1: extents.  Chunks of 64 pixels that hold partially covered pixels keep their weights in
   // a small per-wave LDS cache, so that pass 2 does not evaluate the exact overlap a second time.
   constexpr int kCache = 6;                           // chunks per line (two edge zones, a few chunks each)
@@ -860,9 +900,6 @@ __device__ void mask_line_render(const MaskJobs& jobs, const MaskJob& jb, int it
   const int wave = threadIdx.x >> 6;
   int ncache = 0;
   for (int base = scan_lo; base < scan_hi; base += 64) {
-    const int pos = base + lane;
-    const int c = axis == 0 ? pos : line, r = axis == 0 ? line : pos;
-    double mask = 0.0;
     // Whole chunks inside or outside the ellipse (wave-uniform tests on the chunk's rectangle, theta = 0):
     //  * inside: ellipse_pixel returns exactly 1 when the four corners of a pixel pass x'^2 + y'^2 <= 1; along a
     //    row edge that sum is a monotone function of |x'| also in floating point (every operation rounds
@@ -872,32 +909,24 @@ __device__ void mask_line_render(const MaskJobs& jobs, const MaskJob& jb, int it
     // A line through the middle of a 1024-pixel pupil evaluates 2-4 chunks instead of 16.
     int chunk = 0;  // 0: per pixel, 1: all inside, 2: all outside
     if (SHAPE == 0) {
-      const double lo_a = __dsub_rn((double)base - 0.5, axis == 0 ? xc : yc), hi_a = __dsub_rn((double)(base + 63) + 0.5, axis == 0 ? xc : yc);
-      const double lo_c = __dsub_rn((double)line - 0.5, axis == 0 ? yc : xc), hi_c = __dsub_rn((double)line + 0.5, axis == 0 ? yc : xc);
-      const double sa = axis == 0 ? a : b, sc = axis == 0 ? b : a;  // semi-axes along / across the line
-      auto sum2 = [&](double al, double ac) { const double u = al / sa, v = ac / sc; return axis == 0 ? __dadd_rn(__dmul_rn(u, u), __dmul_rn(v, v)) : __dadd_rn(__dmul_rn(v, v), __dmul_rn(u, u)); };
-      const bool whole = base >= (axis == 0 ? box.ixmin : box.iymin) && base + 64 <= (axis == 0 ? box.ixmax : box.iymax);
-      if (whole && sum2(lo_a, lo_c) <= 1.0 && sum2(hi_a, lo_c) <= 1.0 && sum2(lo_a, hi_c) <= 1.0 && sum2(hi_a, hi_c) <= 1.0) chunk = 1;
+      const double lo_a = __dsub_rn((double)base - 0.5, axis == 0 ? g.xc : g.yc), hi_a = __dsub_rn((double)(base + 63) + 0.5, axis == 0 ? g.xc : g.yc);
+      const double lo_c = __dsub_rn((double)line - 0.5, axis == 0 ? g.yc : g.xc), hi_c = __dsub_rn((double)line + 0.5, axis == 0 ? g.yc : g.xc);
+      const bool whole = base >= g.lo(axis) && base + 64 <= g.hi(axis);
+      if (whole && g.sum2(axis, lo_a, lo_c) <= 1.0 && g.sum2(axis, hi_a, lo_c) <= 1.0 && g.sum2(axis, lo_a, hi_c) <= 1.0 && g.sum2(axis, hi_a, hi_c) <= 1.0) chunk = 1;
       else {
         const double na = lo_a > 0.0 ? lo_a : (hi_a < 0.0 ? hi_a : 0.0), nc = lo_c > 0.0 ? lo_c : (hi_c < 0.0 ? hi_c : 0.0);
-        if (sum2(na, nc) > 1.0 + 1.0e-9) chunk = 2;
+        if (g.sum2(axis, na, nc) > 1.0 + 1.0e-9) chunk = 2;
       }
     }
-    if (chunk == 1) mask = 1.0;
-    else if (chunk == 0 && c >= box.ixmin && c < box.ixmax && r >= box.iymin && r < box.iymax) {
-      if (SHAPE == 0) mask = ellipse_pixel(c, r, xc, yc, a, b, 1.0, 0.0, full_disk);
-      else mask = (double)(axis == 0 ? subpixel_count_1d(c, xc, hw, subpix) : subpixel_count_1d(r, yc, hh, subpix)) / (double)subpix;
-    }
-    const double w = (SHAPE == 0 && obsc) ? __dsub_rn(1.0, mask) : mask;
-    const double wi = SHAPE == 0 ? w_in : 1.0, wo = SHAPE == 0 ? w_out : 0.0;
-    const unsigned long long not_out = __ballot(w != wo), is_in = __ballot(w == wi);
+    const double w = chunk == 0 ? line_weight(g, axis, line, base + lane) : (chunk == 1 ? g.w_in : g.w_out);
+    const unsigned long long not_out = __ballot(w != g.w_out), is_in = __ballot(w == g.w_in);
     if (not_out) {
-      p0 = min(p0, base + (int)__ffsll((long long)not_out) - 1);
-      p3 = max(p3, base + 64 - (int)__clzll((long long)not_out));
+      e.p0 = min(e.p0, base + (int)__ffsll((long long)not_out) - 1);
+      e.p3 = max(e.p3, base + 64 - (int)__clzll((long long)not_out));
     }
     if (is_in) {
-      if (p1 < 0) p1 = base + (int)__ffsll((long long)is_in) - 1;
-      p2i = base + 64 - (int)__clzll((long long)is_in);
+      if (e.p1 < 0) e.p1 = base + (int)__ffsll((long long)is_in) - 1;
+      e.p2i = base + 64 - (int)__clzll((long long)is_in);
     }
     if ((not_out & ~is_in) != 0 && ncache < kCache) {  // wave-uniform: some pixel is neither out nor in
       cache_w[wave][ncache][lane] = w;
@@ -909,106 +938,47 @@ __device__ void mask_line_render(const MaskJobs& jobs, const MaskJob& jb, int it
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  if (p3 <= p0) { p0 = p1 = p2i = p3 = 0; }           // the line never leaves w_out
-  else if (p1 < 0) { p1 = p2i = p3; }                  // no interior: one partial run [p0, p3)
-  if (p1 - p0 > kMaskW || p3 - p2i > kMaskW) {
-    if (lane == 0) atomicAdd(overflow, 1);
-    p0 = p1 = p2i = p3 = 0;
-  }
+  close_record(e, jobs.overflow, lane == 0);
   // pass 2: partial values, from the cache where the chunk was kept
   for (int side = 0; side < 2; ++side) {
-    const int lo = side == 0 ? p0 : p2i, hi = side == 0 ? p1 : p3;
+    const int lo = side == 0 ? e.p0 : e.p2i, hi = side == 0 ? e.p1 : e.p3;
     for (int pos = lo + lane; pos < hi; pos += 64) {
       int slot = -1;
       for (int k = 0; k < ncache; ++k)
         if (cache_base[wave][k] == (pos & ~63)) slot = k;
-      double w;
-      if (slot >= 0) {
-        w = cache_w[wave][slot][pos & 63];
-      } else {
-        const int c = axis == 0 ? pos : line, r = axis == 0 ? line : pos;
-        double mask = 0.0;
-        if (c >= box.ixmin && c < box.ixmax && r >= box.iymin && r < box.iymax) {
-          if (SHAPE == 0) mask = ellipse_pixel(c, r, xc, yc, a, b, 1.0, 0.0, full_disk);
-          else mask = (double)(axis == 0 ? subpixel_count_1d(c, xc, hw, subpix) : subpixel_count_1d(r, yc, hh, subpix)) / (double)subpix;
-        }
-        w = (SHAPE == 0 && obsc) ? __dsub_rn(1.0, mask) : mask;
-      }
-      vout[side * kMaskW + pos - lo] = w;
+      vout[side * kMaskW + pos - lo] = slot >= 0 ? cache_w[wave][slot][pos & 63] : line_weight(g, axis, line, pos);
     }
   }
-  if (lane == 0) *out = {p0, p1, p2i, p3, lm, 0.0};
+  if (lane == 0) *out = {e.p0, e.p1, e.p2i, e.p3, lm, 0.0};
 }
 
-// Round 5: TWO -- then FOUR -- lines per wave.  The window path above spends one exact-overlap evaluation per lane on 2 x 32
-// pixels of which two to four are partially covered; everywhere but near the tips of the ellipse the two boundary runs of a
-// line fit two 16-pixel windows (margins of 3) and, away from the last few per cent of the lines at either tip, two 8-pixel
-// windows (margins of 1: what makes a window exact are the tests below, not its margins).  LPW lines per wave: 64 / LPW lanes
-// render one line, the lower half of them its left window, the upper half its right one -- a half or a quarter of the waves,
-// the same per-pixel functions on the same pixels, the same span tests: records bit for bit those of the 32-pixel windows and
-// of the scan (tests/test_gpu_r4.py, PAOS_MASK_PAIRS=0 / 1, PAOS_MASK_SCAN=1).  Returns false (for the whole wave) when one
-// of the lines needs more: the caller then renders them with the next wider windows.
+// LPW lines of an ellipse per wave through two windows each (window_fit): 64 / LPW lanes render one line, the lower half of
+// them its left window, the upper half its right one -- ONE evaluation of ellipse_pixel per line instead of one per
+// 64-pixel chunk that touches the boundary (2-4).  Round 4: one line, two 32-pixel windows (margins of 3; every line but the
+// few near the tips of the ellipse).  Round 5: two lines through 16-pixel windows and, away from the last few per cent of the
+// lines at either tip, four through 8-pixel windows (margins of 1: what makes a window exact are window_fit's tests, not its
+// margins) -- a half or a quarter of the waves, the same per-pixel functions on the same pixels, the same span tests: records
+// bit for bit those of the scan whatever LPW (tests/test_gpu_r4.py, PAOS_MASK_PAIRS=0 / 1, PAOS_MASK_SCAN=1).  Returns false
+// (for the whole wave) when one of the lines needs more: the caller then renders them with the next wider windows, and
+// in the end with the scan.
 template <int LPW>
 __device__ inline bool mask_multi_render(const MaskJobs& jobs, const MaskJob& jb, int item, int first, int lane) {
   constexpr int G = 64 / LPW, W = G / 2, M = W >= 16 ? 3 : 1;  // lanes per line, pixels per window, margin
-  constexpr unsigned kWin = (1u << W) - 1u;
-  const int n = jobs.n, axis = jb.axis, param_stride = jobs.param_stride;
+  constexpr unsigned long long kWin = (1ull << W) - 1ull;      // (W = 32: the shifts below stay inside the 64-bit ballot)
+  const int n = jobs.n, axis = jb.axis;
   const int grp = lane / G, lg = lane % G;
   const int line = first + grp;
   const bool valid = line < jb.line_end && line < n;
-  const double* p = jb.params + (size_t)item * param_stride;
-  const double* p2 = jb.params + jobs.batch_stride + (size_t)item * param_stride;
-  if (p[AP_ENABLE] == 0.0 || 0 != (int)p2[3]) return true;  // (not this kernel's shape: nothing to render, as the line path decides)
-  const double xc = p[AP_XC], yc = p[AP_YC], a = p[AP_A], b = p[AP_B];
-  const bool obsc = p2[1] != 0.0;
-  const double w_in = obsc ? 0.0 : 1.0, w_out = obsc ? 1.0 : 0.0;
-  const double xe = sqrt(__dmul_rn(a, a)), ye = sqrt(__dmul_rn(b, b));
-  const double full_disk = fmin(__dmul_rn(__dmul_rn(3.141592653589793, a), b), 1.0);
-  const ApertureBox box = make_box(xc, yc, xe, ye);
-  const bool in_box = valid && (axis == 0 ? (line >= box.iymin && line < box.iymax) : (line >= box.ixmin && line < box.ixmax));
-  bool ok = false;
+  MaskLineGeom<0> g;
+  if (!g.init(jobs, jb, item)) return true;  // (not this kernel's shape: nothing to render, as the scan decides)
+  const bool in_box = valid && g.in_box(axis, line);
   int wl0 = 0, wr0 = 0;
-  if (in_box) {
-    const double sa = axis == 0 ? a : b, sc = axis == 0 ? b : a;          // semi-axes along / across the line
-    const double ca = axis == 0 ? xc : yc, cc = axis == 0 ? yc : xc;      // centre along / across
-    const double lo_c = __dsub_rn((double)line - 0.5, cc), hi_c = __dsub_rn((double)line + 0.5, cc);
-    const double near_c = (lo_c > 0.0 ? lo_c : (hi_c < 0.0 ? -hi_c : 0.0)) / sc;
-    const double far_c = fmax(fabs(lo_c), fabs(hi_c)) / sc;
-    const double half_long = near_c < 1.0 ? sa * sqrt(1.0 - near_c * near_c) : 0.0;
-    const double half_short = far_c < 1.0 ? sa * sqrt(1.0 - far_c * far_c) : 0.0;
-    const int box_lo = max(0, axis == 0 ? box.ixmin : box.iymin), box_hi = min(n, axis == 0 ? box.ixmax : box.iymax);
-    wl0 = max(box_lo, (int)floor(ca - half_long) - M);
-    const int wl1 = (int)ceil(ca - half_short) + M;
-    const int wr1 = min(box_hi - 1, (int)ceil(ca + half_long) + M);
-    wr0 = wr1 - (W - 1);
-    const int wr_need = (int)floor(ca + half_short) - M;
-    auto sum2 = [&](double al, double ac) { const double u = al / sa, v = ac / sc; return axis == 0 ? __dadd_rn(__dmul_rn(u, u), __dmul_rn(v, v)) : __dadd_rn(__dmul_rn(v, v), __dmul_rn(u, u)); };
-    ok = wl1 - wl0 < W && wr_need >= wr0 && wl0 + W <= wr0 && half_long > 0.0;
-    if (ok) {
-      const double ia = __dsub_rn((double)(wl0 + W) - 0.5, ca), ib = __dsub_rn((double)(wr0 - 1) + 0.5, ca);
-      ok = sum2(ia, lo_c) <= 1.0 && sum2(ib, lo_c) <= 1.0 && sum2(ia, hi_c) <= 1.0 && sum2(ib, hi_c) <= 1.0;
-      const double nc = lo_c > 0.0 ? lo_c : (hi_c < 0.0 ? hi_c : 0.0);
-      if (ok && wl0 > box_lo) {
-        const double hi_a = __dsub_rn((double)(wl0 - 1) + 0.5, ca);
-        ok = hi_a < 0.0 && sum2(hi_a, nc) > 1.0 + 1.0e-9;
-      }
-      if (ok && wr1 + 1 < box_hi) {
-        const double lo_a = __dsub_rn((double)(wr1 + 1) - 0.5, ca);
-        ok = lo_a > 0.0 && sum2(lo_a, nc) > 1.0 + 1.0e-9;
-      }
-    }
-  }
+  const bool ok = in_box && window_fit<W, M>(g, axis, line, n, wl0, wr0);
   // a line outside the loop's range or outside the bounding box needs no window at all
   if (!__all(!valid || !in_box || ok)) return false;  // wave-uniform
   const int pos = lg < W ? wl0 + lg : wr0 + (lg - W);
-  double w = w_out;
-  if (in_box) {
-    const int c = axis == 0 ? pos : line, r = axis == 0 ? line : pos;
-    double mask = 0.0;
-    if (c >= box.ixmin && c < box.ixmax && r >= box.iymin && r < box.iymax) mask = ellipse_pixel(c, r, xc, yc, a, b, 1.0, 0.0, full_disk);
-    w = obsc ? __dsub_rn(1.0, mask) : mask;
-  }
-  const unsigned long long not_out64 = __ballot(w != w_out), is_in64 = __ballot(w == w_in);
+  const double w = in_box ? line_weight(g, axis, line, pos) : g.w_out;
+  const unsigned long long not_out64 = __ballot(w != g.w_out), is_in64 = __ballot(w == g.w_in);
   if (!valid) return true;
   MaskLine* out = jb.lines + (size_t)item * n + line;
   double* vout = jb.vals + ((size_t)item * n + line) * (2 * kMaskW);
@@ -1016,22 +986,13 @@ __device__ inline bool mask_multi_render(const MaskJobs& jobs, const MaskJob& jb
     if (lg == 0) *out = {0, 0, 0, 0, 1.0, 0.0};
     return true;
   }
-  const unsigned not_out = (unsigned)(not_out64 >> (G * grp)), is_in = (unsigned)(is_in64 >> (G * grp));
-  const unsigned no_l = not_out & kWin, no_r = (not_out >> W) & kWin, in_l = is_in & kWin, in_r = (is_in >> W) & kWin;
-  const int i0 = wl0 + W, i1 = wr0;  // the span between the windows: w_in throughout
-  int p0 = no_l ? wl0 + (__ffs((int)no_l) - 1) : (i0 < i1 ? i0 : (no_r ? wr0 + (__ffs((int)no_r) - 1) : n));
-  int p3 = no_r ? wr0 + 32 - __clz((int)no_r) : (i0 < i1 ? i1 : (no_l ? wl0 + 32 - __clz((int)no_l) : 0));
-  int p1 = in_l ? wl0 + (__ffs((int)in_l) - 1) : (i0 < i1 ? i0 : (in_r ? wr0 + (__ffs((int)in_r) - 1) : -1));
-  int p2i = in_r ? wr0 + 32 - __clz((int)in_r) : (i0 < i1 ? i1 : (in_l ? wl0 + 32 - __clz((int)in_l) : -1));
-  if (p3 <= p0) { p0 = p1 = p2i = p3 = 0; }
-  else if (p1 < 0) { p1 = p2i = p3; }
-  if (p1 - p0 > kMaskW || p3 - p2i > kMaskW) {
-    if (lg == 0) atomicAdd(jobs.overflow, 1);
-    p0 = p1 = p2i = p3 = 0;
-  }
-  if (pos >= p0 && pos < p1) vout[pos - p0] = w;
-  if (pos >= p2i && pos < p3) vout[kMaskW + pos - p2i] = w;
-  if (lg == 0) *out = {p0, p1, p2i, p3, 1.0, 0.0};
+  const unsigned long long not_out = not_out64 >> (G * grp), is_in = is_in64 >> (G * grp);
+  LineExtents e = extents_from_windows<W>((unsigned)(not_out & kWin), (unsigned)((not_out >> W) & kWin), (unsigned)(is_in & kWin),
+                                          (unsigned)((is_in >> W) & kWin), wl0, wr0, n);
+  close_record(e, jobs.overflow, lg == 0);
+  if (pos >= e.p0 && pos < e.p1) vout[pos - e.p0] = w;
+  if (pos >= e.p2i && pos < e.p3) vout[kMaskW + pos - e.p2i] = w;
+  if (lg == 0) *out = {e.p0, e.p1, e.p2i, e.p3, 1.0, 0.0};
   return true;
 }
 
@@ -1041,50 +1002,36 @@ __device__ inline bool mask_multi_render(const MaskJobs& jobs, const MaskJob& jb
 // owns line first + l and forms its `lm`.  The same per-pixel function on the same pixels: records bit for bit those of
 // mask_line_render<1> (tests/test_gpu_r5.py, PAOS_MASK_RECT_BLOCKS=0).  `prof`: 2 kMaskW doubles of LDS of this wave.
 __device__ inline void mask_rect_block_render(const MaskJobs& jobs, const MaskJob& jb, int item, int first, int lane, double* prof) {
-  const int n = jobs.n, axis = jb.axis, param_stride = jobs.param_stride;
+  const int n = jobs.n, axis = jb.axis;
   if (first >= jb.line_end || first >= n) return;
-  const double* p = jb.params + (size_t)item * param_stride;
-  const double* p2 = jb.params + jobs.batch_stride + (size_t)item * param_stride;
-  if (p[AP_ENABLE] == 0.0 || 1 != (int)p2[3]) return;
-  const double xc = p[AP_XC], yc = p[AP_YC], a = p[AP_A], b = p[AP_B];
-  const int subpix = (int)p2[2];
-  const double hw = a / 2.0, hh = b / 2.0;
-  const ApertureBox box = make_box(xc, yc, fabs(hw), fabs(hh));
+  MaskLineGeom<1> g;
+  if (!g.init(jobs, jb, item)) return;
   const int line = first + lane;
   const bool valid = line < jb.line_end && line < n;
-  const bool in_box = valid && (axis == 0 ? (line >= box.iymin && line < box.iymax) : (line >= box.ixmin && line < box.ixmax));
-  const int c_other = axis == 0 ? subpixel_count_1d(line, yc, hh, subpix) : subpixel_count_1d(line, xc, hw, subpix);
-  const double lm = in_box ? (double)c_other / (double)subpix : 0.0;
+  const bool in_box = valid && g.in_box(axis, line);
+  const double lf = g.line_factor(axis, line), lm = in_box ? lf : 0.0;
   const unsigned long long in_lines = __ballot(in_box);
-  int p0 = n, p1 = -1, p2i = -1, p3 = 0;  // first non-out, first in, last in + 1, last non-out + 1 -- of every line inside the box
-  auto weight = [&](int pos) {  // mask_line_render<1>'s pixel rule for a line inside the box
-    const bool inside = axis == 0 ? (pos >= box.ixmin && pos < box.ixmax) : (pos >= box.iymin && pos < box.iymax);
-    return inside ? (double)(axis == 0 ? subpixel_count_1d(pos, xc, hw, subpix) : subpixel_count_1d(pos, yc, hh, subpix)) / (double)subpix : 0.0;
-  };
+  const int box_line = first + (int)__ffsll((long long)in_lines) - 1;  // the profile is that of any line inside the box
+  LineExtents e = {n, -1, -1, 0};  // of every line inside the box
   if (in_lines) {
-    const int scan_lo = max(0, (axis == 0 ? box.ixmin : box.iymin)) & ~63, scan_hi = min(n, axis == 0 ? box.ixmax : box.iymax);
+    const int scan_lo = max(0, g.lo(axis)) & ~63, scan_hi = min(n, g.hi(axis));
     for (int base = scan_lo; base < scan_hi; base += 64) {
-      const double w = weight(base + lane);
+      const double w = line_weight(g, axis, box_line, base + lane);
       const unsigned long long not_out = __ballot(w != 0.0), is_in = __ballot(w == 1.0);
       if (not_out) {
-        p0 = min(p0, base + (int)__ffsll((long long)not_out) - 1);
-        p3 = max(p3, base + 64 - (int)__clzll((long long)not_out));
+        e.p0 = min(e.p0, base + (int)__ffsll((long long)not_out) - 1);
+        e.p3 = max(e.p3, base + 64 - (int)__clzll((long long)not_out));
       }
       if (is_in) {
-        if (p1 < 0) p1 = base + (int)__ffsll((long long)is_in) - 1;
-        p2i = base + 64 - (int)__clzll((long long)is_in);
+        if (e.p1 < 0) e.p1 = base + (int)__ffsll((long long)is_in) - 1;
+        e.p2i = base + 64 - (int)__clzll((long long)is_in);
       }
     }
   }
-  if (p3 <= p0) { p0 = p1 = p2i = p3 = 0; }           // the lines never leave w_out
-  else if (p1 < 0) { p1 = p2i = p3; }                  // no interior: one partial run [p0, p3)
-  if (p1 - p0 > kMaskW || p3 - p2i > kMaskW) {
-    if (lane == 0) atomicAdd(jobs.overflow, __popcll(in_lines));
-    p0 = p1 = p2i = p3 = 0;
-  }
+  close_record(e, jobs.overflow, lane == 0, __popcll(in_lines));
   for (int side = 0; side < 2; ++side) {
-    const int lo = side == 0 ? p0 : p2i, hi = side == 0 ? p1 : p3;
-    for (int pos = lo + lane; pos < hi; pos += 64) prof[side * kMaskW + pos - lo] = weight(pos);
+    const int lo = side == 0 ? e.p0 : e.p2i, hi = side == 0 ? e.p1 : e.p3;
+    for (int pos = lo + lane; pos < hi; pos += 64) prof[side * kMaskW + pos - lo] = line_weight(g, axis, box_line, pos);
   }
   // the profile is written and read by this wave only: order the LDS traffic, no workgroup barrier
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1092,9 +1039,9 @@ __device__ inline void mask_rect_block_render(const MaskJobs& jobs, const MaskJo
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   if (valid) {
     MaskLine* out = jb.lines + (size_t)item * n + line;
-    if (in_box) *out = {p0, p1, p2i, p3, lm, 0.0}; else *out = {0, 0, 0, 0, lm, 0.0};
+    if (in_box) *out = {e.p0, e.p1, e.p2i, e.p3, lm, 0.0}; else *out = {0, 0, 0, 0, lm, 0.0};
   }
-  const int len0 = p1 - p0, len1 = p3 - p2i;
+  const int len0 = e.p1 - e.p0, len1 = e.p3 - e.p2i;
   for (unsigned long long todo = in_lines; todo; todo &= todo - 1) {
     const int k = (int)__ffsll((long long)todo) - 1;
     double* vout = jb.vals + ((size_t)item * n + (first + k)) * (2 * kMaskW);
@@ -1103,6 +1050,7 @@ __device__ inline void mask_rect_block_render(const MaskJobs& jobs, const MaskJo
   }
 }
 
+// The cascade of an ellipse's lines: four per wave -> two -> one (jobs.windows) -> the scan.
 template <int SHAPE>
 __global__ void __launch_bounds__(kMaskWaves * 64) mask_lines_kernel(MaskJobs jobs) {
   const MaskJob& jb = jobs.job[blockIdx.z];
@@ -1116,18 +1064,17 @@ __global__ void __launch_bounds__(kMaskWaves * 64) mask_lines_kernel(MaskJobs jo
     mask_rect_block_render(jobs, jb, item, jb.line0 + 64 * wave, lane, prof[threadIdx.x >> 6]);
     return;
   }
-  if (!(SHAPE == 0 && jobs.pairs != 0)) {  // one line per wave
-    mask_line_render<SHAPE>(jobs, jb, item, jb.line0 + wave, lane);
-    return;
-  }
-  const int per = jobs.pairs >= 2 ? 4 : 2;  // lines per wave (the grid covers a half / a quarter as many waves: launch_mask_jobs)
+  // lines per wave (the grid covers a half / a quarter as many waves: launch_mask_jobs); rectangles: one
+  const int per = SHAPE == 0 && jobs.pairs != 0 ? (jobs.pairs >= 2 ? 4 : 2) : 1;
   const int first = jb.line0 + per * wave;
   if (first >= jb.line_end || first >= jobs.n) return;
-  if (per == 4 && mask_multi_render<4>(jobs, jb, item, first, lane)) return;
+  if (SHAPE == 0 && per == 4 && mask_multi_render<4>(jobs, jb, item, first, lane)) return;
   for (int f = first; f < first + per; f += 2) {
-    if (mask_multi_render<2>(jobs, jb, item, f, lane)) continue;
-    mask_line_render<0>(jobs, jb, item, f, lane);
-    mask_line_render<0>(jobs, jb, item, f + 1, lane);
+    if (SHAPE == 0 && per >= 2 && mask_multi_render<2>(jobs, jb, item, f, lane)) continue;
+    for (int line = f; line < f + (per >= 2 ? 2 : 1); ++line) {
+      if (SHAPE == 0 && jobs.windows != 0 && mask_multi_render<1>(jobs, jb, item, line, lane)) continue;
+      mask_line_render<SHAPE>(jobs, jb, item, line, lane);
+    }
   }
 }
 
@@ -1198,6 +1145,15 @@ __device__ __forceinline__ double zernike_wfe(const double* table, const double*
   return wfe;
 }
 
+// One member's field value turned by exp(i arg), arg = fl(fl(2 pi wfe) / lambda): sincos_fast and the unfused complex
+// product, stored through the field's type
+template <typename T>
+__device__ __forceinline__ cx<T> rotated(cx<double> v, double arg) {
+  double sn, cs;
+  sincos_fast(arg, &sn, &cs);
+  return {(T)__dsub_rn(__dmul_rn(v.x, cs), __dmul_rn(v.y, sn)), (T)__dadd_rn(__dmul_rn(v.x, sn), __dmul_rn(v.y, cs))};
+}
+
 // NMAXC > 0: the loops over the azimuthal order and the radial index are unrolled for orders up to NMAXC (the host
 // picks this build when nmax <= NMAXC): the recurrence constants and coefficients of a whole order are then fetched
 // in one go instead of five dependent scalar loads per term (round 3: the kernel waited four times as long as it
@@ -1266,22 +1222,14 @@ __global__ void zernike_kernel(cx<T>* field, const double* table, const double* 
           for (int q = 0; q < kZernikeGroup; ++q) v4[q] = {(double)f4[q]->x, (double)f4[q]->y};
         }
 #pragma unroll
-        for (int q = 0; q < kZernikeGroup; ++q) {
-          double sn, cs;
-          sincos_fast(__dmul_rn(turns, iw[q]), &sn, &cs);
-          *f4[q] = {(T)__dsub_rn(__dmul_rn(v4[q].x, cs), __dmul_rn(v4[q].y, sn)),
-                    (T)__dadd_rn(__dmul_rn(v4[q].x, sn), __dmul_rn(v4[q].y, cs))};
-        }
+        for (int q = 0; q < kZernikeGroup; ++q) *f4[q] = rotated<T>(v4[q], __dmul_rn(turns, iw[q]));
       }
       for (; g < glen; ++g) {
         const int it = (int)members[g];
         const double arg = __dmul_rn(turns, params[(size_t)it * param_stride + ZP_INV_WL]);
-        double sn, cs;
-        sincos_fast(arg, &sn, &cs);
         cx<T>* f = field + (size_t)it * item_stride;
         const cx<double> v = twins ? lead : cx<double>{(double)f[m].x, (double)f[m].y};
-        f[m] = {(T)__dsub_rn(__dmul_rn(v.x, cs), __dmul_rn(v.y, sn)),
-                (T)__dadd_rn(__dmul_rn(v.x, sn), __dmul_rn(v.y, cs))};
+        f[m] = rotated<T>(v, arg);
       }
     }
     if (wfe_out && item == 0) wfe_out[(size_t)r * n + c] = masked ? __longlong_as_double(0x7ff8000000000000LL) : wfe;
@@ -1291,17 +1239,8 @@ __global__ void zernike_kernel(cx<T>* field, const double* table, const double* 
 // ---- the first surface and the Zernike surface right behind it in one write of the field -------------------------
 // A lean sweep or Monte-Carlo batch opens with aperture -> stop -> Zernike, and nothing reads the field in between:
 // start_write_kernel stored the same masked, normalised constant for every item and zernike_kernel read one copy back and
-// stored all of them again.  Here the field is stored once, as what that pair leaves.
+// stored all of them again.  Here the field is stored once, as what that pair leaves (StartItem::value, then rotated).
 //
-// What start_write_kernel stores at a pixel of weight w, read back the way zernike_kernel / norm2_partial_kernel read it
-template <typename T>
-__device__ __forceinline__ cx<double> start_value(double w, double v0re, double v0im, bool scaled, double s) {
-  double x = w == 1.0 ? v0re : (w == 0.0 ? 0.0 : (double)(T)__dmul_rn(v0re, w));
-  double y = w == 1.0 ? v0im : (w == 0.0 ? 0.0 : (double)(T)__dmul_rn(v0im, w));
-  if (scaled) { x = __dmul_rn(x, s); y = __dmul_rn(y, s); }
-  return {(double)(T)x, (double)(T)y};
-}
-
 // The groups are start_write_kernel's (same aperture record, stop flag and window: one evaluation of the weight per pixel);
 // a group's leader walks its sub-groups -- zernike_kernel's groups among the members, records that differ in the wavelength
 // only: one evaluation of the polynomials per pixel -- subs[3 q ...] = [item whose Zernike record describes the map, or -1:
@@ -1320,34 +1259,15 @@ __global__ void __launch_bounds__(kPwThreads) zernike_start_write_kernel(cx<T>* 
   const int nsub = (int)grp_len[item];
   if (nsub == 0) return;
   const double* sub = subs + 3 * (int)grp_off[item];
-  const double* p = params + (size_t)item * AP_STRIDE;
-  ApertureEval<SHAPE> ap;
-  ap.init(p, p + AP_THETA);
-  const bool on = p[AP_ENABLE] != 0.0;
-  const bool scaled = stop[item] != 0.0;
-  const double s = scaled ? 1.0 / sqrt(norm2[item]) : 1.0;
-  const double v0re = (double)(T)vre, v0im = (double)(T)vim;
-  size_t total = item_stride, first = 0;
-  if (rows) {
-    first = (size_t)((int)rows[2 * item] / BR) * pitch;
-    total = (size_t)(((int)rows[2 * item + 1] + BR - 1) / BR) * pitch;
-    if (total > item_stride) total = item_stride;
-  }
-  unsigned in_lo = 0, span = pitch;
-  if (cols) {
-    in_lo = (unsigned)((int)cols[2 * item] / BC) * (BR * BC);
-    unsigned h = (unsigned)(((int)cols[2 * item + 1] + BC - 1) / BC) * (BR * BC);
-    if (h > (unsigned)n * BR) h = (unsigned)n * BR;
-    span = h > in_lo ? h - in_lo : 0;
-  }
-  const size_t nbr = (total - first) / pitch;
-  const size_t work = cols ? nbr * span : total - first;
+  const StartItem<T, SHAPE> start(params, item, vre, vim, stop[item] != 0.0, norm2);
+  const ItemWindow<BR, BC> win(rows, cols, item, n, pitch, item_stride);
+  const size_t work = win.work();
   for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < work; j += (size_t)gridDim.x * blockDim.x) {
-    const size_t m = cols ? first + (j / span) * pitch + in_lo + (j % span) : first + j;
+    const size_t m = win.element(j);
     int r, c;
     const bool pixel = layout_unmap<BR, BC>(m, n, pitch, r, c);
     cx<double> u = {0.0, 0.0};
-    if (pixel) u = start_value<T>(on ? ap.weight(ap.mask(r, c)) : 1.0, v0re, v0im, scaled, s);
+    if (pixel) u = start.value(r, c);
     for (int q = 0; q < nsub; ++q) {
       const int zl = (int)sub[3 * q], glen = (int)sub[3 * q + 2];
       const double* mem = members + (int)sub[3 * q + 1];
@@ -1383,19 +1303,11 @@ __global__ void __launch_bounds__(kPwThreads) zernike_start_write_kernel(cx<T>* 
           iw[k] = zparams[(size_t)it[k] * param_stride + ZP_INV_WL];
         }
 #pragma unroll
-        for (int k = 0; k < kGroup; ++k) {
-          double sn, cs;
-          sincos_fast(__dmul_rn(turns, iw[k]), &sn, &cs);
-          field[(size_t)it[k] * item_stride + m] = {(T)__dsub_rn(__dmul_rn(u.x, cs), __dmul_rn(u.y, sn)),
-                                                    (T)__dadd_rn(__dmul_rn(u.x, sn), __dmul_rn(u.y, cs))};
-        }
+        for (int k = 0; k < kGroup; ++k) field[(size_t)it[k] * item_stride + m] = rotated<T>(u, __dmul_rn(turns, iw[k]));
       }
       for (; g < glen; ++g) {
         const int it = (int)mem[g];
-        double sn, cs;
-        sincos_fast(__dmul_rn(turns, zparams[(size_t)it * param_stride + ZP_INV_WL]), &sn, &cs);
-        field[(size_t)it * item_stride + m] = {(T)__dsub_rn(__dmul_rn(u.x, cs), __dmul_rn(u.y, sn)),
-                                                (T)__dadd_rn(__dmul_rn(u.x, sn), __dmul_rn(u.y, cs))};
+        field[(size_t)it * item_stride + m] = rotated<T>(u, __dmul_rn(turns, zparams[(size_t)it * param_stride + ZP_INV_WL]));
       }
     }
   }
@@ -1411,39 +1323,18 @@ __global__ void start_norm2_partial_kernel(double* partial, const double* params
   const int item = blockIdx.y;
   if (lead && lead[item] == 0.0) return;
   __shared__ double sh[kPwThreads / 64];
-  const double* p = params + (size_t)item * AP_STRIDE;
-  ApertureEval<SHAPE> ap;
-  ap.init(p, p + AP_THETA);
-  const bool on = p[AP_ENABLE] != 0.0;
-  const bool scaled = stop[item] != 0.0;
-  const double s = scaled ? 1.0 / sqrt(norm2[item]) : 1.0;
-  const double v0re = (double)(T)vre, v0im = (double)(T)vim;
-  size_t total = item_stride, first = 0;
-  if (rows) {
-    first = (size_t)((int)rows[2 * item] / BR) * pitch;
-    total = (size_t)(((int)rows[2 * item + 1] + BR - 1) / BR) * pitch;
-    if (total > item_stride) total = item_stride;
-  }
+  const StartItem<T, SHAPE> start(params, item, vre, vim, stop[item] != 0.0, norm2);
+  const ItemWindow<BR, BC> win(rows, cols, item, n, pitch, item_stride);
   double acc = 0.0;
   const size_t step = (size_t)gridDim.x * blockDim.x;
-  size_t m = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (m < first) m += (first - m + step - 1) / step * step;
-  unsigned in_lo = 0, in_hi = (unsigned)n * BR;
-  if (cols) {
-    in_lo = (unsigned)((int)cols[2 * item] / BC) * (BR * BC);
-    const unsigned h = (unsigned)(((int)cols[2 * item + 1] + BC - 1) / BC) * (BR * BC);
-    in_hi = h < in_hi ? h : in_hi;
-  }
-  for (; m < total; m += step) {
-    const unsigned off = (unsigned)(m % pitch);
-    if (off >= in_hi || off < in_lo) continue;
+  for (size_t m = win.start((size_t)blockIdx.x * blockDim.x + threadIdx.x, step); m < win.total; m += step) {
+    if (win.skips(m)) continue;
     int r, c;
     if (!layout_unmap<BR, BC>(m, n, pitch, r, c)) continue;  // (never inside [in_lo, in_hi): the padding lies behind n BR)
-    const cx<double> u = start_value<T>(on ? ap.weight(ap.mask(r, c)) : 1.0, v0re, v0im, scaled, s);
+    const cx<double> u = start.value(r, c);
     acc += __dadd_rn(__dmul_rn(u.x, u.x), __dmul_rn(u.y, u.y));
   }
-  const double sum = block_sum(acc, sh);
-  if (threadIdx.x == 0) partial[(size_t)item * gridDim.x + blockIdx.x] = sum;
+  store_block_sum(acc, sh, partial);
 }
 
 // ---- PolyOrthoNorm: Gram sums of the Zernike polynomials over the pupil -----------------------

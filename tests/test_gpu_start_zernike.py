@@ -63,6 +63,26 @@ def test_sweep_batch_fused_against_pair():
         dev.close()
 
 
+def test_sweep_of_nine_wavelengths_fused_against_pair():
+    """SYN20, nine sweep wavelengths: one start group with one wfe map, so the fused kernel turns eight members at a time
+    and then one -- the eight-wide loop and its tail, which groups of three and four never reach."""
+    from paos_amd import _lib
+    from paos_amd.chains import syn20_chain, syn20_wavelength
+
+    wls = [syn20_wavelength(k) for k in (3, 59, 120, 181, 242, 303, 364, 425, 508)]
+    chains = [syn20_chain() for _ in wls]
+    dev = _lib.DeviceFields(N, len(wls))
+    try:
+        s_on = {}
+        fused = _lean(dev, wls, chains, True, s_on)
+        pair = _lean(dev, wls, chains, False)
+        assert s_on["fused_start"] == 1
+        _assert_identical(fused, pair, len(wls))
+        assert not np.array_equal(fused[1][0], fused[1][8])  # (every member at its own wavelength)
+    finally:
+        dev.close()
+
+
 def test_monte_carlo_batch_fused_against_pair():
     """Three items of one wavelength with their own coefficient vectors (one start group, three wfe maps: the weight is
     evaluated once per pixel, the polynomials once per item), and a fourth item that repeats the first's coefficients at
