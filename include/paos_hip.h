@@ -541,6 +541,43 @@ int paos_zernike_gram(paos_ctx* ctx, int nmax, int kdim, const double* table, co
 int paos_zernike_pupil(paos_ctx* ctx, int nmax, int kdim, const double* table, const double* params,
                        int param_stride, double* host_wfe);
 
+/* ---- wavefront fits: the Zernike content and the OPD statistics of the field at a surface (README.md, "Wavefront fits") -- */
+/* The round trip of WFO.zernikes (wfo.py:574-652): no reference counterpart.  Item i holds the field u[k][j] (rows k along
+ * y) with samplings dx, dy; its request is the header of its Zernike parameter block (radius, origin, offset), K
+ * polynomials, a weighting and a floor min_intensity >= 0.  The disk is about the grid centre.
+ *   Support: x = (double)(j - N/2) dx, y = (double)(k - N/2) dy, rr = sqrt(fl(x x) + fl(y y)), rho = rr / radius -- the
+ *   arithmetic of paos_zernike_gram, one rounding per operation; I = fl(fl(re re) + fl(im im)) on the components widened to
+ *   double.  Pixel (k, j) is in Omega iff rho <= 1 and I > min_intensity (and, with use_pupil, the pupil weight != 0).
+ *   Reference phasor: r = sum over Omega of u, complex, fp64, in a fixed order; r = 1 + 0i and fallback = 1 if that sum
+ *   is zero or not finite.
+ *   Phase: re' = fl(fl(ux rx) + fl(uy ry)), im' = fl(fl(uy rx) - fl(ux ry)), phi = atan2(im', re') in [-pi, pi].  Nothing
+ *   is unwrapped: the result is valid while the OPD stays within +- lambda / 2 of the amplitude-weighted mean.
+ *   Weights: w = 1 (PAOS_WF_UNIFORM) or w = I (PAOS_WF_INTENSITY).
+ *   Sums: A[p][q] = sum over Omega of fl(fl(w c_p) c_q) for the K + 1 columns c = [Z_0 .. Z_{K-1}, phi], p <= q
+ *   enumerated row by row as paos_zernike_gram does: G = sum w Z_i Z_j, b = sum w phi Z_j (the last column) and
+ *   sum w phi^2 (the last entry).
+ *   Summary, per item: count = |Omega|, r (the sum itself, whatever the fallback), sum sqrt(I), sum I, phi_min, phi_max
+ *   (both 0 for an empty Omega), fallback, sum w, sum w phi.
+ * No float atomics; every sum is added in an order fixed by the item's own request and the grid: a repeated call gives
+ * the same bits, and an item's results do not depend on the batch size, its place in the batch or the other items'
+ * requests.  Everything is fp64 in both kinds of context; a complex64 field is widened on load.  The fit itself -- the
+ * coefficients, the RMS values, the Strehl ratio -- is host algebra on these sums (paos_amd/wavefront.py). */
+enum { PAOS_WF_UNIFORM = 0, PAOS_WF_INTENSITY = 1 };
+enum { PAOS_WF_SUMMARY = 10 };  /* count, r_re, r_im, sum sqrt(I), sum I, phi_min, phi_max, fallback, sum w, sum w phi */
+/* table / params / poly as for paos_zernike_gram (the header of a block is read, its coefficient planes are not; an item
+ * with enable == 0 gets zeros and count = 0); min_intensity[batch], or NULL for zeros.  Settles a pending deferred stop
+ * factor, then enqueues only (three launches; the host does not wait between them).  Scratch is allocated on first use,
+ * again when a request needs more, and freed by paos_ctx_destroy.  PAOS_EINVAL, with nothing touched and the context
+ * usable: null pointers, inconsistent table dimensions, a radius not > 0 or a non-finite header value, a polynomial
+ * outside the table or listed twice, an unknown weight_mode, a min_intensity that is negative or not finite, use_pupil
+ * without a pupil.  PAOS_EUNSUPPORTED for K outside 1 .. 63; PAOS_EHIP for a failed scratch allocation. */
+int paos_wavefront_fit(paos_ctx* ctx, int nmax, int kdim, const double* table, const double* params, int param_stride,
+                       int K, const double* poly, int weight_mode, int use_pupil, const double* min_intensity);
+/* summary[batch][PAOS_WF_SUMMARY] and sums[batch][(K + 1)(K + 2) / 2] of the last paos_wavefront_fit.  Either pointer may
+ * be NULL, not both.  Synchronises.  PAOS_EINVAL before a fit and with both pointers null.  The results are a snapshot of
+ * the field at fit time: nothing tracks later changes (as paos_zoom_fetch). */
+int paos_wavefront_fetch(paos_ctx* ctx, double* summary, double* sums);
+
 /* ---- broadband PSFs on a detector pixel grid (docs/source/user/montecarlo/index.rst, "Multi-wavelength simulations") -- */
 /* No reference counterpart: the reference hands out each wavelength's PSF on its own sampling and leaves the rebinning to
  * the user.  Definitions (README.md, "Detector images"):

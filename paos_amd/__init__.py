@@ -29,6 +29,10 @@ on the GPU; detector images and transfer functions are then the system ones (REA
 ensquared) energy of the last surface's kept PSFs on up to 1024 radii in metres, each about the item's own centroid, peak
 or given centre, with the radii that enclose the requested fractions -- summed, centred and binned on the GPU, on the lean
 walk and behind a blur (README.md, "Encircled energy").
+
+``run_batch(..., wavefront=WavefrontFit(terms, radius, surfaces=(num,)))`` answers the pupil-side questions: the Zernike
+coefficients, RMS and peak-to-valley OPD and the Strehl ratio of the field at saved surfaces, from sums formed on the GPU
+(README.md, "Wavefront fits"); ``WFO.fit_zernikes`` does the same for the drop-in class.
 """
 from .abcd import ABCD
 from .coordinate_break import coordinate_break
@@ -37,7 +41,7 @@ from .zernike import Zernike
 
 from .raytrace import raytrace
 
-__all__ = ["ABCD", "Detector", "EnergyProfile", "PsfBlur", "PsfWindow", "WFO", "Zernike", "coordinate_break", "parse_config", "raytrace",
+__all__ = ["ABCD", "Detector", "EnergyProfile", "PsfBlur", "PsfWindow", "WFO", "WavefrontFit", "Zernike", "coordinate_break", "parse_config", "raytrace",
            "run_batch", "run_broadband", "run_sharded"]
 __version__ = "0.1.0"
 
@@ -58,6 +62,8 @@ def __getattr__(name):
         return importlib.import_module(".blur", __name__).PsfBlur
     if name == "EnergyProfile":
         return importlib.import_module(".energy", __name__).EnergyProfile
+    if name == "WavefrontFit":
+        return importlib.import_module(".wavefront", __name__).WavefrontFit
     if name == "PsfWindow":
         return importlib.import_module(".zoom", __name__).PsfWindow
     if name == "run_sharded":

@@ -27,6 +27,8 @@ MAX_PW = 6
 OTF_MTF, OTF_COMPLEX = 0, 1  # paos_otf_fetch: |OTF| as doubles / the complex OTF
 EE_GIVEN, EE_CENTROID, EE_PEAK = 0, 1, 2  # paos_ee_compute: where the circles of an item are centred
 EE_ITEM, EE_SUMMARY, EE_MAX_BINS = 4, 9, 1024
+WF_UNIFORM, WF_INTENSITY = 0, 1  # paos_wavefront_fit: the weighting of the sums
+WF_SUMMARY, WF_MAX_TERMS = 10, 63  # count, r_re, r_im, sum sqrt(I), sum I, phi_min, phi_max, fallback, sum w, sum w phi
 ZOOM_PSF, ZOOM_FIELD = 0, 1  # paos_zoom_fetch: |u|^2 of the window as doubles / the complex window
 ZOOM_MAX_TABLES = 256  # phase tables a context keeps; the most distinct fractional parts among the centres of one call
 NORM_SLOTS = 64  # PAOS_NORM_SLOTS: tickets of paos_norm2_enqueue that may be outstanding
@@ -100,6 +102,9 @@ SYMBOLS = {
     "paos_blur_apply": (ctypes.c_int, [_c_ctx, _dbl_p]),
     "paos_ee_compute": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dbl_p]),
     "paos_ee_fetch": (ctypes.c_int, [_c_ctx, _dbl_p, _dbl_p]),
+    "paos_wavefront_fit": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, _dbl_p, _dbl_p, ctypes.c_int, ctypes.c_int, _dbl_p,
+                                          ctypes.c_int, ctypes.c_int, _dbl_p]),
+    "paos_wavefront_fetch": (ctypes.c_int, [_c_ctx, _dbl_p, _dbl_p]),
     "paos_zoom_weights": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_double, _dbl_p, ctypes.POINTER(ctypes.c_int)]),
     "paos_zoom_compute": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, _dbl_p, ctypes.c_int]),
     "paos_zoom_fetch": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
@@ -756,6 +761,42 @@ class DeviceFields:
         out = np.empty(shape, dtype=np.float64) if curves else None
         self._check(self._lib.paos_ee_fetch(self._ctx, _dptr(summary), _dptr(out) if curves else None), "paos_ee_fetch")
         return summary, out
+
+    # -- wavefront fits (paos_wavefront_*: README.md, "Wavefront fits") ----------------------------------------------
+    def wavefront_fit(self, nmax, kdim, table, blocks, poly, weight=WF_UNIFORM, min_intensity=None, pupil=False):
+        """The sums of a wavefront fit of every item's field as it stands: ``table`` / ``blocks`` / ``poly`` as for
+        ``zernike_gram`` (the header of a block is read: sampling, radius, origin, offset), ``weight`` WF_UNIFORM or
+        WF_INTENSITY, ``min_intensity`` a scalar or one floor per item (None: zeros), ``pupil``: restrict to the pupil
+        weights != 0.  Enqueued only."""
+        t = np.ascontiguousarray(table, dtype=np.float64).reshape(-1)
+        b = np.ascontiguousarray(blocks, dtype=np.float64)
+        q = np.ascontiguousarray(poly, dtype=np.float64)
+        if b.ndim != 2 or b.shape[0] != self.batch:
+            raise ValueError("zernike blocks must be [batch][stride]")
+        if q.ndim != 2 or q.shape[1] != 4:
+            raise ValueError("poly must be [K][4]")
+        floors = None
+        if min_intensity is not None:
+            try:
+                floors = np.ascontiguousarray(np.broadcast_to(np.asarray(min_intensity, dtype=np.float64), (self.batch,)))
+            except ValueError:
+                raise ValueError(f"wavefront_fit takes a scalar floor or one per item ({self.batch})") from None
+        self._check(self._lib.paos_wavefront_fit(self._ctx, int(nmax), int(kdim), _dptr(t), _dptr(b), int(b.shape[1]), int(q.shape[0]),
+                                                 _dptr(q), int(weight), 1 if pupil else 0,
+                                                 _dptr(floors) if floors is not None else None), "paos_wavefront_fit")
+        self._wf_terms = int(q.shape[0])
+
+    def wavefront_fetch(self):
+        """(summary (batch, WF_SUMMARY), sums (batch, (K + 1)(K + 2) / 2)) of the last ``wavefront_fit``: the Gram matrix of
+        the columns ``[Z_0 .. Z_{K-1}, phi]`` under the weights, upper triangle row by row.  Synchronises.  Refused
+        (``PaosHipError``) before a fit."""
+        k = getattr(self, "_wf_terms", None)
+        if k is None:
+            raise PaosHipError("paos_wavefront_fetch failed (1): no wavefront fit computed (paos_wavefront_fit)")
+        summary = np.empty((self.batch, WF_SUMMARY), dtype=np.float64)
+        sums = np.empty((self.batch, (k + 1) * (k + 2) // 2), dtype=np.float64)
+        self._check(self._lib.paos_wavefront_fetch(self._ctx, _dptr(summary), _dptr(sums)), "paos_wavefront_fetch")
+        return summary, sums
 
     # -- zoomed windows (paos_zoom_*: README.md, "Zoomed PSFs") ------------------------------------------------------
     def zoom_compute(self, size, oversample, centres=None, field=False):

@@ -470,6 +470,7 @@ int paos_ctx_destroy(paos_ctx* c) {
   if (c->det_rows) (void)hipFree(c->det_rows);
   if (c->det_out) (void)hipFree(c->det_out);
   if (c->ee_buf) (void)hipFree(c->ee_buf);
+  if (c->wf_buf) (void)hipFree(c->wf_buf);
   for (int i = 0; i < 2; ++i) {
     if (c->bounce[i]) (void)hipHostFree(c->bounce[i]);
     if (c->bounce_ev[i]) (void)hipEventDestroy(c->bounce_ev[i]);

@@ -3,7 +3,7 @@
 // The host side of the library is split by what it launches: context.hip (contexts, the parameter arena, errors,
 // the launch timer), passes.hip (pass programs; what a program launches is planned in plain C++: pass_program.h on the
 // records of pass_records.h), generic_pass.hip and frugal_<family>.hip (the pass kernels), paos_hip.hip (the pointwise entry points: every kernel of pointwise.h) and the products: focus_otf.hip, zoom.hip,
-// detector.hip.  Here: the build-time layout, the context, the error and launch helpers, the dispatchers that turn what a
+// detector.hip, energy.hip, wavefront.hip.  Here: the build-time layout, the context, the error and launch helpers, the dispatchers that turn what a
 // context is at run time into template arguments (dispatch_n: the grid size; dispatch_layout / dispatch_block_rows: element
 // type and block height; with pass_records.h's dispatch_family: the families of the frugal pass kernel -- every launch is
 // written once, inside a generic lambda), and the declarations of the functions
@@ -166,6 +166,12 @@ struct paos_ctx {
   size_t ee_bytes = 0;
   int ee_bins = 0, ee_curves = 0;
   bool ee_computed = false, ee_valid = false;
+  // wavefront fits (paos_wavefront_fit): one buffer -- summary [batch][10] | sums [batch][wf_pairs] | the reference phasors
+  // | the partial sums of the launches -- allocated on first use and again when a request needs more
+  double* wf_buf = nullptr;
+  size_t wf_bytes = 0;
+  int wf_pairs = 0;
+  bool wf_fitted = false;
   void* bounce[2] = {nullptr, nullptr};  // pinned host buffers for device -> pageable host copies
   hipEvent_t bounce_ev[2] = {nullptr, nullptr};
   void* field = nullptr;

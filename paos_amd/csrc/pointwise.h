@@ -16,16 +16,15 @@
 //                               summing kernels read it (filtered walk), zero_outside_box_kernel clears its complement
 //   StartItem / start_value     what a start stores at a pixel: the four start kernels
 //   rotated                     one member's value turned by exp(i turns / lambda): zernike_kernel, zernike_start_write_kernel
-//   store_block_sum             how a reduction kernel ends
+//   store_block_sum             how a reduction kernel ends (pointwise_shared.h: the wavefront fits end theirs the same way)
 //   MaskLineGeom, line_weight, window_fit, extents_from_windows, close_record
 //                               the aperture line records: one geometry, one pixel rule, one window fit for every renderer
 #pragma once
 #include "frugal_pass.h"
 #include "item_window.h"
+#include "pointwise_shared.h"
 
 namespace paos {
-
-constexpr int kPwThreads = 256;
 
 template <typename T>
 __global__ void fill_kernel(cx<T>* f, size_t total, T re, T im) {
@@ -241,24 +240,6 @@ __global__ void pointwise_kernel(PassArgs a, int n) {
 }
 
 // ---- make_stop: sum |u|^2 (two deterministic stages), then scale ---------------
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += sh[w];
-  return s;  // valid in thread 0
-}
-
-// how a reduction kernel ends: this workgroup's sum goes to partial[item][workgroup] (blockIdx.y = item)
-__device__ __forceinline__ void store_block_sum(double acc, double* sh, double* partial) {
-  const double s = block_sum(acc, sh);
-  if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
-}
-
 // ``rows`` (optional, [batch][2]): rows of the item outside [lo, hi) are exact zeros (or hold stale data standing for
 // zeros) and are not read.  Block rows are contiguous in memory, so that is a window of the walk; every thread keeps
 // the elements it would have had, in the same order, and a zero adds nothing: the sum is bit-identical.
@@ -1083,7 +1064,7 @@ __global__ void __launch_bounds__(kMaskWaves * 64) mask_lines_kernel(MaskJobs jo
 // recurrence constants A, B, C of P_k^{(am,0)}:  P_k = (A x + B) P_{k-1} - C P_{k-2}.
 // per-item block: [enable, dx, dy, radius, origin_is_y, cos_off, sin_off, inv_wl,
 //                  then coefC[am][k], coefS[am][k]] with the (-1)^k norm Z product folded in.
-enum : int { ZP_ENABLE = 0, ZP_DX, ZP_DY, ZP_RADIUS, ZP_ORIGIN_Y, ZP_COS_OFF, ZP_SIN_OFF, ZP_INV_WL, ZP_HEAD };
+// (the indices ZP_* of that header: pointwise_shared.h)
 
 // The Zernike sum of one pixel inside the unit disk (rho <= 1): zernike_kernel and zernike_start_write_kernel share it, so that
 // both form the wfe by the same operations in the same order.
@@ -1343,7 +1324,7 @@ __global__ void start_norm2_partial_kernel(double* partial, const double* params
 // (one Jacobi recurrence + one rotation per pixel, like zernike_kernel), then the 256 threads of
 // the workgroup each own up to kGramAcc (i, j) pairs and add the chunk's products.  Fixed chunk ->
 // workgroup mapping and a second, ordered stage over workgroups: bit-reproducible sums.
-constexpr int kGramMaxK = 64, kGramPix = 128, kGramThreads = 256, kGramRow = kGramPix + 1;
+// (the chunk shape kGramPix, kGramThreads, kGramRow and kGramMaxK: pointwise_shared.h)
 constexpr int kGramAcc = (kGramMaxK * (kGramMaxK + 1) / 2 + kGramThreads - 1) / kGramThreads;
 
 // slots[(am * kdim + k) * 2 + {0: cos, 1: sin}] = polynomial index j or -1; fac[j] = its

@@ -1224,6 +1224,40 @@ def _need_saved_last(chains, last_key, who):
         raise ValueError(f"{who} the last surface of the chain to be saved")
 
 
+def _plan_wavefront(wavefront, chains, nb, sync):
+    """Every check of ``wavefront`` -- before anything is launched.  Returns {chain key: the WavefrontFit asked for there}."""
+    if wavefront is None:
+        return {}
+    from .wavefront import WavefrontFit
+
+    requests = [wavefront] if isinstance(wavefront, WavefrontFit) else wavefront
+    try:
+        requests = list(requests)
+    except TypeError:
+        raise ValueError(f"wavefront must be a paos_amd.WavefrontFit or a sequence of them, got {wavefront!r}") from None
+    at = {}
+    for wf in requests:
+        if not isinstance(wf, WavefrontFit):
+            raise ValueError(f"wavefront must be a paos_amd.WavefrontFit or a sequence of them, got {wf!r}")
+        if not sync:
+            raise ValueError("wavefront synchronises: it cannot be combined with sync=False")
+        wf.check(nb)
+        if wf.surfaces is None:
+            keys = [key for key in chains[0] if any(key in chain and chain[key]["save"] for chain in chains)]
+        else:
+            keys = []
+            for num in wf.surfaces:
+                hit = [key for key, item in chains[0].items() if item["num"] == num]
+                if not hit or not all(hit[0] in chain and chain[hit[0]]["num"] == num and chain[hit[0]]["save"] for chain in chains):
+                    raise ValueError(f"wavefront: surface {num!r} is not a saved surface of every chain")
+                keys.append(hit[0])
+        for key in keys:
+            if key in at:
+                raise ValueError(f"wavefront: two requests name surface {chains[0][key]['num']!r}")
+            at[key] = wf
+    return at
+
+
 def _plan_focus(states, chains, focus_planes, last_key):
     """Every check of ``focus_planes`` -- on the scalars alone, so before anything is launched: the pilot beams are taken
     through the chain the way ``_walk`` takes them (one planner call per surface), the field is not.  Returns (the
@@ -1387,7 +1421,7 @@ def _focus_stack(dev, focus, outputs, metrics_radii_px, power, products):
 def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, precision="fp64",
               device=0, outputs=("psf",), dev=None, sync=True, stats=None, metrics_radii_px=None,
               keep_psf=False, power=True, detector=None, detector_weights=None, detector_origin=None, focus_planes=None,
-              mtf_cuts=False, psf_zoom=None, psf_blur=None, psf_energy=None):
+              mtf_cuts=False, psf_zoom=None, psf_blur=None, psf_energy=None, wavefront=None):
     """Propagate ``B = len(opt_chains)`` wavefronts together on one GPU.
 
     ``wavelengths[i]`` / ``opt_chains[i]`` describe wavefront ``i`` (chains must
@@ -1495,6 +1529,16 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     not an ``EnergyProfile``; a last surface that is not saved; ``sync=False``; centres of another shape than (B, 2) or
     outside ``[0, N)``.  An item whose largest circle would be wider or taller than the grid (``bins step / dx_i`` or
     ``bins step / dy_i`` above ``N / 2``) is a ``ValueError`` that names it, raised before the curves are computed.
+
+    ``wavefront`` (a :class:`paos_amd.WavefrontFit`, or a sequence of them: surfaces with different beam sizes need
+    different radii) fits Zernike polynomials to the phase of every item's field at the saved surfaces a request names
+    (all of them with ``surfaces=None``), on the GPU (README.md, "Wavefront fits": ``paos_wavefront_fit``; one small copy
+    per surface, ``paos_wavefront_fetch``).  Each such record gets ``'wf_coeff'`` (metres, one per term), ``'wf_rms'``,
+    ``'wf_residual_rms'``, ``'wf_pv'`` (metres), ``'wf_strehl'``, ``'wf_pixels'``, ``'wf_phase_absmax'`` (radians),
+    ``'wf_fallback'`` and ``'wf_singular'``.  It needs the field, so the run takes the ordinary walk, like
+    ``metrics_radii_px``; focus planes get nothing.  ``ValueError``, before anything is launched: an argument that is not
+    a ``WavefrontFit``; ``sync=False``; a named surface that is not a saved surface of every chain; two requests that
+    name the same surface; per-item values of another length than the batch.
     """
     nb = len(opt_chains)
     if len(wavelengths) != nb:
@@ -1528,6 +1572,7 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
             raise ValueError("psf_energy synchronises: it cannot be combined with sync=False")
         _need_saved_last(opt_chains, last_key, "psf_energy needs")
         psf_energy.check(nb, int(gridsize))
+    wf_at = _plan_wavefront(wavefront, opt_chains, nb, sync)
     if otf:
         if not sync:
             raise ValueError("'mtf' / 'otf' outputs and mtf_cuts synchronise: they cannot be combined with sync=False")
@@ -1585,7 +1630,7 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     # nobody reads an array at a saved surface: the walk may skip writing dead rows at the start and store the PSF
     # straight from the last pass (csrc/frugal_pass.h: STORE)
     # (a focus stack and a zoomed window need the field of the last surface: the ordinary walk)
-    lean = _WalkState() if (not outputs and metrics_radii_px is None and focus is None and psf_zoom is None) else None
+    lean = _WalkState() if (not outputs and metrics_radii_px is None and focus is None and psf_zoom is None and not wf_at) else None
     ledger = _PowerLedger(dev)
 
     def on_saved(key, items, plans, wfe):
@@ -1604,6 +1649,13 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
             met = dev.psf_metrics(metrics_radii_px)
             for i, rec in pending:
                 rec["metrics"] = met[i]
+        if key in wf_at and pending:
+            # (an item that does not save here is fitted on the first saving item's sampling, and its result dropped)
+            saved = dict(pending)
+            scalars = [saved.get(i, pending[0][1]) for i in range(nb)]
+            fits = wf_at[key].fit(dev, [sc["dx"] for sc in scalars], [sc["dy"] for sc in scalars], [sc["wl"] for sc in scalars])
+            for i, rec in pending:
+                rec.update(fits[i])
         keep = keep_psf and key == last_key
         if det is not None and det.chief and key == last_key:
             det.origins = plans.chief_ray

@@ -170,6 +170,17 @@ class WFO:
         outside = np.isnan(wfe)
         return np.ma.MaskedArray(data=np.where(outside, 0.0, wfe), mask=outside, fill_value=0.0)
 
+    def fit_zernikes(self, terms, radius, ordering="standard", normalize=True, origin="x", offset=0.0, weight="uniform",
+                     min_intensity=0.0):
+        """The round trip of ``zernikes``: the first ``terms`` Zernike coefficients (metres) of the field's phase on the
+        disk of ``radius`` about the grid centre, with the OPD statistics and the Strehl ratio -- the ``wf_*`` entries of
+        ``run_batch(..., wavefront=...)`` for this one field (README.md, "Wavefront fits").  No reference counterpart."""
+        from .wavefront import WavefrontFit
+
+        b = self._beam
+        return WavefrontFit(terms, radius, ordering=ordering, normalize=normalize, origin=origin, offset=offset, weight=weight,
+                            min_intensity=min_intensity).fit(self._dev, [b.dx], [b.dy], [b.wl])[0]
+
     def grid_sag(self, sag, nx, ny, delx, dely, xdec=0.0, ydec=0.0):
         """wfo.py:656-871: add a user-specified sag (metres) to the wavefront; returns the masked
         WFE map.  Maps must come at the wavefront's pixel scale (see ``phase_maps``)."""
