@@ -480,6 +480,12 @@ int paos_record_set_stats(paos_ctx* ctx, unsigned long long* found, unsigned lon
  * the ordinary build (*plain).  PAOS_CENTRAL_HALF=0 / 1 in the environment when the context is created switches the
  * central-half builds off / on; results are equal as numbers either way. */
 int paos_central_half_stats(paos_ctx* ctx, unsigned long long* central, unsigned long long* plain);
+/* Likewise: how many frugal pass launches ran on the narrow-window variant of their central-half build (*narrow: besides,
+ * every item of the first pass loads and every item of the pass whose stores leave the launch stores positions inside
+ * [5 n / 16, 11 n / 16) only, so the kernel neither loads, computes nor tests what lies outside) and how many on any other
+ * build (*other).  A narrow launch counts as *central above.  PAOS_NARROW_WINDOWS=0 / 1 in the environment when the context
+ * is created switches the variant off / on; results are equal as numbers either way. */
+int paos_narrow_window_stats(paos_ctx* ctx, unsigned long long* narrow, unsigned long long* other);
 /* Test aid, host only (no context): is there a build of the frugal pass kernel of this name in the family (precision, n)?
  * `record`: the nine fields of a build's name -- axis, kpre, kmid, nfft, store, tab, fuse, one_line, central.  1 / 0; a field out
  * of its range names no build (0).  The families are complex128 at 1024, 2048 and 4096 and complex64 at 2048 and 4096: any other

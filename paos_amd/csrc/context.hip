@@ -332,6 +332,8 @@ int paos_ctx_create(int device, int n, int batch, int precision, paos_ctx** out)
   if (const char* pad = getenv("PAOS_LDS_PAD")) c->lds_pad = (size_t)std::max(0, std::atoi(pad));
   if (env_is("PAOS_CENTRAL_HALF", '0')) c->central_half = false;
   if (env_is("PAOS_CENTRAL_HALF", '1')) c->central_half = true;
+  if (env_is("PAOS_NARROW_WINDOWS", '0')) c->narrow_windows = false;
+  if (env_is("PAOS_NARROW_WINDOWS", '1')) c->narrow_windows = true;
   if ((e = hipMalloc(&c->dyn_scale, (size_t)batch * sizeof(double))) != hipSuccess) return bail(e, "hipMalloc(dyn_scale)");
   {
     std::vector<double> ones((size_t)batch, 1.0);
@@ -536,6 +538,13 @@ int paos_central_half_stats(paos_ctx* c, unsigned long long* central, unsigned l
   if (!c || !central || !plain) return fail(c, PAOS_EINVAL, "bad central-half request");
   *central = c->central_launches;
   *plain = c->plain_launches;
+  return PAOS_OK;
+}
+
+int paos_narrow_window_stats(paos_ctx* c, unsigned long long* narrow, unsigned long long* other) {
+  if (!c || !narrow || !other) return fail(c, PAOS_EINVAL, "bad narrow-window request");
+  *narrow = c->narrow_launches;
+  *other = c->other_launches;
   return PAOS_OK;
 }
 

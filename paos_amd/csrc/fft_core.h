@@ -278,7 +278,10 @@ __device__ __forceinline__ void dft16_lf(cx<T>* v) {
 // and what dft<4> makes of them -- t0 = 0 + b, t1 = 0 - b, t2 = a + 0, t3 = a - 0 -- is b, -b, a, a: four complex additions,
 // in the order and with the operands of the full butterfly, so the live sums keep their bits (an exact zero may change its
 // sign).  The second layer is dft16_lf's.  Forward transforms only (the pass kernel conjugates around an inverse one).
-template <int DIR, typename T>
+// NARROW (round 23, CH = 2): v[4] and v[11] are exact zeros too -- the live inputs are v[5..10].  The butterfly n2 = 0 then has
+// the inputs (0, 0, b, 0) and n2 = 3 has (0, a, 0, 0); with every x +- 0 of dft<4> written out their outputs are b, -b, b, -b
+// and a, -i a, -a, +i a: copies, negations and swaps, no addition.  n2 = 1 and n2 = 2 keep the four additions.
+template <int DIR, bool NARROW = false, typename T>
 __device__ __forceinline__ void dft16_lf_central(cx<T>* v) {
   static_assert(DIR > 0, "the pass kernel runs forward transforms only");
   cx<T> y[16];
@@ -286,10 +289,22 @@ __device__ __forceinline__ void dft16_lf_central(cx<T>* v) {
   for (int n2 = 0; n2 < 4; ++n2) {
     const cx<T> a = v[4 + n2], b = v[8 + n2];
     const cx<T> nb = {-b.x, -b.y};
-    y[0 * 4 + n2] = cadd(b, a);     // t0 + t2
-    y[1 * 4 + n2] = sub_ib(nb, a);  // t1 - i t3
-    y[2 * 4 + n2] = csub(b, a);     // t0 - t2
-    y[3 * 4 + n2] = add_ib(nb, a);  // t1 + i t3
+    if (NARROW && n2 == 0) {         // a = 0: t2 = t3 = 0
+      y[0 * 4 + n2] = b;
+      y[1 * 4 + n2] = nb;
+      y[2 * 4 + n2] = b;
+      y[3 * 4 + n2] = nb;
+    } else if (NARROW && n2 == 3) {  // b = 0: t0 = t1 = 0
+      y[0 * 4 + n2] = a;
+      y[1 * 4 + n2] = cx<T>{a.y, -a.x};   // -i a
+      y[2 * 4 + n2] = cx<T>{-a.x, -a.y};
+      y[3 * 4 + n2] = cx<T>{-a.y, a.x};   // +i a
+    } else {
+      y[0 * 4 + n2] = cadd(b, a);     // t0 + t2
+      y[1 * 4 + n2] = sub_ib(nb, a);  // t1 - i t3
+      y[2 * 4 + n2] = csub(b, a);     // t0 - t2
+      y[3 * 4 + n2] = add_ib(nb, a);  // t1 + i t3
+    }
   }
   cx<T> o[4];
   {
@@ -439,7 +454,7 @@ __device__ __forceinline__ void apply_twiddle_chain(cx<T>* v, cx<T> w1) {
 // (N = 4096: one, k = t; N = 2048: two) -- per-thread constants the caller keeps in registers, so that the stage needs no
 // table in LDS (the four-per-CU shapes of frugal_pass.h only fit without the 4 KiB table).
 // CH != 0 (the first stage, NS = 1, of 16-point-per-thread complex128 lines): slots 0..3 and 12..15 hold exact zeros
-// (dft16_lf_central); the later stages are the ordinary ones.
+// (dft16_lf_central); CH = 2: slots 4 and 11 too; the later stages are the ordinary ones.
 template <typename T, int N, int E, int DIR, bool SPLIT, int NS = 1, int FR = 0, int CH = 0>
 __device__ __forceinline__ void fft_stages(cx<T>* v, void* lds, int t,
                                            const cx<T>* __restrict__ tw, const cx<double>* circle = nullptr,
@@ -476,7 +491,7 @@ __device__ __forceinline__ void fft_stages(cx<T>* v, void* lds, int t,
     }
     if constexpr (CH != 0 && NS == 1) {
       static_assert(R == 16 && TPT == 1, "central-half first stage: one 16-point butterfly per thread");
-      dft16_lf_central<DIR>(v);
+      dft16_lf_central<DIR, CH == 2>(v);
     } else {
       dft<R, DIR>(v + s * R);
     }

@@ -55,8 +55,10 @@ struct FrugalGeometry {
 
 namespace {
 
+// narrow (central-half builds only, CH = 1): the launch takes the narrow-window variant of the build, the CH = 2 kernel of the
+// same shape -- a property of the launch (pass_program.h: pick_narrow), not of the build's name
 template <typename T, int N, int AXIS, int KPRE, int KMID, int NFFT, int STORE, int TAB, int LONG, int ONE, int CH>
-int frugal_launch(paos_ctx* c, const FrugalArgs& args) {
+int frugal_launch(paos_ctx* c, const FrugalArgs& args, bool narrow) {
   using C = FftCfg<T, N>;
   using G = FrugalGeometry<T, N, AXIS, KPRE, KMID, STORE, LONG, ONE>;
   FrugalArgs a = args;
@@ -74,7 +76,13 @@ int frugal_launch(paos_ctx* c, const FrugalArgs& args) {
   constexpr size_t kMaxPad = 8192;
   const size_t lds = G::LDS + (c->lds_pad < kMaxPad ? c->lds_pad : kMaxPad);
   auto kern = frugal_pass_kernel<T, N, C::E, G::LINES, G::TILES, AXIS, C::BR, C::BC, G::SPLIT, KPRE, KMID, NFFT, STORE, TAB, LONG, G::OCC, CH>;
-  ++(CH != 0 ? c->central_launches : c->plain_launches);  // paos_central_half_stats
+  if constexpr (CH == 1) {
+    if (narrow) kern = frugal_pass_kernel<T, N, C::E, G::LINES, G::TILES, AXIS, C::BR, C::BC, G::SPLIT, KPRE, KMID, NFFT, STORE, TAB, LONG, G::OCC, 2>;
+  } else {
+    narrow = false;
+  }
+  ++(CH != 0 ? c->central_launches : c->plain_launches);  // paos_central_half_stats (a narrow launch is a central one)
+  ++(narrow ? c->narrow_launches : c->other_launches);    // paos_narrow_window_stats
   return TIMED_LAUNCH(c, kern, grid, block, lds, G::LDS + kMaxPad, AXIS == 0 ? PAOS_KERNEL_PASS_ROWS : PAOS_KERNEL_PASS_COLS,
                       c->prof_next_tag, PAOS_FRUGAL_PASS(a));
 }
@@ -83,25 +91,25 @@ int frugal_launch(paos_ctx* c, const FrugalArgs& args) {
 // the next one is compared with.  Behind the last field: the launch, where the name has a build.
 constexpr int kFrugalFieldMax[] = {1, kFrugalMaxPre, kFrugalMaxMid, 2, 2, 1, 4, 1, 1};  // (FrugalBuild's fields, in order)
 template <typename T, int N, int X, int... V>
-int frugal_unfold(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a) {
+int frugal_unfold(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a, bool narrow) {
   constexpr int I = sizeof...(V), kFields = sizeof(kFrugalFieldMax) / sizeof(int);
   static_assert(kFields == kBuildFields, "one maximum per field");
   int field[kBuildFields];
   build_to_ints(b, field);
   if (field[I] != X) {
-    if constexpr (X < kFrugalFieldMax[I]) return frugal_unfold<T, N, X + 1, V...>(c, b, a);
+    if constexpr (X < kFrugalFieldMax[I]) return frugal_unfold<T, N, X + 1, V...>(c, b, a, narrow);
     else return frugal_not_built(c, b);
   } else if constexpr (I + 1 < kFields) {
-    return frugal_unfold<T, N, 0, V..., X>(c, b, a);
+    return frugal_unfold<T, N, 0, V..., X>(c, b, a, narrow);
   } else if constexpr (frugal_built<T, N>(FrugalBuild{V..., X})) {
-    return frugal_launch<T, N, V..., X>(c, a);
+    return frugal_launch<T, N, V..., X>(c, a, narrow);
   } else {
     return frugal_not_built(c, b);
   }
 }
 template <typename T, int N>
-int frugal_dispatch(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a) {
-  return frugal_unfold<T, N, 0>(c, b, a);
+int frugal_dispatch(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a, bool narrow = false) {
+  return frugal_unfold<T, N, 0>(c, b, a, narrow);
 }
 
 }  // namespace

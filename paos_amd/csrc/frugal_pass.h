@@ -227,12 +227,21 @@ __device__ __forceinline__ cx<float> slot_factor32(const double* g, const double
   return p;
 }
 
+// The elements [ch_first, ch_end) of a thread's E that can be non-zero when a CH build enters (frugal_pass_kernel: CH): all of
+// them, those of the central half (CH = 1), those of the narrow window [5 N / 16, 11 N / 16) (CH = 2).
+template <int E, int CH>
+constexpr int ch_first() { return CH == 2 ? 5 * E / 16 : (CH != 0 ? E / 4 : 0); }  // the first element that can be non-zero on entry
+template <int E, int CH>
+constexpr int ch_end() { return CH == 2 ? 11 * E / 16 : (CH != 0 ? 3 * E / 4 : E); }  // ... and the end of them
+
 // RECS > 0: the aperture line records of the workgroup's RECS lines (first line ``lbase``) were fetched by the kernel
 // before the tile's loads (wave-uniform: scalar registers); RECS < 0: the kernel staged them in LDS (``recs``);
 // RECS = 0: the slot loads its line's record itself.
 // CH != 0 (the table slot in front of the first transform of a launch whose every item loads positions of the central half
 // [N / 4, 3 N / 4) only -- frugal_pass_kernel: CH): elements 0 .. E/4 - 1 and 3 E/4 .. E - 1 are exact zeros for every thread
 // and stay the {0, 0} they are: the aperture weights and the table factors go to elements E/4 .. 3 E/4 - 1 alone.
+// CH = 2 (narrow windows, [5 N / 16, 11 N / 16)): elements 5 E/16 .. 11 E/16 - 1 alone (ch_first / ch_end) -- and likewise on
+// the slot a CH = 2 launch ends on, where the other elements are never stored.
 template <typename T, int N, int E, int K, typename Map, int PLAIN = 0, bool SHARE = false, int RECS = 0, int TAB = 0, int CH = 0>
 __device__ __forceinline__ void frugal_slot(cx<T>* v, const FrugalSlot& sl, const FrugalPhase* ph,
                                             const Map& m, const cx<double>* circle, bool conj_in, bool conj_out, int tpos,
@@ -266,8 +275,8 @@ __device__ __forceinline__ void frugal_slot(cx<T>* v, const FrugalSlot& sl, cons
   // tpos: position along the line of the thread's element 0 (its elements are TL apart): m.t
   constexpr int TL = N / E;
   static_assert(TL % 2 == 0, "the checkerboard sign is constant along a thread's elements");
-  static_assert(CH == 0 || (K > 0 && TAB != 0 && sizeof(T) == 8 && E % 4 == 0), "central-half slots: complex128 table slots");
-  constexpr int kFirst = CH != 0 ? E / 4 : 0, kEnd = CH != 0 ? 3 * E / 4 : E;  // the elements that can be non-zero
+  static_assert(CH == 0 || (K > 0 && TAB != 0 && sizeof(T) == 8 && E % 16 == 0), "central-half slots: complex128 table slots");
+  constexpr int kFirst = ch_first<E, CH>(), kEnd = ch_end<E, CH>();  // the elements that can be non-zero
   const double sc = __dmul_rn(sl.scale, extra_scale);  // (extra_scale: 1 exactly, except behind a deferred stop)
   const int line = Map::kAxis == 0 ? m.row(0) : m.col(0);  // this thread's row (column): constant
   if (sl.mask_on != 0.0) {  // wave-uniform: an aperture rides on this slot
@@ -563,13 +572,26 @@ __device__ __forceinline__ void stream_store(cx<T>* p, cx<T> v) {
   else *p = v;
 }
 
+// Every element of the tile counts as used here.  CH = 2 builds, behind the slot in front of the last transform of a later
+// pass: where that transform is the launch's last, ten of the sixteen elements are wanted only if it is switched on, so the
+// compiler sinks their share of the slot -- with the table entries already loaded for it -- into that branch, across the
+// slot's fences.  The launches that end on a one-transform pass lose their spill-free register allocation to it (LONG = 1, 3:
+// 8 - 28 B of scratch), the others 1 - 3 VGPRs and, measured, most of what the narrow stores gain on the three-pass shapes
+// (profiles/r23_fftbench_narrow_windows.txt).  An empty asm per element keeps the slot's work where it was written.
+template <int E, typename T>
+__device__ __forceinline__ void pin_tile(cx<T>* v) {
+#pragma unroll
+  for (int k = 0; k < E; ++k) asm volatile("" : "+v"(v[k].x), "+v"(v[k].y));
+}
+
 // Direction as data: IFFT(x) = conj(FFT(conj x)).  A scalar branch between a forward and an inverse
 // instantiation would spare the conjugations but costs ~60 spilled VGPRs at the join (measured), so
 // the direction stays data and the conjugations are made cheap instead: the one in FRONT of the
 // transform is folded into the slot that precedes it (frugal_slot multiplies the imaginary part by
 // -f instead of f), the one BEHIND it is an XOR on the sign bit (half the issue cost of an fp64 multiply).
 // FLIP = false: the conjugation behind the transform is left to the slot that follows (frugal_slot: conj_in)
-// CH != 0: elements 0 .. E/4 - 1 and 3 E/4 .. E - 1 are exact zeros on entry (fft_core.h: dft16_lf_central)
+// CH != 0: elements 0 .. E/4 - 1 and 3 E/4 .. E - 1 are exact zeros on entry (fft_core.h: dft16_lf_central); CH = 2: E/4 and
+// 3 E/4 - 1 too
 template <typename T, int N, int E, bool SPLIT, bool FLIP = true, int CH = 0>
 __device__ __forceinline__ void frugal_fft(cx<T>* v, void* lds, int t, const cx<T>* tw, const cx<double>* circle,
                                            double inv, const cx<T>* w1_last = nullptr) {
@@ -679,13 +701,24 @@ __device__ __forceinline__ void tile_power_out(double acc, double* scratch, doub
 // is reproduced by the same operations or was an exact zero (whose sign alone may differ in an intermediate).
 // There is NO device-side guard: the build never looks at an outer element, so an item whose [pos_lo, pos_hi) reaches beyond
 // the central half would silently lose those positions.  Whoever asks for the build (FrugalBuild::central) must have checked every
-// active item of the first pass (passes.hip: pick_build is the only place that does).
+// active item of the first pass (pass_program.h: pick_build is the only place that does).
+// CH = 2 (round 23, narrow windows; the same shapes): the host launches it in place of the CH = 1 build when, besides, every
+// active item of the first pass loads positions of [5 N / 16, 11 N / 16) only AND every active item of the pass whose stores
+// leave the launch stores positions of that window only (pass_program.h: pick_narrow) -- the quarter windows of a zoom-4
+// chain.  Load side: k = 4 and k = 11 are exact zeros as well, so the load loop, the pre slot and the first butterfly layer
+// run over k = 5 .. 10 (dft16_lf_central<NARROW>).  Store side: the store loop runs over k = 5 .. 10 with compile-time
+// bounds, so whatever feeds the other ten elements alone -- ten outputs of the last transform's last 16-point butterfly,
+// their conjugation flips, or the last slot's factors where no transform follows it -- is dead code and is not compiled
+// in.  An item whose last transform is off stores v[5 .. 10] as they are.  Everything between the first stage and the
+// last is the ordinary code.  Again there is NO device-side guard, on either side: an item that stores beyond the window
+// would silently keep what memory held there.
 template <typename T, int N, int E, int LINES, int TILES, int AXIS, int BR, int BC, bool SPLIT,
           int KPRE, int KMID, int NFFT, int STORE = 0, int TAB = 0, int LONG = 0, int OCC = 0, int CH = 0>
 __global__ void __launch_bounds__(TILES* LINES* N / E, (frugal_min_waves<T, N, TILES * LINES * N / E, OCC>()))
     frugal_pass_kernel(PAOS_FRUGAL_PARAMS) {
   static_assert(LONG == 0 || (TAB != 0 && NFFT == 2 && KPRE == 1 && KMID == 1), "LONG builds: see above");
   static_assert(CH == 0 || (sizeof(T) == 8 && N == 4096 && E == 16 && TAB != 0 && KPRE == 1 && NFFT <= 2), "CH builds: see above");
+  static_assert(CH >= 0 && CH <= 2 && (CH != 2 || STORE == 0), "CH = 2: field-storing builds");
   FrugalArgs a;
   a.items = k_items; a.field = k_field; a.pitch = k_pitch; a.item_stride = k_item_stride; a.wg0 = k_wg0;
   a.tw = k_tw; a.psf = k_psf; a.psf_partial = k_psf_partial; a.pow_partial = k_pow_partial; a.dyn_scale = k_dyn_scale; a.live_lo = a.live_hi = 0;
@@ -820,11 +853,11 @@ __global__ void __launch_bounds__(TILES* LINES* N / E, (frugal_min_waves<T, N, T
   constexpr int kPlainPre = KPRE != 0 ? 0 : (AXIS == 1 ? PAOS_COL_PRE : PAOS_ROW_PRE);
   cx<T> v[E];
   const int plo = (int)h_pos_lo, phi = (int)h_pos_hi;
-  if constexpr (CH != 0) {  // [plo, phi) lies inside [N / 4, 3 N / 4): the outer elements are never loaded
+  if constexpr (CH != 0) {  // [plo, phi) lies inside [N / 4, 3 N / 4) ([5 N / 16, 11 N / 16)): the outer elements are never loaded
 #pragma unroll
     for (int k = 0; k < E; ++k) v[k] = cx<T>{(T)0, (T)0};
 #pragma unroll
-    for (int k = E / 4; k < 3 * E / 4; ++k) {
+    for (int k = ch_first<E, CH>(); k < ch_end<E, CH>(); ++k) {
       const int pos = m.t + k * (N / E);
       if (pos >= plo && pos < phi) v[k] = stream_load<NT>(at(k));
     }
@@ -910,7 +943,9 @@ __global__ void __launch_bounds__(TILES* LINES* N / E, (frugal_min_waves<T, N, T
   if (ran1) frugal_fft<T, N, E, SPLIT, false, CH>(v, lds, m.t, tw, circle, it.fft1_inv, w1_last);
   PAOS_STAMP(3);
   constexpr bool kShareMid = kShare && KPRE == 0 && KMID < 3;
-  frugal_slot<T, N, E, KMID, decltype(m), 0, kShareMid, (kRecMode == 1 ? -1 : kRecs), TAB>(
+  // (CH = 2: where this slot is the last thing the launch does to the tile, it runs over the elements that are stored)
+  constexpr int kNarrowMid = (CH == 2 && NFFT == 1 && LONG == 0 && KMID > 0) ? 2 : 0;
+  frugal_slot<T, N, E, KMID, decltype(m), 0, kShareMid, (kRecMode == 1 ? -1 : kRecs), TAB, kNarrowMid>(
       v, it.mid, it.mid_ph, m, circle, inv1, ran2 && it.fft2_inv != 0.0, m.t, lds, ran1, kRecMode == 1 ? rec_lds : mrec, lbase, h_dyn);
   PAOS_STAMP(4);
   if constexpr (NFFT == 2) {
@@ -929,13 +964,16 @@ __global__ void __launch_bounds__(TILES* LINES* N / E, (frugal_min_waves<T, N, T
     const bool ran4 = (kTwo) && (ix).fft2_on != 0.0;                                                                                 \
     const bool inv3 = ran3 && (ix).fft1_inv != 0.0;                                                                                  \
     frugal_slot<T, N, E, 1, decltype(m), 0, false, 0, TAB>(v, (ix).pre, (ix).pre_ph, m, circle, false, inv3, m.t, lds, false);       \
+    if constexpr (CH == 2 && !(kTwo)) pin_tile<E>(v);                                                                                \
     if (ran3) {                                                                                                                      \
       if (busy) __syncthreads();                                                                                                     \
       frugal_fft<T, N, E, SPLIT, false>(v, lds, m.t, tw, circle, (ix).fft1_inv, w1_last);                                            \
       busy = true;                                                                                                                   \
     }                                                                                                                                \
-    frugal_slot<T, N, E, 1, decltype(m), 0, false, 0, TAB>(v, (ix).mid, (ix).mid_ph, m, circle, inv3, ran4 && (ix).fft2_inv != 0.0,  \
-                                                           m.t, lds, ran3);                                                          \
+    /* (a pass of one transform is the launch's last: CH = 2 runs its second slot over the elements that are stored) */            \
+    frugal_slot<T, N, E, 1, decltype(m), 0, false, 0, TAB, (CH == 2 && !(kTwo)) ? 2 : 0>(                                            \
+        v, (ix).mid, (ix).mid_ph, m, circle, inv3, ran4 && (ix).fft2_inv != 0.0, m.t, lds, ran3);                                    \
+    if constexpr (CH == 2 && (kTwo)) pin_tile<E>(v);                                                                                 \
     if constexpr (kTwo) {                                                                                                            \
       if (ran4) {                                                                                                                    \
         if (busy) __syncthreads();                                                                                                   \
@@ -972,7 +1010,13 @@ __global__ void __launch_bounds__(TILES* LINES* N / E, (frugal_min_waves<T, N, T
     return;
   }
   const int slo = (int)h_spos_lo, shi = (int)h_spos_hi;
-  if (slo <= 0 && shi >= N) {  // wave-uniform: everything is stored
+  if constexpr (CH == 2) {  // [slo, shi) lies inside [5 N / 16, 11 N / 16): nothing else leaves the kernel (or was computed)
+#pragma unroll
+    for (int k = ch_first<E, CH>(); k < ch_end<E, CH>(); ++k) {
+      const int pos = m.t + k * (N / E);
+      if (pos >= slo && pos < shi) stream_store<NT>(at(k), v[k]);
+    }
+  } else if (slo <= 0 && shi >= N) {  // wave-uniform: everything is stored
 #pragma unroll
     for (int k = 0; k < E; ++k) stream_store<NT>(at(k), v[k]);
   } else {

@@ -207,6 +207,11 @@ struct paos_ctx {
   // context, so that a test can hold an "on" and an "off" context in one process.  (On by default: profiles/r11_central_half.md.)
   bool central_half = true;
   unsigned long long central_launches = 0, plain_launches = 0;  // frugal pass launches on CH / ordinary builds (paos_central_half_stats)
+  // Round 23: of the central-half launches, those whose first pass loads and whose last pass stores positions of
+  // [5 n / 16, 11 n / 16) only take the narrow-window variant of the build (frugal_pass.h: CH = 2; pass_program.h: pick_narrow).
+  // PAOS_NARROW_WINDOWS=0 / 1 when the context is created switches it off / on, like PAOS_CENTRAL_HALF.  (profiles/r23_narrow_windows.md)
+  bool narrow_windows = true;
+  unsigned long long narrow_launches = 0, other_launches = 0;  // frugal pass launches on the CH = 2 kernels / on any other (paos_narrow_window_stats)
   std::vector<int> pass_builds;  // the FrugalBuild of every frugal launch of the most recent pass program, nine ints each (paos_pass_builds)
   int* mask_overflow = nullptr;    // device counter: partial runs that did not fit (must stay 0)
   double* partial = nullptr;
@@ -396,8 +401,9 @@ int generic_pass(paos_ctx* c, int axis, const PassArgs& a, int feat);
 
 // ---- frugal_<family>.hip: the pass-kernel builds of one (type, N) family behind one ordinary function each ----
 // (the record that names a build, FrugalBuild, and the list of the families, dispatch_family: pass_records.h)
+// narrow: a central-half build launches its narrow-window variant (pass_program.h: Launch::narrow)
 template <typename T, int N>
-int frugal_family(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a);
+int frugal_family(paos_ctx* c, const FrugalBuild& b, const FrugalArgs& a, bool narrow);
 
 // ---- paos_hip.hip: the one unit that includes pointwise.h (its non-template kernels can be compiled once only), so
 // whatever another unit needs of that header's kernels is launched through these ----

@@ -25,6 +25,7 @@ struct PlanDims {
   int n, batch, br;  // grid size, items, block height of the layout
   int precision;     // PAOS_F64 / PAOS_F32
   int central_half;  // the context takes the central-half builds (PAOS_CENTRAL_HALF when it was created)
+  int narrow_windows = 1;  // ... and their narrow-window variant (PAOS_NARROW_WINDOWS likewise)
 };
 // The environment switches the planning reads (true: the default path), and the context's own pruning switch.
 struct PlanSwitches {
@@ -449,6 +450,7 @@ struct Launch {
   // finish_launch:
   int store = 0;                       // FrugalBuild::store
   FrugalBuild build{};                 // the build it takes
+  int narrow = 0;                      // ... and whether it launches the narrow-window variant of that build (pick_narrow)
   unsigned live_lo = 0, live_hi = 0;   // the grid covers the workgroups of these lines only (0, 0: all lines)
   int tag = 0;                         // for the launch timer: what the launch skips
   double bytes = 0.0, lines = 0.0;     // ... the bytes the plan has it move, the line transforms it runs
@@ -543,11 +545,33 @@ inline FrugalBuild pick_build(const PlanDims& d, const Launch& g) {
   return b;
 }
 
+// Does the launch take the narrow-window variant of its central-half build (frugal_pass.h: CH = 2)?  A property of the launch,
+// not of the build's name: the build is a central-half one, the context's switch is on, every active item of the FIRST pass
+// loads positions of [5 n / 16, 11 n / 16) only, and every active item of the pass whose stores leave the launch stores
+// positions of that window only.  Per launch, like `central`: one item outside either window keeps the whole launch on the
+// central-half kernel.  (There is no device-side guard on either side: frugal_pass.h, CH.)
+inline int pick_narrow(const PlanDims& d, const Launch& g, const FrugalBuild& b) {
+  if (b.central != 1 || !d.narrow_windows) return 0;
+  const double lo = 5.0 * (double)d.n, hi = 11.0 * (double)d.n;
+  bool any = false;
+  for (const FrugalItem& fi : g.lp[0]->items) {
+    if (fi.active == 0.0) continue;
+    any = true;
+    if (!(16.0 * fi.pos_lo >= lo && 16.0 * fi.pos_hi <= hi)) return 0;
+  }
+  for (const FrugalItem& fo : g.last().items) {
+    if (fo.active == 0.0) continue;
+    if (!(16.0 * fo.spos_lo >= lo && 16.0 * fo.spos_hi <= hi)) return 0;
+  }
+  return any ? 1 : 0;
+}
+
 // Everything else that is decided about a launch once its tables flag and what it stores are known: its build, the lines
 // its grid has to cover, and the launch timer's figures.
 inline void finish_launch(const PlanDims& d, const PlanSwitches& sw, Launch& g, int store) {
   g.store = store;
   g.build = pick_build(d, g);
+  g.narrow = pick_narrow(d, g, g.build);
   const bool store_psf = store == 1;
   const LoweredPass& lp = *g.lp[0];
   {  // the lines some item still works on: the grid need not cover the others when their tiles have nothing to write

@@ -125,6 +125,10 @@ inline FrugalBuild build_from_ints(const int* rec) {
 //     the one-line workgroups -- the field-storing fused launches and the one-line single passes.  The PSF-storing fused build
 //     (two-line workgroups; the last column launch of a step loads a quarter too) was built and measured as well: 0.97 ->
 //     1.10 ms per launch, so it keeps the ordinary build (profiles/r11_central_half.md).
+//     Round 23: every central-half build holds a second kernel, the narrow-window variant (CH = 2), for launches that load
+//     and store inside [5 n / 16, 11 n / 16).  It has no name of its own here: which of the two kernels a launch of the build
+//     takes is decided per launch (pass_program.h: pick_narrow) and handed to frugal_launch beside the record
+//     (profiles/r23_narrow_windows.md).
 template <typename T, int N>
 constexpr bool frugal_built(const FrugalBuild& b) {
   constexpr bool kOneLineSizes = sizeof(T) == 8 && (N == 4096 || N == 2048) && PAOS_LONG_ONE_LINE != 0;

@@ -111,7 +111,9 @@ MaskRender mask_job(paos_ctx* c, int axis, const LoweredPass& lp, const double* 
 }
 
 // What the planner (pass_program.h) reads of a context ...
-PlanDims plan_dims(const paos_ctx* c) { return PlanDims{c->n, c->batch, c->br, c->precision, c->central_half ? 1 : 0}; }
+PlanDims plan_dims(const paos_ctx* c) {
+  return PlanDims{c->n, c->batch, c->br, c->precision, c->central_half ? 1 : 0, c->narrow_windows ? 1 : 0};
+}
 // ... and of the environment: read once per process, except the two that tests switch (host.h: env_is)
 PlanSwitches plan_switches(const paos_ctx* c) {
   static const bool line_tables = !env_is("PAOS_LINE_TABLES", '0'), compact_grid = !env_is("PAOS_COMPACT_GRID", '0'),
@@ -246,7 +248,7 @@ int launch_lowered(paos_ctx* c, const Launch& g, const double* dblocks, const Fr
   }
   // (a pass is lowered only in a context of one of the families: frugal_sizes)
   return dispatch_family(c->precision, c->n, (int)PAOS_EUNSUPPORTED,
-                         [&](auto t, auto n) { return frugal_family<decltype(t), decltype(n)::value>(c, b, a); });
+                         [&](auto t, auto n) { return frugal_family<decltype(t), decltype(n)::value>(c, b, a, g.narrow != 0); });
 }
 
 int launch_one_pass(paos_ctx* c, const paos_pass& p, const double* dblocks, int n_blocks,

@@ -230,6 +230,8 @@ void bench_frugal(const char* name, int batch, int reps, int pad_blocks) {
 // library's two-line workgroups (512 threads, two per CU) against one-line workgroups (256 threads, four per CU).
 // Round 11, CH = 1: the central-half build of the same launch (frugal_pass.h: CH) -- the live quarter [1536, 2560) lies inside
 // [1024, 3072), so both builds run the same program and their checksums must agree (PAOS_BENCH_CENTRAL below).
+// Round 23, CH = 2: its narrow-window variant -- the quarter is loaded AND stored, inside [1280, 2816) (PAOS_BENCH_NARROW).
+// LONG = 0: a single table pass on the one-line workgroup.
 template <int AXIS, int LINES, int LONG = 2, int NFFT = 2, int CH = 0>
 void bench_fused(const char* name, int batch, int reps, int pad_blocks) {
   using T = double;
@@ -375,6 +377,22 @@ int main(int argc, char** argv) {
       bench_fused<0, 1, 4, 2, 1>("fused rows [2][2][2], central half", 32, reps, pad);
       bench_fused<1, 1, 4>("fused cols [2][2][2], base", 32, reps, pad);
       bench_fused<1, 1, 4, 2, 1>("fused cols [2][2][2], central half", 32, reps, pad);
+    }
+    return 0;
+  }
+  if (getenv("PAOS_BENCH_NARROW")) {  // round 23: central-half build against its narrow-window variant (CH = 2), interleaved:
+    // the four one-line fused shapes and a single table pass; [1536, 2560) loaded and stored lies inside [1280, 2816)
+    for (int round = 0; round < 3; ++round) {
+      bench_fused<0, 1, 2, 2, 1>("fused rows [2][2], central half", 32, reps, pad);
+      bench_fused<0, 1, 2, 2, 2>("fused rows [2][2], narrow windows", 32, reps, pad);
+      bench_fused<1, 1, 2, 2, 1>("fused cols [2][2], central half", 32, reps, pad);
+      bench_fused<1, 1, 2, 2, 2>("fused cols [2][2], narrow windows", 32, reps, pad);
+      bench_fused<0, 1, 4, 2, 1>("fused rows [2][2][2], central half", 32, reps, pad);
+      bench_fused<0, 1, 4, 2, 2>("fused rows [2][2][2], narrow windows", 32, reps, pad);
+      bench_fused<1, 1, 4, 2, 1>("fused cols [2][2][2], central half", 32, reps, pad);
+      bench_fused<1, 1, 4, 2, 2>("fused cols [2][2][2], narrow windows", 32, reps, pad);
+      bench_fused<0, 1, 0, 2, 1>("single rows [2], central half", 32, reps, pad);
+      bench_fused<0, 1, 0, 2, 2>("single rows [2], narrow windows", 32, reps, pad);
     }
     return 0;
   }
