@@ -486,6 +486,12 @@ int paos_central_half_stats(paos_ctx* ctx, unsigned long long* central, unsigned
  * build (*other).  A narrow launch counts as *central above.  PAOS_NARROW_WINDOWS=0 / 1 in the environment when the context
  * is created switches the variant off / on; results are equal as numbers either way. */
 int paos_narrow_window_stats(paos_ctx* ctx, unsigned long long* narrow, unsigned long long* other);
+/* Measurement / test aid: what the block renderer of ellipse line records did since the context was created.  out[0]: lines
+ * inside an aperture's bounding box whose records a wave rendered as part of a block of 64 lines, out[1]: such lines handed to
+ * the per-line renderers (no window fits, or the block's list of undecided pixels was full), out[2]: window pixels whose exact
+ * overlap was evaluated (the others were decided by comparisons).  Waits for the context's stream.  PAOS_MASK_BLOCKS=0 in the
+ * environment (read at every call) renders four lines per wave instead; the records are equal bit for bit either way. */
+int paos_record_block_stats(paos_ctx* ctx, unsigned long long* out);
 /* Test aid, host only (no context): is there a build of the frugal pass kernel of this name in the family (precision, n)?
  * `record`: the nine fields of a build's name -- axis, kpre, kmid, nfft, store, tab, fuse, one_line, central.  1 / 0; a field out
  * of its range names no build (0).  The families are complex128 at 1024, 2048 and 4096 and complex64 at 2048 and 4096: any other

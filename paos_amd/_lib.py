@@ -115,6 +115,7 @@ SYMBOLS = {
     "paos_record_set_stats": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
     "paos_central_half_stats": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
     "paos_narrow_window_stats": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
+    "paos_record_block_stats": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_ulonglong)]),
     "paos_frugal_built": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "paos_pass_builds": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "paos_deferred_stop_stats": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
@@ -842,6 +843,13 @@ class DeviceFields:
         self._check(self._lib.paos_central_half_stats(self._ctx, ctypes.byref(central), ctypes.byref(plain)),
                     "paos_central_half_stats")
         return int(central.value), int(plain.value)
+
+    def record_block_stats(self):
+        """(block, handed, undecided): lines of ellipse records rendered by blocks of 64 / handed to the per-line renderers,
+        and window pixels whose exact overlap was evaluated, since creation."""
+        out = (ctypes.c_ulonglong * 3)()
+        self._check(self._lib.paos_record_block_stats(self._ctx, out), "paos_record_block_stats")
+        return int(out[0]), int(out[1]), int(out[2])
 
     def pass_builds(self, capacity=64):
         """The build records (tuples of nine ints, BUILD_FIELDS) of the frugal launches of the most recent pass program, in

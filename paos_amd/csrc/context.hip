@@ -448,6 +448,7 @@ int paos_ctx_destroy(paos_ctx* c) {
     if (ms.vals) (void)hipFree(ms.vals);
   }
   if (c->mask_overflow) (void)hipFree(c->mask_overflow);
+  if (c->block_stats) (void)hipFree(c->block_stats);
   if (c->partial) (void)hipFree(c->partial);
   if (c->norm2) (void)hipFree(c->norm2);
   if (c->norm2_host) (void)hipHostFree(c->norm2_host);
@@ -545,6 +546,15 @@ int paos_narrow_window_stats(paos_ctx* c, unsigned long long* narrow, unsigned l
   if (!c || !narrow || !other) return fail(c, PAOS_EINVAL, "bad narrow-window request");
   *narrow = c->narrow_launches;
   *other = c->other_launches;
+  return PAOS_OK;
+}
+
+int paos_record_block_stats(paos_ctx* c, unsigned long long* out) {
+  if (!c || !out) return fail(c, PAOS_EINVAL, "bad record-block request");
+  out[0] = out[1] = out[2] = 0ull;
+  if (!c->block_stats) return PAOS_OK;  // nothing was rendered yet
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, c->block_stats, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return PAOS_OK;
 }
 

@@ -214,6 +214,7 @@ struct paos_ctx {
   unsigned long long narrow_launches = 0, other_launches = 0;  // frugal pass launches on the CH = 2 kernels / on any other (paos_narrow_window_stats)
   std::vector<int> pass_builds;  // the FrugalBuild of every frugal launch of the most recent pass program, nine ints each (paos_pass_builds)
   int* mask_overflow = nullptr;    // device counter: partial runs that did not fit (must stay 0)
+  unsigned long long* block_stats = nullptr;  // device, three counters of the block renderer of ellipse records (paos_record_block_stats)
   double* partial = nullptr;
   double* norm2 = nullptr;
   double* norm2_host = nullptr;  // pinned, kNormSlots x batch

@@ -72,12 +72,10 @@ int render_mask_records(paos_ctx* c, const MaskRender* renders, int count) {
     jobs.job[j] = MaskJob{r.params, r.shared, ms.lines, ms.vals, r.axis, r.line0, r.line_end, r.shapes};
   }
   jobs.batch_stride = c->batch * (int)FP_STRIDE; jobs.param_stride = (int)FP_STRIDE; jobs.n = c->n; jobs.overflow = c->mask_overflow;
-  {
-    const int mode = mask_render_mode();
-    jobs.windows = mode != 0 ? 1 : 0;
-    jobs.pairs = mode >= 2 ? mode - 1 : 0;
-    jobs.rect_blocks = mask_rect_blocks() ? 1 : 0;
-  }
+  const int mode = mask_render_mode();
+  jobs.windows = mode != 0 ? 1 : 0;
+  jobs.pairs = mode >= 2 ? std::min(mode, 3) - 1 : 0;  // (mode 4, blocks of lines: the lines it hands over go two per wave first)
+  jobs.rect_blocks = mask_rect_blocks() ? 1 : 0;
   int widest = 0, shapes = 0;
   for (int j = 0; j < count; ++j) {
     widest = std::max(widest, jobs.job[j].line_end - jobs.job[j].line0);
@@ -86,7 +84,11 @@ int render_mask_records(paos_ctx* c, const MaskRender* renders, int count) {
   const dim3 block(256);
   // (ellipses: a wave renders four / two lines, the grid covers a quarter / half as many waves)
   const int per_wg = 4 * (jobs.pairs >= 2 ? 4 : (jobs.pairs ? 2 : 1));
-  if (shapes & 1) hipLaunchKernelGGL(mask_lines_kernel<0>, dim3((widest + per_wg - 1) / per_wg, c->batch, count), block, 0, c->stream, jobs);
+  constexpr int block_per_wg = kMaskBlockLines * kMaskWaves;  // (round 24) ... or a block of 64
+  if ((shapes & 1) && mode == 4)
+    hipLaunchKernelGGL(mask_blocks_kernel, dim3((widest + block_per_wg - 1) / block_per_wg, c->batch, count), block, 0, c->stream, jobs, c->block_stats);
+  else if (shapes & 1)
+    hipLaunchKernelGGL(mask_lines_kernel<0>, dim3((widest + per_wg - 1) / per_wg, c->batch, count), block, 0, c->stream, jobs);
   const int rect_per_wg = 4 * (jobs.rect_blocks ? 64 : 1);
   if (shapes & 2) hipLaunchKernelGGL(mask_lines_kernel<1>, dim3((widest + rect_per_wg - 1) / rect_per_wg, c->batch, count), block, 0, c->stream, jobs);
   HIPCHK(c, hipGetLastError());

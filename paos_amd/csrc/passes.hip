@@ -49,6 +49,10 @@ int ensure_mask_store(paos_ctx* c) {
     HIPCHK(c, hipMalloc(&c->mask_overflow, sizeof(int)));
     HIPCHK(c, hipMemsetAsync(c->mask_overflow, 0, sizeof(int), c->stream));
   }
+  if (!c->block_stats) {
+    HIPCHK(c, hipMalloc(&c->block_stats, 3 * sizeof(unsigned long long)));
+    HIPCHK(c, hipMemsetAsync(c->block_stats, 0, 3 * sizeof(unsigned long long), c->stream));
+  }
   return PAOS_OK;
 }
 
@@ -565,10 +569,13 @@ int run_passes(paos_ctx* c, const paos_pass* passes, int n_passes, const double*
 
 // How ellipse records are rendered (read per call: tests switch it).  PAOS_MASK_SCAN=1: the chunk scan of rounds 2-3 (0);
 // PAOS_MASK_PAIRS=0: one line per wave through two 32-pixel windows (1), =1: two lines per wave through 16-pixel windows
-// where they fit (2); default: four lines per wave through 8-pixel windows where they fit (3).
+// where they fit (2); PAOS_MASK_BLOCKS=0: four lines per wave through 8-pixel windows where they fit (3); default: blocks of
+// 64 lines per wave, the exact overlap on the undecided window pixels only (4, round 24: mask_blocks_kernel).
 int mask_render_mode() {
   if (env_is("PAOS_MASK_SCAN", '1')) return 0;
-  return env_is("PAOS_MASK_PAIRS", '0') ? 1 : (env_is("PAOS_MASK_PAIRS", '1') ? 2 : 3);
+  if (env_is("PAOS_MASK_PAIRS", '0')) return 1;
+  if (env_is("PAOS_MASK_PAIRS", '1')) return 2;
+  return env_is("PAOS_MASK_BLOCKS", '0') ? 3 : 4;  // 4 (round 24): blocks of 64 lines per wave in front of the cascade
 }
 // ... and rectangle records: 64 lines per wave from one column profile (round 5); PAOS_MASK_RECT_BLOCKS=0: one line per wave
 bool mask_rect_blocks() {

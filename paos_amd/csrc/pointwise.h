@@ -23,6 +23,7 @@
 #include "frugal_pass.h"
 #include "item_window.h"
 #include "pointwise_shared.h"
+#include "record_blocks.h"
 
 namespace paos {
 
@@ -717,7 +718,7 @@ constexpr int kMaskJobs = 8;
 struct MaskJobs {
   MaskJob job[kMaskJobs];
   int windows;       // 1: lines whose two boundary runs fit two 32-pixel windows take the one-evaluation path (PAOS_MASK_SCAN=1: 0)
-  int pairs;         // (round 5) 2: a wave renders FOUR lines at once when all fit two 8-pixel windows, else / 1: TWO through 16-pixel windows (PAOS_MASK_PAIRS=1), 0: one line per wave (=0)
+  int pairs;         // (round 24: mask_blocks_kernel in front renders 64 lines per wave, PAOS_MASK_BLOCKS=0: not) (round 5) 2: a wave renders FOUR lines at once when all fit two 8-pixel windows, else / 1: TWO through 16-pixel windows (PAOS_MASK_PAIRS=1), 0: one line per wave (=0)
   int rect_blocks;   // 1 (round 5): a wave renders 64 lines of a rectangle's records at once -- one column profile for all of them (PAOS_MASK_RECT_BLOCKS=0: 0)
   int batch_stride;  // doubles between the two parameter block sets of a job (= batch * param_stride)
   int param_stride, n;
@@ -1056,6 +1057,129 @@ __global__ void __launch_bounds__(kMaskWaves * 64) mask_lines_kernel(MaskJobs jo
       if (SHAPE == 0 && jobs.windows != 0 && mask_multi_render<1>(jobs, jb, item, line, lane)) continue;
       mask_line_render<SHAPE>(jobs, jb, item, line, lane);
     }
+  }
+}
+
+// Round 24: an ellipse's records by blocks of 64 consecutive lines per wave, in front of the cascade above (record_blocks.h).
+//  1. lane = line: the item's geometry once per wave; every lane fits the windows of its own line, the narrowest of
+//     (8, 1), (16, 3), (32, 3) that window_fit accepts (a wider one does not always fit where a narrower one fails);
+//  2. every lane classes its 2 W window pixels from W + 1 edge quotients per window (pixel_class: ellipse_pixel's own first
+//     test says 1.0, the scan's chunk == 2 test says 0.0) and lists the undecided ones in the wave's LDS list;
+//  3. lane = list entry: the wave runs line_weight -- the unchanged function on the unchanged arguments -- over the list,
+//     64 entries at a time: the exact overlap on the pixels that need it and on no other, with every lane busy;
+//  4. lane = line again: the weights of the window pixels from the classes and the list, then extents_from_windows and
+//     close_record as mask_multi_render runs them, and the stores.
+// A line inside the box that fits no window, or whose entries would end behind the list's capacity, is handed over: the
+// wave renders these behind the block through two lines per wave, one line per wave and the scan, one call site each.
+// stats (three counters of the context, one atomic instruction per wave): box lines rendered here / handed over, and
+// undecided pixels evaluated.
+constexpr int kMaskBlockLines = 64;  // lines per wave: 16, 32 or 64 (profiles/r24_record_blocks.md has the three measured)
+__global__ void __launch_bounds__(kMaskWaves * 64) mask_blocks_kernel(MaskJobs jobs, unsigned long long* stats) {
+  const MaskJob& jb = jobs.job[blockIdx.z];
+  if (!(jb.shapes & 1)) return;
+  const int item = blockIdx.y;
+  if (jb.shared[item] != 0.0) return;  // reads the records of an earlier, identical item
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int n = jobs.n, axis = jb.axis;
+  const int first = jb.line0 + kMaskBlockLines * (blockIdx.x * kMaskWaves + wv);
+  if (first >= jb.line_end || first >= n) return;
+  MaskLineGeom<0> g;
+  if (!g.init(jobs, jb, item)) return;  // (not an ellipse: nothing to render)
+  __shared__ unsigned long long list_all[kMaskWaves][kBlockListCap];
+  __shared__ int counts_all[kMaskWaves][64];
+  unsigned long long* list = list_all[wv];
+  int* counts = counts_all[wv];
+  const auto wave_sync = [] {  // the list is written and read by this wave only: order the LDS traffic, no workgroup barrier
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
+
+  // 1. the windows of this lane's line
+  const int line = first + lane;
+  const bool valid = lane < kMaskBlockLines && line < jb.line_end && line < n;
+  const bool in_box = valid && g.in_box(axis, line);
+  int W = 0, wl0 = 0, wr0 = 0;
+  if (in_box) {
+    if (window_fit<8, 1>(g, axis, line, n, wl0, wr0)) W = 8;
+    else if (window_fit<16, 3>(g, axis, line, n, wl0, wr0)) W = 16;
+    else if (window_fit<32, 3>(g, axis, line, n, wl0, wr0)) W = 32;
+  }
+  // 2. the classes of its window pixels: bit k < W = pixel wl0 + k, bit W + k = pixel wr0 + k
+  unsigned long long in_bits = 0ull, und_bits = 0ull;
+  if (W != 0) {
+    const double sa = axis == 0 ? g.a : g.b, sc = axis == 0 ? g.b : g.a;
+    const double ca = axis == 0 ? g.xc : g.yc, cc = axis == 0 ? g.yc : g.xc;
+    const double lo_c = __dsub_rn((double)line - 0.5, cc), hi_c = __dsub_rn((double)line + 0.5, cc);
+    const double vv_lo = edge_square(lo_c, sc), vv_hi = edge_square(hi_c, sc);
+    unsigned in_l, in_r, und_l, und_r;
+    window_classes(wl0, W, ca, sa, lo_c, hi_c, vv_lo, vv_hi, in_l, und_l);
+    window_classes(wr0, W, ca, sa, lo_c, hi_c, vv_lo, vv_hi, in_r, und_r);
+    in_bits = (unsigned long long)in_l | ((unsigned long long)in_r << W);
+    und_bits = (unsigned long long)und_l | ((unsigned long long)und_r << W);
+  }
+  const int count = __popcll(und_bits);
+  counts[lane] = count;
+  wave_sync();
+  int offset, total;
+  list_layout(counts, 64, lane, offset, total);
+  const bool kept = W != 0 && list_keeps(offset, count);
+  if (kept) list_write(list, lane, offset, und_bits);
+  wave_sync();
+  // 3. the exact overlap of the listed pixels, 64 at a time; the weight takes the entry's place
+  for (int base = 0; base < total; base += 64) {
+    const int at = base + lane;
+    const unsigned long long e = at < total ? list[at] : 0ull;
+    const int owner = entry_line(e), k = entry_pixel(e);
+    const int oW = __shfl(W, owner), owl0 = __shfl(wl0, owner), owr0 = __shfl(wr0, owner);
+    if (at < total) list[at] = (unsigned long long)__double_as_longlong(line_weight(g, axis, first + owner, k < oW ? owl0 + k : owr0 + (k - oW)));
+  }
+  wave_sync();
+  // 4. the record of this lane's line
+  if (valid && !in_box) jb.lines[(size_t)item * n + line] = {0, 0, 0, 0, 1.0, 0.0};  // the line never leaves w_out (what the scan finds for it)
+  if (kept) {
+    unsigned long long not_out = in_bits, is_in = in_bits;
+    int at = offset;
+    for (unsigned long long m = und_bits; m; m &= m - 1, ++at) {
+      const double w = __longlong_as_double((long long)list[at]);
+      const unsigned long long bit = 1ull << __builtin_ctzll(m);
+      if (w != g.w_out) not_out |= bit;
+      if (w == g.w_in) is_in |= bit;
+    }
+    const unsigned long long win = (1ull << W) - 1ull;
+    const unsigned no_l = (unsigned)(not_out & win), no_r = (unsigned)((not_out >> W) & win), ii_l = (unsigned)(is_in & win), ii_r = (unsigned)((is_in >> W) & win);
+    LineExtents e = W == 8 ? extents_from_windows<8>(no_l, no_r, ii_l, ii_r, wl0, wr0, n)
+                           : (W == 16 ? extents_from_windows<16>(no_l, no_r, ii_l, ii_r, wl0, wr0, n) : extents_from_windows<32>(no_l, no_r, ii_l, ii_r, wl0, wr0, n));
+    close_record(e, jobs.overflow, true);
+    double* vout = jb.vals + ((size_t)item * n + line) * (2 * kMaskW);
+    for (int side = 0; side < 2; ++side) {
+      const int lo = side == 0 ? e.p0 : e.p2i, hi = side == 0 ? e.p1 : e.p3;
+      for (int pos = lo; pos < hi; ++pos) {  // (as in mask_multi_render: window pixels only)
+        const int k = pos >= wl0 && pos < wl0 + W ? pos - wl0 : (pos >= wr0 && pos < wr0 + W ? W + pos - wr0 : -1);
+        if (k < 0) continue;
+        const unsigned long long below = und_bits & ((1ull << k) - 1ull);
+        const double w = (und_bits >> k) & 1ull ? __longlong_as_double((long long)list[offset + __popcll(below)]) : ((in_bits >> k) & 1ull ? g.w_in : g.w_out);
+        vout[side * kMaskW + pos - lo] = w;
+      }
+    }
+    jb.lines[(size_t)item * n + line] = {e.p0, e.p1, e.p2i, e.p3, 1.0, 0.0};
+  }
+  unsigned long long handed = __ballot(in_box && !kept);
+  {
+    const unsigned long long nk = __ballot(kept);
+    const unsigned long long add = lane == 0 ? (unsigned long long)__popcll(nk) : (lane == 1 ? (unsigned long long)__popcll(handed) : (unsigned long long)total);
+    if (lane < 3 && add != 0ull) atomicAdd(stats + lane, add);
+  }
+  // the lines handed over, in ascending order: two neighbours through 16-pixel windows, one line through 32-pixel ones, the scan
+  while (handed) {
+    const int l = (int)__ffsll((long long)handed) - 1;
+    handed &= handed - 1;
+    if (jobs.pairs != 0 && l < 63 && ((handed >> (l + 1)) & 1ull) && mask_multi_render<2>(jobs, jb, item, first + l, lane)) {
+      handed &= handed - 1;
+      continue;
+    }
+    if (jobs.windows != 0 && mask_multi_render<1>(jobs, jb, item, first + l, lane)) continue;
+    mask_line_render<0>(jobs, jb, item, first + l, lane);
   }
 }
 
