@@ -630,6 +630,43 @@ enum { PAOS_DETECTOR_PLACED_ITEM = 5 };  /* dx, dy, w, x0, y0 */
 int paos_detector_add_placed(paos_ctx* ctx, const double* per_item);
 int paos_detector_images_placed(paos_ctx* ctx, const double* per_item, double* host_out);
 
+/* ---- pointing series: detector frames and box flux of the kept PSFs while the line of sight moves (README.md, "Pointing series") - */
+/* No reference counterpart.  The series carries its own detector (geom[PAOS_DETECTOR_GEOM], what paos_detector_begin takes)
+ * and neither reads nor writes the context's detector state: the accumulator and the geometry of paos_detector_begin
+ * survive a call untouched.  per_item[batch][PAOS_SERIES_ITEM] = dx, dy, x0, y0: the item's samplings and the image-plane
+ * position of its grid centre; offsets[frames][2] (per_item_offsets == 0: one list for every item) or
+ * offsets[batch][frames][2] = (ox_t, oy_t) in metres.  In frame t item i's grid centre lies at X = fl(x0_i + ox_t),
+ * Y = fl(y0_i + oy_t), the detector centre seen from the item at fl(xc - X), fl(yc - Y); everything else is the definition
+ * of the detector images above, and pixel (n, m) is formed in the order of its two contractions:
+ *   a = 0;  for k ascending over the grid rows under detector row n:  fy = min(k + 1, e1y) - max(k, e0y), skipped unless > 0;
+ *     r = 0;  for j ascending over the grid columns under detector column m:  r = r + P[k][j] fx  where fx > 0;   a = a + r fy
+ * so that frame t of item i equals paos_detector_images_placed on the same detector with (x0, y0) = (X, Y) bit for bit (zero
+ * offsets and origins: paos_detector_images); with a response g[ny][nx] (pixel gains) every value is multiplied by
+ * g[n][m], rounded once.  A frame whose footprint misses the grid is exact zeros and reads nothing.
+ * boxes[nboxes][4] = m0, m1, n0, n1: half-open boxes of detector pixels (columns m0 .. m1-1, rows n0 .. n1-1), and
+ * flux[i][t][a] the sum of the frame over box a in a fixed order: with q counting the box's pixels row-major, lane l of 64
+ * adds the pixels q = l, l + 64, ... in ascending order starting from +0.0; the 64 partial sums are combined by the tree
+ * p[l] = p[l] + p[l + s] for s = 32, 16, 8, 4, 2, 1; p[0] is the flux.  No atomics: a flux does not depend on the batch size,
+ * the item's place in the batch, the chunking or what else is asked for.  Everything is fp64 in fp32 contexts too.
+ * The frames go through a device buffer of at most PAOS_DETECTOR_SCRATCH_MIB (the environment's PAOS_SERIES_SCRATCH_BYTES,
+ * read at every call, overrides it) in chunks: as many whole frames of every item as fit, at least one -- or, if one frame
+ * of every item does not fit, one frame of as many items as do, at least one.  Chunks run in frame order on the context's
+ * stream.  With host_frames == NULL the call enqueues only; otherwise every chunk is copied to
+ * host_frames[batch][frames][ny][nx] and the call synchronises.  Scratch is kept in the context, regrown when needed, and
+ * freed with it.  PAOS_EINVAL, nothing touched and the context left usable: before any PSF is kept; null geom, per_item or
+ * offsets; a geometry paos_detector_begin refuses; a dx or dy that is not finite and positive; an x0, y0, offset, x0 + ox
+ * or xc - X (y alike) that is not finite; frames outside 1 .. 65536; nboxes outside 0 .. 16; nboxes == 0 with a null
+ * host_frames (nothing to compute); nboxes > 0 with null boxes; an empty box or one outside [0, nx) x [0, ny); a response
+ * value that is not finite.  PAOS_EHIP for a failed allocation. */
+enum { PAOS_SERIES_ITEM = 4 };  /* dx, dy, x0, y0 */
+enum { PAOS_SERIES_MAX_FRAMES = 65536, PAOS_SERIES_MAX_BOXES = 16 };
+int paos_series_compute(paos_ctx* ctx, const double* geom, const double* per_item, const double* offsets, int frames,
+                        int per_item_offsets, const int* boxes, int nboxes, const double* response, double* host_frames);
+/* flux[batch][frames][nboxes] of the last paos_series_compute, in one copy.  Synchronises.  The fluxes are a snapshot of
+ * the PSF buffer at compute time: nothing tracks later stores (as paos_zoom_fetch).  PAOS_EINVAL before a compute, after a
+ * compute with nboxes == 0, and for a null pointer. */
+int paos_series_fetch(paos_ctx* ctx, double* flux);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,11 @@ walk and behind a blur (README.md, "Encircled energy").
 ``run_batch(..., wavefront=WavefrontFit(terms, radius, surfaces=(num,)))`` answers the pupil-side questions: the Zernike
 coefficients, RMS and peak-to-valley OPD and the Strehl ratio of the field at saved surfaces, from sums formed on the GPU
 (README.md, "Wavefront fits"); ``WFO.fit_zernikes`` does the same for the drop-in class.
+
+``run_batch(..., pointing=PointingSeries(det, offsets, apertures=[(m0, m1, n0, n1)], response=gains))`` gives the time
+series of a moving line of sight: the flux of every frame inside boxes of detector pixels whose gains differ (and, with
+``frames=True``, the frames), made on the GPU from the kept PSFs; only the fluxes cross to the host (README.md, "Pointing
+series").
 """
 from .abcd import ABCD
 from .coordinate_break import coordinate_break
@@ -41,7 +46,7 @@ from .zernike import Zernike
 
 from .raytrace import raytrace
 
-__all__ = ["ABCD", "Detector", "EnergyProfile", "PsfBlur", "PsfWindow", "WFO", "WavefrontFit", "Zernike", "coordinate_break", "parse_config", "raytrace",
+__all__ = ["ABCD", "Detector", "EnergyProfile", "PointingSeries", "PsfBlur", "PsfWindow", "WFO", "WavefrontFit", "Zernike", "coordinate_break", "parse_config", "raytrace",
            "run_batch", "run_broadband", "run_sharded"]
 __version__ = "0.1.0"
 
@@ -62,6 +67,8 @@ def __getattr__(name):
         return importlib.import_module(".blur", __name__).PsfBlur
     if name == "EnergyProfile":
         return importlib.import_module(".energy", __name__).EnergyProfile
+    if name == "PointingSeries":
+        return importlib.import_module(".pointing", __name__).PointingSeries
     if name == "WavefrontFit":
         return importlib.import_module(".wavefront", __name__).WavefrontFit
     if name == "PsfWindow":

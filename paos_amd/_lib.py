@@ -27,6 +27,7 @@ MAX_PW = 6
 OTF_MTF, OTF_COMPLEX = 0, 1  # paos_otf_fetch: |OTF| as doubles / the complex OTF
 EE_GIVEN, EE_CENTROID, EE_PEAK = 0, 1, 2  # paos_ee_compute: where the circles of an item are centred
 EE_ITEM, EE_SUMMARY, EE_MAX_BINS = 4, 9, 1024
+SERIES_ITEM, SERIES_MAX_FRAMES, SERIES_MAX_BOXES = 4, 65536, 16  # paos_series_compute: dx, dy, x0, y0 per item
 WF_UNIFORM, WF_INTENSITY = 0, 1  # paos_wavefront_fit: the weighting of the sums
 WF_SUMMARY, WF_MAX_TERMS = 10, 63  # count, r_re, r_im, sum sqrt(I), sum I, phi_min, phi_max, fallback, sum w, sum w phi
 ZOOM_PSF, ZOOM_FIELD = 0, 1  # paos_zoom_fetch: |u|^2 of the window as doubles / the complex window
@@ -102,6 +103,9 @@ SYMBOLS = {
     "paos_blur_apply": (ctypes.c_int, [_c_ctx, _dbl_p]),
     "paos_ee_compute": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dbl_p]),
     "paos_ee_fetch": (ctypes.c_int, [_c_ctx, _dbl_p, _dbl_p]),
+    "paos_series_compute": (ctypes.c_int, [_c_ctx, _dbl_p, _dbl_p, _dbl_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                           ctypes.c_int, _dbl_p, _dbl_p]),
+    "paos_series_fetch": (ctypes.c_int, [_c_ctx, _dbl_p]),
     "paos_wavefront_fit": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, _dbl_p, _dbl_p, ctypes.c_int, ctypes.c_int, _dbl_p,
                                           ctypes.c_int, ctypes.c_int, _dbl_p]),
     "paos_wavefront_fetch": (ctypes.c_int, [_c_ctx, _dbl_p, _dbl_p]),
@@ -763,6 +767,47 @@ class DeviceFields:
         out = np.empty(shape, dtype=np.float64) if curves else None
         self._check(self._lib.paos_ee_fetch(self._ctx, _dptr(summary), _dptr(out) if curves else None), "paos_ee_fetch")
         return summary, out
+
+    # -- pointing series (paos_series_*: README.md, "Pointing series") -------------------------------------------------
+    def series_compute(self, det, dxs, dys, offsets, boxes=(), response=None, origins=None, frames=False):
+        """Detector frames of every item's kept PSF on ``det`` (a :class:`paos_amd.detector.Detector`; the context's own
+        detector state is neither read nor written) while the line of sight moves by ``offsets`` ((T, 2), or (batch, T, 2)
+        per item; metres) about ``origins`` ((batch, 2); None: the origin), and the flux of every frame inside ``boxes``
+        (up to 16 of ``(m0, m1, n0, n1)``: columns m0 .. m1-1, rows n0 .. n1-1), each frame multiplied by ``response``
+        ((ny, nx) pixel gains) when given.  ``frames=True`` returns the frames, (batch, T, ny, nx) float64, and
+        synchronises; otherwise the call enqueues only and returns None.  ``series_fetch`` reads the fluxes."""
+        per_item = np.empty((self.batch, SERIES_ITEM), dtype=np.float64)
+        per_item[:, 0] = np.broadcast_to(np.asarray(dxs, dtype=np.float64), (self.batch,))
+        per_item[:, 1] = np.broadcast_to(np.asarray(dys, dtype=np.float64), (self.batch,))
+        per_item[:, 2:] = 0.0 if origins is None else np.broadcast_to(np.asarray(origins, dtype=np.float64), (self.batch, 2))
+        off = np.ascontiguousarray(offsets, dtype=np.float64)
+        if off.ndim not in (2, 3) or off.shape[-1] != 2 or (off.ndim == 3 and off.shape[0] != self.batch):
+            raise ValueError(f"offsets must have shape (T, 2) or ({self.batch}, T, 2), got {off.shape}")
+        nframes = int(off.shape[-2])
+        bx = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 4))
+        geom = np.ascontiguousarray(det.geometry(), dtype=np.float64)
+        resp = None
+        if response is not None:
+            resp = np.ascontiguousarray(response, dtype=np.float64)
+            if resp.shape != (det.ny, det.nx):
+                raise ValueError(f"the response must have shape ({det.ny}, {det.nx}), got {resp.shape}")
+        out = np.empty((self.batch, nframes, det.ny, det.nx), dtype=np.float64) if frames else None
+        self._check(self._lib.paos_series_compute(self._ctx, _dptr(geom), _dptr(per_item), _dptr(off), nframes, int(off.ndim == 3),
+                                                  bx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if len(bx) else None, len(bx),
+                                                  _dptr(resp) if resp is not None else None, _dptr(out) if frames else None),
+                    "paos_series_compute")
+        self._series_shape = (self.batch, nframes, len(bx))
+        return out
+
+    def series_fetch(self):
+        """The fluxes of the last ``series_compute``, (batch, T, boxes) float64, in one copy.  Synchronises.  Refused
+        (``PaosHipError``) before a compute and after one without boxes."""
+        shape = getattr(self, "_series_shape", None)
+        if shape is None or shape[2] == 0:
+            raise PaosHipError("paos_series_fetch failed (1): no series with boxes computed (paos_series_compute)")
+        out = np.empty(shape, dtype=np.float64)
+        self._check(self._lib.paos_series_fetch(self._ctx, _dptr(out)), "paos_series_fetch")
+        return out
 
     # -- wavefront fits (paos_wavefront_*: README.md, "Wavefront fits") ----------------------------------------------
     def wavefront_fit(self, nmax, kdim, table, blocks, poly, weight=WF_UNIFORM, min_intensity=None, pupil=False):

@@ -474,6 +474,11 @@ int paos_ctx_destroy(paos_ctx* c) {
   if (c->det_out) (void)hipFree(c->det_out);
   if (c->ee_buf) (void)hipFree(c->ee_buf);
   if (c->wf_buf) (void)hipFree(c->wf_buf);
+  if (c->series_par) (void)hipFree(c->series_par);
+  if (c->series_flux) (void)hipFree(c->series_flux);
+  if (c->series_frames) (void)hipFree(c->series_frames);
+  if (c->series_host) (void)hipHostFree(c->series_host);
+  if (c->series_ev) (void)hipEventDestroy(c->series_ev);
   for (int i = 0; i < 2; ++i) {
     if (c->bounce[i]) (void)hipHostFree(c->bounce[i]);
     if (c->bounce_ev[i]) (void)hipEventDestroy(c->bounce_ev[i]);

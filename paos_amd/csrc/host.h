@@ -3,7 +3,7 @@
 // The host side of the library is split by what it launches: context.hip (contexts, the parameter arena, errors,
 // the launch timer), passes.hip (pass programs; what a program launches is planned in plain C++: pass_program.h on the
 // records of pass_records.h), generic_pass.hip and frugal_<family>.hip (the pass kernels), paos_hip.hip (the pointwise entry points: every kernel of pointwise.h) and the products: focus_otf.hip, zoom.hip,
-// detector.hip, energy.hip, wavefront.hip.  Here: the build-time layout, the context, the error and launch helpers, the dispatchers that turn what a
+// detector.hip, energy.hip, wavefront.hip, series.hip.  Here: the build-time layout, the context, the error and launch helpers, the dispatchers that turn what a
 // context is at run time into template arguments (dispatch_n: the grid size; dispatch_layout / dispatch_block_rows: element
 // type and block height; with pass_records.h's dispatch_family: the families of the frugal pass kernel -- every launch is
 // written once, inside a generic lambda), and the declarations of the functions
@@ -172,6 +172,20 @@ struct paos_ctx {
   size_t wf_bytes = 0;
   int wf_pairs = 0;
   bool wf_fitted = false;
+  // pointing series (paos_series_compute): the parameters of the last call (per-item records | offsets | boxes | response;
+  // staged in series_host, pinned, which series_ev guards until the copy has run), the fluxes [batch][frames][nboxes]
+  // and the frames of one chunk -- each allocated on first use and again when a request needs more
+  double* series_par = nullptr;
+  size_t series_par_bytes = 0;
+  double* series_host = nullptr;
+  size_t series_host_bytes = 0;
+  hipEvent_t series_ev = nullptr;
+  double* series_flux = nullptr;
+  size_t series_flux_bytes = 0;
+  double* series_frames = nullptr;
+  size_t series_frames_bytes = 0;
+  int series_nframes = 0, series_nboxes = 0;
+  bool series_done = false;
   void* bounce[2] = {nullptr, nullptr};  // pinned host buffers for device -> pageable host copies
   hipEvent_t bounce_ev[2] = {nullptr, nullptr};
   void* field = nullptr;

@@ -1297,7 +1297,7 @@ def _plan_focus(states, chains, focus_planes, last_key):
 
 
 # The products of the last surface -- a blur of the kept PSFs (blur.PsfBlur), their energy curves (energy.EnergyProfile),
-# detector images, transfer functions, zoomed windows (zoom.PsfWindow) -- share one
+# pointing series (pointing.PointingSeries), detector images, transfer functions, zoomed windows (zoom.PsfWindow) -- share one
 # method: ``attach(dev, recs, dxs, dys)`` gives ``recs[i]`` item i's entries from what ``dev`` holds right now (the kept
 # PSFs: ``reads_psf``, or the field) on the samplings ``dxs`` / ``dys``.  ``_attach_products`` walks them.
 class _DetectorRequest:
@@ -1421,7 +1421,7 @@ def _focus_stack(dev, focus, outputs, metrics_radii_px, power, products):
 def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, precision="fp64",
               device=0, outputs=("psf",), dev=None, sync=True, stats=None, metrics_radii_px=None,
               keep_psf=False, power=True, detector=None, detector_weights=None, detector_origin=None, focus_planes=None,
-              mtf_cuts=False, psf_zoom=None, psf_blur=None, psf_energy=None, wavefront=None):
+              mtf_cuts=False, psf_zoom=None, psf_blur=None, psf_energy=None, wavefront=None, pointing=None):
     """Propagate ``B = len(opt_chains)`` wavefronts together on one GPU.
 
     ``wavelengths[i]`` / ``opt_chains[i]`` describe wavefront ``i`` (chains must
@@ -1539,6 +1539,21 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     ``metrics_radii_px``; focus planes get nothing.  ``ValueError``, before anything is launched: an argument that is not
     a ``WavefrontFit``; ``sync=False``; a named surface that is not a saved surface of every chain; two requests that
     name the same surface; per-item values of another length than the batch.
+
+    ``pointing`` (a :class:`paos_amd.PointingSeries`) adds the time series of a moving line of sight from every item's
+    kept PSF at the LAST surface, which must be saved, made on the GPU (README.md, "Pointing series"; it implies
+    ``keep_psf``): for each of its T offsets the PSF is rebinned onto the series' own detector with the item's grid centre
+    at origin + offset, multiplied by the pixel response and summed inside its boxes of detector pixels in a fixed order
+    (``paos_series_compute``; the fluxes come back in one copy, ``paos_series_fetch``).  The last surface's record gets
+    ``'series_flux'`` (T, A), ``'series_offsets'`` (T, 2) and, with ``frames=True``, ``'series_frames'`` (T, ny, nx), each
+    frame equal to the ``'detector'`` image placed there bit for bit (times the response).  It reads the kept PSFs: it is
+    attached behind ``psf_blur`` and ``psf_energy`` (behind a blur the frames are those of ``P'``), ``outputs=()`` stays on
+    the lean walk, and with ``focus_planes`` every plane's dict gets the same keys (the ``dz == 0.0`` plane's equal the
+    nominal record's bit for bit).  It is independent of ``detector``, ``detector_weights`` and ``detector_origin``: the
+    series carries its own detector and origin, and their results do not change by a bit.  ``ValueError``, before anything
+    is launched: an argument that is not a ``PointingSeries``; ``sync=False``; a last surface that is not saved; per-item
+    offsets or an origin array for another batch size; ``psf_blur`` with a ``pixel`` aperture (the rebinning already
+    integrates over the pixel).
     """
     nb = len(opt_chains)
     if len(wavelengths) != nb:
@@ -1572,7 +1587,18 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
             raise ValueError("psf_energy synchronises: it cannot be combined with sync=False")
         _need_saved_last(opt_chains, last_key, "psf_energy needs")
         psf_energy.check(nb, int(gridsize))
-    wf_at = _plan_wavefront(wavefront, opt_chains, nb, sync)
+    if pointing is not None:
+        from .pointing import PointingSeries
+
+        if not isinstance(pointing, PointingSeries):
+            raise ValueError(f"pointing must be a paos_amd.PointingSeries, got {pointing!r}")
+        if not sync:
+            raise ValueError("pointing synchronises: it cannot be combined with sync=False")
+        _need_saved_last(opt_chains, last_key, "pointing needs")
+        pointing.check(nb, int(gridsize))
+        if psf_blur is not None and psf_blur.pixel is not None:
+            raise ValueError("psf_blur with a pixel aperture and a pointing series: the rebinning already integrates over the pixel")
+    wf_at =_plan_wavefront(wavefront, opt_chains, nb, sync)
     if otf:
         if not sync:
             raise ValueError("'mtf' / 'otf' outputs and mtf_cuts synchronise: they cannot be combined with sync=False")
@@ -1611,7 +1637,8 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
                 raise ValueError("detector_origin must be finite")
     det = None if detector is None else _DetectorRequest(detector, detector_weights, origins, isinstance(detector_origin, str))
     # (in the order in which they are attached: a blur rewrites the kept PSFs, so it goes before everything that reads them)
-    products = [p for p in (psf_blur, psf_energy, det, otf, psf_zoom) if p]
+    products = [p for p in (psf_blur, psf_energy, pointing, det, otf, psf_zoom) if p]
+    placed_at_chief = [p for p in (det, pointing) if p is not None and p.chief]  # their origins: the chief rays at the last surface
     keep_psf = keep_psf or any(p.reads_psf for p in products)
     fields = _fields_of(field, nb)
     states = [_Item(pupil_diameter, wl, gridsize, zoom, f) for wl, f in zip(wavelengths, fields)]
@@ -1657,8 +1684,9 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
             for i, rec in pending:
                 rec.update(fits[i])
         keep = keep_psf and key == last_key
-        if det is not None and det.chief and key == last_key:
-            det.origins = plans.chief_ray
+        if key == last_key:
+            for p in placed_at_chief:
+                p.origins = plans.chief_ray
         # the last pass has stored |u|^2 and enqueued its sum -- for this surface, or for good (inert surfaces behind it)
         fused = (lean.psf_ticket if lean.psf_ticket is not None else lean.final_ticket) if lean is not None else None
         if not power:
