@@ -667,6 +667,39 @@ int paos_series_compute(paos_ctx* ctx, const double* geom, const double* per_ite
  * compute with nboxes == 0, and for a null pointer. */
 int paos_series_fetch(paos_ctx* ctx, double* flux);
 
+/* ---- broadband series: weighted sums of frames over the items of a sweep, kept on the device (README.md, "Broadband series") */
+/* No reference counterpart.  paos_series_sum_begin opens a sum on a detector geom[PAOS_DETECTOR_GEOM] (what
+ * paos_detector_begin takes) for `frames` frames: an accumulator S[frames][ny][nx] of doubles in device memory, all +0.0
+ * (it replaces an earlier sum of the context).  Enqueues only.  frames * ny * nx may not exceed PAOS_SERIES_SUM_MAX_DOUBLES
+ * (1 GiB of accumulator): more is refused before anything is allocated.
+ * paos_series_sum_add adds the kept PSFs of the batch: per_item[batch][PAOS_SERIES_ITEM] = dx, dy, x0, y0 and
+ * offsets[frames][2] (per_item_offsets == 0) or offsets[batch][frames][2], both as for paos_series_compute; weights[batch]
+ * (per_frame_weights == 0: w[i][t] = weights[i] for every t) or weights[batch][frames].  For every (t, n, m):
+ *   a = S[t][n][m];  for i = 0 .. batch-1 ascending:  if w[i][t] == 0.0 skip, reading nothing of item i;
+ *     a = a + fl(w[i][t] F_i[t][n][m]);   S[t][n][m] = a
+ * where F_i[t][n][m] is the frame value of paos_series_compute without a response, formed by the same operations in the
+ * same order (one device function serves both kernels); the product is rounded once, then the sum.  So S does not depend
+ * on how a sweep is cut into adds as long as the items arrive in the same order; weight-0 padding adds nothing; a weight-0
+ * item whose PSF holds NaN leaves S finite; one item with weight 1 on a fresh sum gives frame t of paos_series_compute bit
+ * for bit.  Everything is fp64 in fp32 contexts too; no atomics.  Enqueues only: the parameters go up from a pinned buffer
+ * of the sum's own, guarded by an event, so a call never overwrites what the copy of the previous one still reads.
+ * paos_series_sum_flux: host_flux[frames][nboxes], the sum of S'[t] = fl(S[t] g) (response g[ny][nx]; NULL: S itself) over
+ * boxes[nboxes][4] = m0, m1, n0, n1 in the lane-and-tree order of paos_series_compute.  Synchronises.
+ * paos_series_sum_fetch: host_frames[frames][ny][nx] = S itself (no response).  Synchronises.
+ * The sum owns its buffers: the context's detector state, the accumulator of paos_detector_add and the results of the last
+ * paos_series_compute (paos_series_fetch still serves them) are left untouched, and paos_series_compute leaves S untouched.
+ * PAOS_EINVAL, nothing touched and the context left usable: a null pointer; a geometry paos_detector_begin refuses; frames
+ * outside 1 .. 65536; the size rule; add, flux or fetch before begin; add before a PSF is kept; a dx or dy that is not
+ * finite and positive; an x0, y0, offset, x0 + ox or xc - X (y alike) or weight that is not finite; nboxes outside 1 .. 16;
+ * an empty box or one outside [0, nx) x [0, ny); a response value that is not finite.  PAOS_EHIP for a failed allocation
+ * (the sum is then closed). */
+enum { PAOS_SERIES_SUM_MAX_DOUBLES = 1 << 27 };
+int paos_series_sum_begin(paos_ctx* ctx, const double* geom, int frames);
+int paos_series_sum_add(paos_ctx* ctx, const double* per_item, const double* offsets, int per_item_offsets, const double* weights,
+                        int per_frame_weights);
+int paos_series_sum_flux(paos_ctx* ctx, const int* boxes, int nboxes, const double* response, double* host_flux);
+int paos_series_sum_fetch(paos_ctx* ctx, double* host_frames);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,7 +37,9 @@ coefficients, RMS and peak-to-valley OPD and the Strehl ratio of the field at sa
 ``run_batch(..., pointing=PointingSeries(det, offsets, apertures=[(m0, m1, n0, n1)], response=gains))`` gives the time
 series of a moving line of sight: the flux of every frame inside boxes of detector pixels whose gains differ (and, with
 ``frames=True``, the frames), made on the GPU from the kept PSFs; only the fluxes cross to the host (README.md, "Pointing
-series").
+series").  With ``pointing_weights`` the frames are instead added, weighted, into a sum that the caller's device context
+keeps in HBM across the blocks of a sweep, and ``run_broadband_series(..., pointing)`` returns the broadband series: what a
+detector records over its passband while the line of sight moves (README.md, "Broadband series").
 """
 from .abcd import ABCD
 from .coordinate_break import coordinate_break
@@ -47,7 +49,7 @@ from .zernike import Zernike
 from .raytrace import raytrace
 
 __all__ = ["ABCD", "Detector", "EnergyProfile", "PointingSeries", "PsfBlur", "PsfWindow", "WFO", "WavefrontFit", "Zernike", "coordinate_break", "parse_config", "raytrace",
-           "run_batch", "run_broadband", "run_sharded"]
+           "run_batch", "run_broadband", "run_broadband_series", "run_sharded"]
 __version__ = "0.1.0"
 
 
@@ -61,7 +63,7 @@ def __getattr__(name):
         return importlib.import_module(".wfo", __name__).WFO
     if name == "run_batch":
         return importlib.import_module(".run", __name__).run_batch
-    if name in ("Detector", "run_broadband"):
+    if name in ("Detector", "run_broadband", "run_broadband_series"):
         return getattr(importlib.import_module(".detector", __name__), name)
     if name == "PsfBlur":
         return importlib.import_module(".blur", __name__).PsfBlur

@@ -28,6 +28,7 @@ OTF_MTF, OTF_COMPLEX = 0, 1  # paos_otf_fetch: |OTF| as doubles / the complex OT
 EE_GIVEN, EE_CENTROID, EE_PEAK = 0, 1, 2  # paos_ee_compute: where the circles of an item are centred
 EE_ITEM, EE_SUMMARY, EE_MAX_BINS = 4, 9, 1024
 SERIES_ITEM, SERIES_MAX_FRAMES, SERIES_MAX_BOXES = 4, 65536, 16  # paos_series_compute: dx, dy, x0, y0 per item
+SERIES_SUM_MAX_DOUBLES = 1 << 27  # paos_series_sum_begin: frames * ny * nx of the accumulator
 WF_UNIFORM, WF_INTENSITY = 0, 1  # paos_wavefront_fit: the weighting of the sums
 WF_SUMMARY, WF_MAX_TERMS = 10, 63  # count, r_re, r_im, sum sqrt(I), sum I, phi_min, phi_max, fallback, sum w, sum w phi
 ZOOM_PSF, ZOOM_FIELD = 0, 1  # paos_zoom_fetch: |u|^2 of the window as doubles / the complex window
@@ -106,6 +107,10 @@ SYMBOLS = {
     "paos_series_compute": (ctypes.c_int, [_c_ctx, _dbl_p, _dbl_p, _dbl_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                            ctypes.c_int, _dbl_p, _dbl_p]),
     "paos_series_fetch": (ctypes.c_int, [_c_ctx, _dbl_p]),
+    "paos_series_sum_begin": (ctypes.c_int, [_c_ctx, _dbl_p, ctypes.c_int]),
+    "paos_series_sum_add": (ctypes.c_int, [_c_ctx, _dbl_p, _dbl_p, ctypes.c_int, _dbl_p, ctypes.c_int]),
+    "paos_series_sum_flux": (ctypes.c_int, [_c_ctx, ctypes.POINTER(ctypes.c_int), ctypes.c_int, _dbl_p, _dbl_p]),
+    "paos_series_sum_fetch": (ctypes.c_int, [_c_ctx, _dbl_p]),
     "paos_wavefront_fit": (ctypes.c_int, [_c_ctx, ctypes.c_int, ctypes.c_int, _dbl_p, _dbl_p, ctypes.c_int, ctypes.c_int, _dbl_p,
                                           ctypes.c_int, ctypes.c_int, _dbl_p]),
     "paos_wavefront_fetch": (ctypes.c_int, [_c_ctx, _dbl_p, _dbl_p]),
@@ -354,6 +359,7 @@ class DeviceFields:
         _HIP_TOUCHED[0] = True
         self._ctx = _c_ctx()
         self.detector = None  # the geometry of the last detector_begin
+        self.series_sum = None  # (detector, frames) of the last series_sum_begin
         self.n, self.batch = int(n), int(batch)
         if precision not in ("fp64", "fp32"):
             raise ValueError("precision must be 'fp64' or 'fp32'")
@@ -807,6 +813,61 @@ class DeviceFields:
             raise PaosHipError("paos_series_fetch failed (1): no series with boxes computed (paos_series_compute)")
         out = np.empty(shape, dtype=np.float64)
         self._check(self._lib.paos_series_fetch(self._ctx, _dptr(out)), "paos_series_fetch")
+        return out
+
+    # -- broadband series (paos_series_sum_*: README.md, "Broadband series") ---------------------------------------------
+    def series_sum_begin(self, det, frames):
+        """Open a sum of ``frames`` frames on ``det`` (a :class:`paos_amd.detector.Detector`): an accumulator
+        ``S[frames][ny][nx]`` in device memory, all +0.0; it replaces an earlier sum.  Enqueues only.  ``series_sum`` is
+        ``(det, frames)`` of the open sum."""
+        geom = np.ascontiguousarray(det.geometry(), dtype=np.float64)
+        self._check(self._lib.paos_series_sum_begin(self._ctx, _dptr(geom), int(frames)), "paos_series_sum_begin")
+        self.series_sum = (det, int(frames))
+
+    def _series_sum_open(self, call):
+        opened = getattr(self, "series_sum", None)
+        if opened is None:
+            raise PaosHipError(f"{call} failed (1): no sum open (paos_series_sum_begin)")
+        return opened
+
+    def series_sum_add(self, dxs, dys, weights, offsets, origins=None):
+        """``S[t] += w[i][t] F_i[t]`` for every item in order, from the kept PSFs: ``weights`` (batch,) or (batch, T),
+        ``offsets`` (T, 2) or (batch, T, 2), ``origins`` (batch, 2) or None, as for ``series_compute``.  An item whose
+        weight is 0 is not read.  Enqueues only: nothing synchronises."""
+        _, nframes = self._series_sum_open("paos_series_sum_add")
+        per_item = np.empty((self.batch, SERIES_ITEM), dtype=np.float64)
+        per_item[:, 0] = np.broadcast_to(np.asarray(dxs, dtype=np.float64), (self.batch,))
+        per_item[:, 1] = np.broadcast_to(np.asarray(dys, dtype=np.float64), (self.batch,))
+        per_item[:, 2:] = 0.0 if origins is None else np.broadcast_to(np.asarray(origins, dtype=np.float64), (self.batch, 2))
+        off = np.ascontiguousarray(offsets, dtype=np.float64)
+        if off.shape not in ((nframes, 2), (self.batch, nframes, 2)):
+            raise ValueError(f"offsets must have shape ({nframes}, 2) or ({self.batch}, {nframes}, 2), got {off.shape}")
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape not in ((self.batch,), (self.batch, nframes)):
+            raise ValueError(f"weights must have shape ({self.batch},) or ({self.batch}, {nframes}), got {w.shape}")
+        self._check(self._lib.paos_series_sum_add(self._ctx, _dptr(per_item), _dptr(off), int(off.ndim == 3), _dptr(w), int(w.ndim == 2)),
+                    "paos_series_sum_add")
+
+    def series_sum_flux(self, boxes, response=None):
+        """The flux of every frame of the sum inside ``boxes`` (1 .. 16 of ``(m0, m1, n0, n1)``), (T, boxes) float64, each
+        frame multiplied by ``response`` ((ny, nx)) as it is read.  Synchronises."""
+        det, nframes = self._series_sum_open("paos_series_sum_flux")
+        bx = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 4))
+        resp = None
+        if response is not None:
+            resp = np.ascontiguousarray(response, dtype=np.float64)
+            if resp.shape != (det.ny, det.nx):
+                raise ValueError(f"the response must have shape ({det.ny}, {det.nx}), got {resp.shape}")
+        out = np.empty((nframes, len(bx)), dtype=np.float64)
+        self._check(self._lib.paos_series_sum_flux(self._ctx, bx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(bx),
+                                                   _dptr(resp) if resp is not None else None, _dptr(out)), "paos_series_sum_flux")
+        return out
+
+    def series_sum_fetch(self):
+        """The accumulator itself, (T, ny, nx) float64 (no response).  Synchronises."""
+        det, nframes = self._series_sum_open("paos_series_sum_fetch")
+        out = np.empty((nframes, det.ny, det.nx), dtype=np.float64)
+        self._check(self._lib.paos_series_sum_fetch(self._ctx, _dptr(out)), "paos_series_sum_fetch")
         return out
 
     # -- wavefront fits (paos_wavefront_*: README.md, "Wavefront fits") ----------------------------------------------

@@ -479,6 +479,11 @@ int paos_ctx_destroy(paos_ctx* c) {
   if (c->series_frames) (void)hipFree(c->series_frames);
   if (c->series_host) (void)hipHostFree(c->series_host);
   if (c->series_ev) (void)hipEventDestroy(c->series_ev);
+  if (c->sum_acc) (void)hipFree(c->sum_acc);
+  if (c->sum_par) (void)hipFree(c->sum_par);
+  if (c->sum_flux) (void)hipFree(c->sum_flux);
+  if (c->sum_host) (void)hipHostFree(c->sum_host);
+  if (c->sum_ev) (void)hipEventDestroy(c->sum_ev);
   for (int i = 0; i < 2; ++i) {
     if (c->bounce[i]) (void)hipHostFree(c->bounce[i]);
     if (c->bounce_ev[i]) (void)hipEventDestroy(c->bounce_ev[i]);

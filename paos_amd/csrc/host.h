@@ -186,6 +186,21 @@ struct paos_ctx {
   size_t series_frames_bytes = 0;
   int series_nframes = 0, series_nboxes = 0;
   bool series_done = false;
+  // broadband series sum (paos_series_sum_*): the accumulator S[frames][ny][nx] of the open sum with its geometry, the
+  // parameters of the last add or flux call (staged in sum_host, pinned, which sum_ev guards until the copy has run) and
+  // the fluxes [frames][nboxes] -- its own buffers: nothing of the per-item series above is shared
+  double* sum_acc = nullptr;
+  size_t sum_acc_bytes = 0;
+  int sum_nx = 0, sum_ny = 0, sum_frames = 0;
+  double sum_geom[4] = {0, 0, 0, 0};  // pitch_x, pitch_y, xc, yc
+  bool sum_open = false;
+  double* sum_par = nullptr;
+  size_t sum_par_bytes = 0;
+  double* sum_host = nullptr;
+  size_t sum_host_bytes = 0;
+  hipEvent_t sum_ev = nullptr;
+  double* sum_flux = nullptr;
+  size_t sum_flux_bytes = 0;
   void* bounce[2] = {nullptr, nullptr};  // pinned host buffers for device -> pageable host copies
   hipEvent_t bounce_ev[2] = {nullptr, nullptr};
   void* field = nullptr;

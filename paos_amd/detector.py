@@ -77,7 +77,36 @@ def run_broadband(pupil_diameter, wavelengths, weights, gridsize, zoom, field, o
     step (``run_batch`` with ``outputs=()``, the lean walk, ``keep_psf``, no synchronisation) and followed by
     ``detector_add``.  A last block that is short is filled up with its last wavelength at weight 0, which adds exact
     zeros.  Returns ``{"image": (ny, nx) float64, "power": sum_i w_i P_i (P_i: sum |u|^2 at the last surface),
-    "wavelengths", "weights"}``; the image crosses to the host once, at the end."""
+    "wavelengths", "weights"}``; the image crosses to the host once, at the end.  ``run_broadband_series`` is the same
+    sweep with the time series of a moving line of sight beside the image."""
+    return _broadband(pupil_diameter, wavelengths, weights, gridsize, zoom, field, opt_chains, detector, batch, precision, device,
+                      detector_origin, psf_blur, None, None)
+
+
+def run_broadband_series(pupil_diameter, wavelengths, weights, gridsize, zoom, field, opt_chains, detector, pointing,
+                         pointing_weights=None, batch=32, precision="fp64", device=0, detector_origin=None, psf_blur=None):
+    """``run_broadband`` with the broadband series of the sweep (README.md, "Broadband series"): every other argument, the
+    block walk and ``"image"`` / ``"power"`` are ``run_broadband``'s, bit for bit.  ``pointing`` (a
+    :class:`paos_amd.PointingSeries`; per-wavelength offsets (nw, T, 2) and origins (nw, 2) are sliced per block): every
+    block's frames are added into a sum that stays on the device, ``S[t] += w[i][t] F_i[t]``, with ``pointing_weights``
+    ((nw,) or (nw, T); None: the spectral ``weights``); the padded tail has weight 0 and is not read.  Blocks stay
+    unsynchronised unless a blur forces it.  The result gains ``"series_flux"`` (T, A) -- the flux of ``S g`` inside the
+    series' apertures, ``g`` its response --, ``"series_offsets"`` and, with ``frames=True``, ``"series_frames"``
+    (T, ny, nx) = ``S g`` (the product formed with NumPy).  The series' detector is its own and need not be ``detector``.
+    ``ValueError`` before a device context is made: a ``pointing`` that is not a ``PointingSeries``; per-item offsets or
+    origins for another number of wavelengths; weights of a wrong shape or not finite; ``psf_blur`` with a ``pixel``
+    aperture."""
+    from .pointing import PointingSeries
+
+    if not isinstance(pointing, PointingSeries):
+        raise ValueError(f"pointing must be a paos_amd.PointingSeries, got {pointing!r}")
+    return _broadband(pupil_diameter, wavelengths, weights, gridsize, zoom, field, opt_chains, detector, batch, precision, device,
+                      detector_origin, psf_blur, pointing, pointing_weights)
+
+
+def _broadband(pupil_diameter, wavelengths, weights, gridsize, zoom, field, opt_chains, detector, batch, precision, device,
+               detector_origin, psf_blur, pointing, pointing_weights):
+    """The sweep of ``run_broadband`` (``pointing`` None) and ``run_broadband_series``."""
     from . import _lib
     from .run import run_batch
 
@@ -109,6 +138,11 @@ def run_broadband(pupil_diameter, wavelengths, weights, gridsize, zoom, field, o
         if not isinstance(psf_blur, PsfBlur):
             raise ValueError(f"psf_blur must be a paos_amd.PsfBlur, got {psf_blur!r}")
         psf_blur.check(nw)
+    if pointing is not None:
+        pointing.check(nw, int(gridsize))
+        pw = pointing.weights_for(w if pointing_weights is None else pointing_weights, nw)
+        if psf_blur is not None and psf_blur.pixel is not None:
+            raise ValueError("psf_blur with a pixel aperture and a pointing series: the rebinning already integrates over the pixel")
     nb = min(int(batch), nw)
     dev = _lib.DeviceFields(int(gridsize), nb, precision, device)
     try:
@@ -130,6 +164,9 @@ def run_broadband(pupil_diameter, wavelengths, weights, gridsize, zoom, field, o
             o_blk = detector_origin if origins is None else origins[idx + [idx[-1]] * pad]
             w_blk = np.concatenate([w[idx], np.zeros(pad)])
             blur = {} if psf_blur is None else {"psf_blur": psf_blur.take(idx + [idx[-1]] * pad)}
+            if pointing is not None:
+                blur["pointing"] = pointing.take(idx + [idx[-1]] * pad)
+                blur["pointing_weights"] = np.concatenate([pw[idx], np.zeros((pad,) + pw.shape[1:])])
             res = run_batch(pupil_diameter, wl_blk, gridsize, zoom, f_blk, ch_blk, precision=precision, device=device,
                             outputs=(), dev=dev, sync=psf_blur is not None, keep_psf=True, detector=detector,
                             detector_weights=w_blk, detector_origin=o_blk, **blur)
@@ -146,9 +183,18 @@ def run_broadband(pupil_diameter, wavelengths, weights, gridsize, zoom, field, o
         image = dev.detector_fetch()
         for entry in pending:
             power += settle(entry)
+        series = {}
+        if pointing is not None:
+            nframes = pointing.offsets.shape[-2]
+            series["series_flux"] = (dev.series_sum_flux(pointing.apertures, pointing.response) if pointing.apertures
+                                     else np.zeros((nframes, 0)))
+            series["series_offsets"] = pointing.offsets.copy()
+            if pointing.frames:
+                frames = dev.series_sum_fetch()
+                series["series_frames"] = frames if pointing.response is None else frames * pointing.response
     finally:
         dev.close()
-    return {"image": image, "power": power, "wavelengths": np.asarray(wls), "weights": w.copy()}
+    return {"image": image, "power": power, "wavelengths": np.asarray(wls), "weights": w.copy(), **series}
 
 
 def _last_num(chain):

@@ -1,4 +1,5 @@
 """Pointing series: what ``run_batch(..., pointing=PointingSeries(...))`` asks for (README.md, "Pointing series")."""
+import copy
 from numbers import Integral
 
 import numpy as np
@@ -82,6 +83,39 @@ class PointingSeries:
             raise ValueError(f"per-item offsets must have shape ({batch}, T, 2), got {self.offsets.shape}")
         if not self.chief and self.origins is not None and self.origins.shape != (batch, 2):
             raise ValueError(f"origin must have shape ({batch}, 2), got {self.origins.shape}")
+
+    def take(self, idx):
+        """The series of the items ``idx`` of the batch this one was written for (a block of a longer sweep): per-item
+        offsets and origins are sliced, everything else is shared."""
+        pick = np.asarray(idx, dtype=np.int64)
+        part = copy.copy(self)
+        if self.offsets.ndim == 3:
+            part.offsets = self.offsets[pick]
+        if not self.chief and self.origins is not None:
+            part.origins = self.origins[pick]
+        return part
+
+    def weights_for(self, weights, batch, what="pointing_weights"):
+        """``weights`` of a broadband sum as a float64 array of shape (batch,) or (batch, T) -- ``ValueError`` otherwise."""
+        try:
+            w = np.array(weights, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} must be an array of shape ({batch},) or ({batch}, T), got {weights!r}") from None
+        nframes = self.offsets.shape[-2]
+        if w.shape not in ((batch,), (batch, nframes)):
+            raise ValueError(f"{what} must have shape ({batch},) or ({batch}, {nframes}), got {w.shape}")
+        if not np.all(np.isfinite(w)):
+            raise ValueError(f"{what} must be finite")
+        return w
+
+    def add_to_sum(self, dev, weights, dxs, dys):
+        """Add every item's frames, weighted, into the broadband sum of ``dev`` (README.md, "Broadband series"), which is
+        opened first when ``dev`` has none for this detector and number of frames.  Enqueues only; no record is touched."""
+        self.check(dev.batch, dev.n)
+        nframes = self.offsets.shape[-2]
+        if getattr(dev, "series_sum", None) != (self.detector, nframes):
+            dev.series_sum_begin(self.detector, nframes)
+        dev.series_sum_add(dxs, dys, weights, self.offsets, origins=self.origins)
 
     def attach(self, dev, recs, dxs, dys):
         """``recs[i]`` gets item i's entries, from the PSFs ``dev`` keeps right now.  Synchronises (one copy of the fluxes,

@@ -1297,7 +1297,8 @@ def _plan_focus(states, chains, focus_planes, last_key):
 
 
 # The products of the last surface -- a blur of the kept PSFs (blur.PsfBlur), their energy curves (energy.EnergyProfile),
-# pointing series (pointing.PointingSeries), detector images, transfer functions, zoomed windows (zoom.PsfWindow) -- share one
+# pointing series (pointing.PointingSeries; with weights: _SeriesSumRequest), detector images, transfer functions, zoomed
+# windows (zoom.PsfWindow) -- share one
 # method: ``attach(dev, recs, dxs, dys)`` gives ``recs[i]`` item i's entries from what ``dev`` holds right now (the kept
 # PSFs: ``reads_psf``, or the field) on the samplings ``dxs`` / ``dys``.  ``_attach_products`` walks them.
 class _DetectorRequest:
@@ -1319,6 +1320,19 @@ class _DetectorRequest:
         else:
             for rec, image in zip(recs, dev.detector_images(dxs, dys, **placed)):
                 rec["detector"] = image
+
+
+class _SeriesSumRequest:
+    """A pointing series added, with ``weights`` ((B,) or (B, T)), into the broadband sum of ``dev`` (paos_series_sum_*;
+    ``pointing.PointingSeries.add_to_sum``): no record is touched and nothing synchronises."""
+
+    reads_psf = True
+
+    def __init__(self, pointing, weights):
+        self.pointing, self.weights = pointing, weights
+
+    def attach(self, dev, recs, dxs, dys):
+        self.pointing.add_to_sum(dev, self.weights, dxs, dys)
 
 
 class _OtfRequest:
@@ -1421,7 +1435,8 @@ def _focus_stack(dev, focus, outputs, metrics_radii_px, power, products):
 def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, precision="fp64",
               device=0, outputs=("psf",), dev=None, sync=True, stats=None, metrics_radii_px=None,
               keep_psf=False, power=True, detector=None, detector_weights=None, detector_origin=None, focus_planes=None,
-              mtf_cuts=False, psf_zoom=None, psf_blur=None, psf_energy=None, wavefront=None, pointing=None):
+              mtf_cuts=False, psf_zoom=None, psf_blur=None, psf_energy=None, wavefront=None, pointing=None,
+              pointing_weights=None):
     """Propagate ``B = len(opt_chains)`` wavefronts together on one GPU.
 
     ``wavelengths[i]`` / ``opt_chains[i]`` describe wavefront ``i`` (chains must
@@ -1554,6 +1569,17 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
     is launched: an argument that is not a ``PointingSeries``; ``sync=False``; a last surface that is not saved; per-item
     offsets or an origin array for another batch size; ``psf_blur`` with a ``pixel`` aperture (the rebinning already
     integrates over the pixel).
+
+    ``pointing_weights`` ((B,) or (B, T) finite numbers) turns ``pointing`` into a contribution to a broadband series
+    (README.md, "Broadband series"): instead of per-item records, every item's frames are added, weighted, into the sum
+    that the caller's ``dev`` keeps in device memory, ``S[t] += w[i][t] F_i[t]`` in item order (``paos_series_sum_add``;
+    the sum is opened, ``dev.series_sum_begin``, when ``dev`` has none for this detector and T).  No record is touched and
+    nothing synchronises, so ``sync=False`` is allowed; the caller reads ``dev.series_sum_flux(boxes, response)`` and
+    ``dev.series_sum_fetch()`` when the sweep is done (the response, the apertures and ``frames`` of ``pointing`` play no
+    part in the add).  Behind ``psf_blur`` it reads ``P'``; ``origin="chief_ray"`` resolves as above.  ``ValueError``,
+    before anything is launched: weights without ``pointing``; weights without a caller-owned ``dev``; a wrong shape or
+    non-finite weights; ``focus_planes`` (what the sum should hold across planes is ambiguous); ``psf_blur`` with a
+    ``pixel`` aperture.
     """
     nb = len(opt_chains)
     if len(wavelengths) != nb:
@@ -1592,12 +1618,20 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
 
         if not isinstance(pointing, PointingSeries):
             raise ValueError(f"pointing must be a paos_amd.PointingSeries, got {pointing!r}")
-        if not sync:
+        if not sync and pointing_weights is None:
             raise ValueError("pointing synchronises: it cannot be combined with sync=False")
         _need_saved_last(opt_chains, last_key, "pointing needs")
         pointing.check(nb, int(gridsize))
+        if pointing_weights is not None:
+            pointing_weights = pointing.weights_for(pointing_weights, nb)
+            if dev is None:
+                raise ValueError("pointing_weights accumulate into `dev`: pass a DeviceFields that outlives the call")
+            if focus_planes is not None:
+                raise ValueError("focus_planes with pointing_weights: what the sum should hold across planes is ambiguous")
         if psf_blur is not None and psf_blur.pixel is not None:
             raise ValueError("psf_blur with a pixel aperture and a pointing series: the rebinning already integrates over the pixel")
+    elif pointing_weights is not None:
+        raise ValueError("pointing_weights without pointing")
     wf_at =_plan_wavefront(wavefront, opt_chains, nb, sync)
     if otf:
         if not sync:
@@ -1637,7 +1671,8 @@ def run_batch(pupil_diameter, wavelengths, gridsize, zoom, field, opt_chains, pr
                 raise ValueError("detector_origin must be finite")
     det = None if detector is None else _DetectorRequest(detector, detector_weights, origins, isinstance(detector_origin, str))
     # (in the order in which they are attached: a blur rewrites the kept PSFs, so it goes before everything that reads them)
-    products = [p for p in (psf_blur, psf_energy, pointing, det, otf, psf_zoom) if p]
+    series = pointing if pointing_weights is None else _SeriesSumRequest(pointing, pointing_weights)
+    products = [p for p in (psf_blur, psf_energy, series, det, otf, psf_zoom) if p]
     placed_at_chief = [p for p in (det, pointing) if p is not None and p.chief]  # their origins: the chief rays at the last surface
     keep_psf = keep_psf or any(p.reads_psf for p in products)
     fields = _fields_of(field, nb)
